@@ -19,8 +19,16 @@ Named workloads (BASELINE.json configs):
   --config configs3   4 persons x 8 views x 256 frames frame-sharded over 8 GPUs = 4 x 32 frames (128 problems) per GPU
   --config configs4   16-view rig x 1024 frames over 8 GPUs = 128 frames per GPU, half-width blendshape operands
 
+A plain run sets up, warms up, times --steps fits and prints the headline line.  Everything else it can
+measure - the vertex-pass roofline (HIP events, rocprofv3 PMC passes), the prior / contraction / reuse /
+end-to-end variants, the CPU baselines, the demo's spread over 48 starts - runs only with --full (and
+there the --no-pmc / --no-variants / --no-cpu-baseline switches still drop parts of it).
+--dump-outputs DIR writes what the last timed step returned (fitted parameters, final losses, closure and
+iteration counts) as DIR/*.npy, so that two builds can be compared output for output.
+
   python bench.py --gpus 1 --steps 5 --warmup 1
-  python bench.py --gpus 8                       # starts 8 ranks itself (torch.distributed.run, 127.0.0.1)
+  python bench.py --gpus 1 --steps 5 --warmup 1 --full --dump-outputs out/
+  python bench.py --gpus 8                      # starts 8 ranks itself (torch.distributed.run, 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -429,10 +437,11 @@ def cpu_baseline(model, cams, gt, conf, stages, use_vposer, vpw, budget_s=15.0):
     return out
 
 
-def end_to_end(MvFit, syn, frames=32, reps=3):
+def end_to_end(MvFit, syn, frames=32, reps=3, last=None):
     """The whole per-frame pipeline the reference times as one (code/main.py:27,91-94): keypoint / camera files -> initial
     guess -> 4-stage fit -> decoded pose -> result pkl, by mvsmplfitting_amd.batch.fit_folder on the shipped demo frame
-    (tests/golden/demo_data: 6 real views, VPoser checkpoint) replicated to `frames` frames of one serial.  Best of `reps`."""
+    (tests/golden/demo_data: 6 real views, VPoser checkpoint) replicated to `frames` frames of one serial.  Best of `reps`.
+    `last` (a dict) receives the serial's params / final_loss / n_closure of the last rep."""
     import shutil
     import tempfile
     from mvsmplfitting_amd import batch
@@ -459,6 +468,8 @@ def end_to_end(MvFit, syn, frames=32, reps=3):
                                    os.path.join(tmp, 'results_%d' % rep), vposer=vpw, engine=eng, timing=tm)
             torch.cuda.synchronize()
             wall = time.time() - t0
+            if last is not None:
+                last.update({k: res['0000'][k] for k in ('params', 'final_loss', 'n_closure')})
             if rep and (best is None or wall < best['wall_s']):
                 r = res['0000']
                 best = dict(wall_s=wall, steps_s=tm, closures=int(r['n_closure'].sum()), final_loss_median=float(np.median(r['final_loss'])))
@@ -634,6 +645,14 @@ def sdf_faces_variants(eng, model, stages, x0_d, grid, steps=2):
     return out
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array; float32 stays float32, everything else is stored as float64."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(directory, name + '.npy'), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -681,6 +700,11 @@ def main():
                          '(tests compare an N-rank run with a 1-rank run bit for bit)')
     ap.add_argument('--single-device', action='store_true',
                     help='dry run of the multi-rank path on ONE GPU: every rank uses cuda:0 (needs --dist-backend gloo)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline line does not need: vertex-pass roofline and PMC passes, variants, CPU '
+                         'baselines, the demo\'s 48-start spread (off by default: a plain run only times the fits)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step returned as DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
 
     # ---- --gpus N without a launcher: start the N ranks here (one process per GPU, torch.distributed over 127.0.0.1) ----
@@ -714,7 +738,10 @@ def main():
 
     if args.config == 'folder':
         assert world == 1, '--config folder is a single-GPU line'
-        e2e = end_to_end(MvFit, syn, frames=args.frames or 32, reps=max(1, args.steps))
+        last = {}
+        e2e = end_to_end(MvFit, syn, frames=args.frames or 32, reps=max(1, args.steps), last=last)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         print(json.dumps({'metric': 'end-to-end ms per frame (keypoint files -> initial guess -> 4-stage fit -> result files)',
                           'value': e2e['ms_per_frame_end_to_end'], 'unit': 'ms/frame', 'n_gpus': 1, 'steps': args.steps,
                           'warmup': 1, 'ms_per_step': e2e['ms_total'], 'higher_is_better': False, 'scaling': 'weak',
@@ -842,11 +869,17 @@ def main():
         # [frames_total, persons, 118] (the gather's layout: contiguous frame blocks per rank) -> [persons, frames_total, 118]
         full = gathered if world > 1 else xf.reshape(persons, B // persons, -1).transpose(0, 1)
         np.save(args.dump_gathered, full.transpose(0, 1).contiguous().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        # what the last timed fit returned: the parameters as [persons, frames_total, 118] (all ranks' frames, gathered), the
+        # per-problem statistics of this rank's batch (person-major)
+        full = gathered if world > 1 else xf.reshape(persons, B // persons, -1).transpose(0, 1)
+        dump_outputs(args.dump_outputs, dict(params=full.transpose(0, 1).contiguous(), final_loss=st['final_loss'],
+                                             n_closure=st['n_closure'], n_iter=st['n_iter']))
 
     # roofline of the dominant HBM kernel (LBS vertex pass), measured live with HIP events on the stream the kernel is
-    # launched on
+    # launched on (--full)
     roof = None
-    if not args.sparse and not demo:
+    if args.full and not args.sparse and not demo:
         in_fit = bool(passes and passes['run'] > 0)          # asynchronous fit: ring operands, non-temporal streams
         nchunks = (B + 31) // 32
         sparse_w = bool(args.skin_topk and args.skin_topk <= 4)
@@ -913,18 +946,18 @@ def main():
 
     if rank == 0:
         variants = None
-        if not args.no_variants and world == 1 and args.config == 'configs1' and args.prior == 'l2' and not sdf and not args.sparse:
+        if args.full and not args.no_variants and world == 1 and args.config == 'configs1' and args.prior == 'l2' and not sdf and not args.sparse:
             variants = prior_variants(MvFit, syn, _lib, stage_weights, model, frames, views)
             variants['time_to_solution_opt_in'] = reuse_variant(eng, _lib, stage_weights, x0_d)
             try:
                 variants['end_to_end'] = end_to_end(MvFit, syn, frames=32, reps=2)
             except Exception as e:                          # noqa: BLE001 - the headline line must not die on the extra
                 variants['end_to_end'] = {'error': repr(e)}
-        if not args.no_variants and world == 1 and sdf and args.sdf_faces == 'wired' and not demo:
+        if args.full and not args.no_variants and world == 1 and sdf and args.sdf_faces == 'wired' and not demo:
             variants = dict(variants or {})
             variants['sdf_faces'] = sdf_faces_variants(eng, model, stages, x0_d, 128)
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and args.prior != 'gmm':
+        if args.full and not args.no_cpu_baseline and world == 1 and args.prior != 'gmm':
             cpu_stages = [dict(s) for s in stages]
             port = cpu_baseline(model, cams, gt, conf, cpu_stages, args.prior == 'vposer', vpw, budget_s=8.0)
             cpu = cpu_baseline_reference(model, cams, gt, conf, cpu_stages, args.prior == 'vposer', vpw)
@@ -1027,7 +1060,7 @@ def main():
             if e_ and args.prior == 'l2':
                 out['us_per_round'][k_] = round(1e3 * e_['ms_per_step'] / max(e_['closure_rounds_per_fit'], 1), 2)
         if demo:
-            out['demo_48_starts'] = demo_spread_timing(eng, g, stages)
+            out['demo_48_starts'] = demo_spread_timing(eng, g, stages) if args.full else None
             out['reference_fit'] = dict(final_loss_fp32=float(g['fit_final32']), final_loss_fp64=float(g['fit_final64']),
                                         closures_fp32=int(g['fit_ncl32'].sum()), closures_fp64=int(g['fit_ncl64'].sum()),
                                         final_loss_spread_fp32=[float(v) for v in g['fit_spread32']],

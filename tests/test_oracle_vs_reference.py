@@ -1,17 +1,22 @@
-"""CPU, build container only: the oracle against the live reference (skips on the GPU box)."""
+"""CPU: the oracle against what the reference itself returns on the same seeded inputs (tests/golden/reference_checks.npz,
+written by the reference's own functions: oracle/make_golden_reference_checks.py)."""
+import os
+
 import numpy as np
 import pytest
 
 from mvsmplfitting_amd import synthetic as syn
 from oracle import closure_np as cn
-from oracle import ref_import as ri
-from tests.helpers import body_model, stage_weights
+from tests.helpers import GOLD, body_model, stage_weights
 
-pytestmark = pytest.mark.skipif(not ri.available(), reason='reference tree not mounted')
+TRIANGULATION_CASES = [(8, 2, 11), (3, 2, 12)]
 
 
-@pytest.mark.parametrize('use_vp', [False, True])
-def test_live_reference_fp64(use_vp):
+def _ref():
+    return np.load(os.path.join(GOLD, 'reference_checks.npz'))
+
+
+def closure_inputs(use_vp):
     model = body_model()
     cams = syn.make_camera_ring(5)
     vpw = syn.make_vposer_decoder(seed=3, gain=2.0, identity_bias=False) if use_vp else None
@@ -24,18 +29,10 @@ def test_live_reference_fp64(use_vp):
     lay, D = cn.param_layout(use_vp)
     x = np.random.default_rng(5).normal(0, 0.2, D)
     x[lay['scale'][0]] = 0.95
-    wts = stage_weights(2)
-    L, g, out = orc.closure(x, cams, gt[0], cf[0], wts, use_vposer=use_vp)
-    rp = ri.RefProblem(model, cams, gt[0], cf[0], 'float64', use_vposer=use_vp, vposer_weights=vpw)
-    Lr, gr, vr, jr = rp.eval_closure(x, wts)
-    assert abs(L - Lr) <= 1e-13 * abs(Lr)
-    assert np.abs(g - gr).max() <= 1e-11 * np.abs(gr).max()
-    assert np.abs(out['vertices'] - vr).max() < 1e-13
-    assert np.abs(out['joints'] - jr).max() < 1e-13
+    return orc, model, cams, gt, cf, x, stage_weights(2), vpw
 
 
-def test_live_reference_3d_joint_term():
-    """use_3d (fitting.py:319-324): oracle vs the reference with gt_joints3d / joints3d_conf."""
+def closure_3d_inputs():
     model = body_model()
     cams = syn.make_camera_ring(4)
     orc = cn.ClosureOracle(model, np.float64)
@@ -49,10 +46,27 @@ def test_live_reference_3d_joint_term():
     lay, D = cn.param_layout(False)
     x = rng.normal(0, 0.2, D)
     x[lay['scale'][0]] = 1.05
-    wts = stage_weights(1)
+    return orc, model, cams, gt, cf, x, stage_weights(1), j3
+
+
+@pytest.mark.parametrize('use_vp', [False, True])
+def test_live_reference_fp64(use_vp):
+    orc, model, cams, gt, cf, x, wts, vpw = closure_inputs(use_vp)
+    L, g, out = orc.closure(x, cams, gt[0], cf[0], wts, use_vposer=use_vp)
+    r = _ref()
+    Lr, gr, vr, jr = (r['closure_vp%d_%s' % (use_vp, k)] for k in ('L', 'g', 'verts', 'joints'))
+    assert abs(L - Lr) <= 1e-13 * abs(Lr)
+    assert np.abs(g - gr).max() <= 1e-11 * np.abs(gr).max()
+    assert np.abs(out['vertices'] - vr).max() < 1e-13
+    assert np.abs(out['joints'] - jr).max() < 1e-13
+
+
+def test_live_reference_3d_joint_term():
+    """use_3d (fitting.py:319-324): oracle vs the reference with gt_joints3d / joints3d_conf."""
+    orc, model, cams, gt, cf, x, wts, j3 = closure_3d_inputs()
     L, g, out = orc.closure(x, cams, gt[0], cf[0], wts, joints3d=j3)
-    rp = ri.RefProblem(model, cams, gt[0], cf[0], 'float64', joints3d=j3)
-    Lr, gr, vr, jr = rp.eval_closure(x, wts)
+    r = _ref()
+    Lr, gr = r['closure_3d_L'], r['closure_3d_g']
     assert abs(L - Lr) <= 1e-13 * abs(Lr)
     assert np.abs(g - gr).max() <= 1e-11 * np.abs(gr).max()
     L0, _, _ = orc.closure(x, cams, gt[0], cf[0], wts)
@@ -62,14 +76,12 @@ def test_live_reference_3d_joint_term():
 def test_triangulation_oracle_equals_reference_recompute3D():
     """oracle/triangulate_np.py against the reference's own function on the seeded rigs of the golden file."""
     from oracle import make_golden_triangulate as mg, triangulate_np as tn
-    ri.load()
-    from utils.recompute3D import recompute3D
-    for V, B, seed in [(8, 2, 11), (3, 2, 12)]:
+    r = _ref()
+    for V, B, seed in TRIANGULATION_CASES:
         extris, intris, kps = mg.make_case(V, B, seed)
+        ref = r['recompute3d_%d_%d_%d' % (V, B, seed)]
         for b in range(B):
-            ref = recompute3D(list(extris), list(intris), [kps[b, v][None].copy() for v in range(V)])
-            assert np.abs(tn.recompute3d(extris, intris, kps[b]) - ref).max() <= 1e-12
-
+            assert np.abs(tn.recompute3d(extris, intris, kps[b]) - ref[b]).max() <= 1e-12
 
 
 def test_oracle_full_pose_against_reference_golden():

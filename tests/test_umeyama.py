@@ -14,7 +14,6 @@ import tempfile
 import numpy as np
 import pytest
 
-from oracle import ref_import as ri
 from oracle import umeyama_np as un
 
 
@@ -34,13 +33,12 @@ def _cases(n=12, seed=0):
     return out
 
 
-@pytest.mark.skipif(not ri.available(), reason='reference tree not mounted')
 def test_restatement_equals_reference_umeyama():
-    ri.load()
-    from utils.umeyama import umeyama as ref_umeyama
+    """against utils/umeyama.umeyama's own results on these cases (tests/golden/reference_checks.npz)"""
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_checks.npz'))
     for est in (True, False):
-        for src, dst in _cases():
-            r0, t0, s0 = ref_umeyama(src.copy(), dst.copy(), est)
+        for i, (src, dst) in enumerate(_cases()):
+            r0, t0, s0 = (ref['umeyama_%d_%d_%s' % (est, i, k)] for k in 'rts')
             r1, t1, s1, _ = un.umeyama(src, dst, est)
             assert np.abs(r0 - r1).max() < 1e-12 and np.abs(t0 - t1).max() < 1e-12 and abs(s0 - s1) < 1e-12
 
