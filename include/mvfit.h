@@ -84,9 +84,13 @@ typedef struct mvfit_model {
     const float* J_regressor;        /* [24,Nv] dense */
     const int32_t* parents;          /* [24], parents[0] = -1 */
     const float* lbs_weights;        /* [Nv,24] dense */
-    const float* kp_regressor;       /* [14,Nv] dense ('smpllsp' joint_regressor, :283-286) */
+    const float* kp_regressor;       /* [14,Nv] dense ('smpllsp' joint_regressor, :283-286), or NULL: model_type 'smpl' */
     const int32_t* face_vertex_ids;  /* [5]  (code/smplx/vertex_joint_selector.py:38-43) */
-    const int32_t* joint_map;        /* [17] (code/utils/utils.py:453-457) */
+    const int32_t* joint_map;        /* [17] indices into the model's joint tensor (code/utils/utils.py:444-457):
+                                      *   with kp_regressor ('smpllsp', 'lsp14'): 0..13 regressor rows, 14..18 face vertices;
+                                      *   kp_regressor NULL ('smpl', 'coco17'): 0..23 posed skeleton joints (the translation
+                                      *   column of the chained transforms, lbs.py:316-370, + transl), 24..28 face vertices.
+                                      * An entry outside its range: MVFIT_E_ARG. */
     const int32_t* faces;            /* [Nf,3] or NULL */
     /* optional VPoser decoder (code/model/VPoser.py:188-195), NULL if unused */
     const float* vp_fc1_w; const float* vp_fc1_b;   /* [512,32],[512] */

@@ -7,7 +7,9 @@ frame of a serial fitted in ONE batched device fit (the refer
                     initial guess: triangulation over the frame's own views, the single-view depth guess when it has one)
     camera file     io_formats.load_camera_para  (utils.py:352-394)
       -> joint weights: hips 11, 12 ignored unless pose_format == 'lsp14' and use_hip (data_parser.py:340-357;
-         model_type 'smpllsp' -> 'lsp14', init.py:63-69, and fit_smpl.yaml has use_hip: true: the default here)
+         model_type 'smpllsp' -> 'lsp14', init.py:63-69, and fit_smpl.yaml has use_hip: true: the default here).
+         The format follows the model kind (smpl_to_annotation, utils.py:441-457): 'lsp14' for a model with a keypoint
+         regressor ('smpllsp'), 'coco17' for one without ('smpl': posed skeleton joints); anything else is a ValueError
       -> initial guess on the device (init_guess.py:18-106 + fix_params :190-212): init_guess.init_guess_batch
       -> staged fit of all frames at once (non_linear_solver.py:156-211), or the warm-start chain with is_seq
          (main.py:76-79, init_guess.py:137-166): sequence.fit_sequences
@@ -31,6 +33,10 @@ from . import io_formats as iof
 from .engine import MvFit, stage_weights
 from .init_guess import init_guess_batch, initial_params
 from .sequence import fit_sequences
+
+
+# pose format -> the model kind whose joint tensor it maps (reference code/utils/utils.py:441-457 smpl_to_annotation)
+POSE_FORMATS = {'lsp14': 'smpllsp', 'coco17': 'smpl'}
 
 
 def list_frames(keyp_root):
@@ -105,6 +111,12 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             timing[key] = timing.get(key, 0.0) + (_time.time() - t0)
         return _time.time()
     _t = _time.time()
+    model_type = 'smpllsp' if model.get('kp_regressor') is not None else 'smpl'
+    if pose_format not in POSE_FORMATS:
+        raise ValueError('Unknown pose format: {}'.format(pose_format))
+    if POSE_FORMATS[pose_format] != model_type:                   # utils.py:444-457
+        raise ValueError("pose_format '%s' needs a model of type '%s'; this model is of type '%s'"
+                         % (pose_format, POSE_FORMATS[pose_format], model_type))
     extris, intris = iof.load_camera_para(cam_file)
     use_vposer = vposer is not None
     flags = _lib.F_VPOSER if use_vposer else 0
@@ -230,4 +242,4 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     return results
 
 
-__all__ = ['list_frames', 'load_serial', 'fit_folder']
+__all__ = ['list_frames', 'load_serial', 'fit_folder', 'POSE_FORMATS']

@@ -777,6 +777,11 @@ __device__ __forceinline__ void keypoints_from_xs(ClosureLds& L, int tid) {
         } else {
             for (int t = L.M.kp_start[k]; t < L.M.kp_start[k + 1]; ++t) acc = fmaf(L.M.kp_w[t], L.xs[3 * L.M.kp_s[t] + a], acc);
         }
+        if (L.M.n_skel) {                                  // uniform: a model without a regressor ('smpl', coco17)
+            // posed skeleton joint = translation column of the chained transform (lbs.py:370); its selection row is empty
+            const int j = kp_joint_of(L.M, k);
+            if (j >= 0) acc = L.pose.G[j][4 * a + 3];
+        }
         L.kp[k][a] = acc + L.opt.x[X_TR + a];
     }
     __syncthreads();
@@ -1190,7 +1195,7 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
     __syncthreads();                  // L.gkp (view sums) and L.gtau are written after E4's last barrier
     // ---- E5: g_x = Ksel^T g_kp ; g_vposed = Tr^T g_x ----
     if constexpr (DEFER) {
-        static_assert(NC_MAX <= STEP_NT - 64, "E5's threads leave the last wave free");
+        static_assert(NC_MAX + NJ * 3 <= STEP_NT - 64, "E5's threads leave the last wave free");
         if (tid >= STEP_NT - 64) loss_combine<SDFW>(M, L, V, W, tid == STEP_NT - 64);
     }
     if (tid < nc_pad) {
@@ -1219,6 +1224,13 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
         L.gvp[tid] = v;
     } else if (tid < NC_MAX) {
         L.gvp[tid] = 0.f;                     // surplus columns of the transposed contraction's slices (E7 reads them unconditionally)
+    } else if (tid < NC_MAX + NJ * 3 && L.M.n_skel) {
+        // model without a regressor: g_Gt seed of joint j = sum of the g_kp of the keypoints that are its posed position,
+        // staged in L.gM (dead until E8a) for E6
+        const int i = tid - NC_MAX, j = i / 3, a = i - 3 * j;
+        float gs = 0.f;
+        for (int k = 0; k < NKP; ++k) if (kp_joint_of(L.M, k) == j) gs += L.gkp[k][a];
+        L.gM[j][a] = gs;
     }
     __syncthreads();
     PH_T(4);
@@ -1247,11 +1259,13 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
             }
             // A_j = [Gr_j | Gt_j - Gr_j J_j]:  g_Gt = g_At ; g_Gr = g_Ar - g_At J^T ; g_J = -Gr^T g_At
             const float J0 = L.pose.J[j][0], J1 = L.pose.J[j][1], J2 = L.pose.J[j][2];
+            // + the keypoints that ARE this joint's posed position (model without a regressor): their g_kp goes to g_Gt alone,
+            // not through A (staged by E5 in L.gM)
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 *reinterpret_cast<float4*>(&L.gG[j][4 * a]) =
                     make_float4(acc[3 * a + 0] - acc[9 + a] * J0, acc[3 * a + 1] - acc[9 + a] * J1,
-                                acc[3 * a + 2] - acc[9 + a] * J2, acc[9 + a]);
+                                acc[3 * a + 2] - acc[9 + a] * J2, L.M.n_skel ? acc[9 + a] + L.gM[j][a] : acc[9 + a]);
                 L.gJ[j][a] = -(L.pose.G[j][0 + a] * acc[9] + L.pose.G[j][4 + a] * acc[10] + L.pose.G[j][8 + a] * acc[11]);
             }
         }

@@ -174,16 +174,33 @@ __global__ __launch_bounds__(STEP_NT) void closure_kernel(DevModel M, const ObsB
     }
 }
 
-// keypoints only (mvfit_vertices): gather from the vertex buffer
-__global__ __launch_bounds__(64) void joints_kernel(DevModel M, const float* __restrict__ verts,
-                                                    float* __restrict__ joints) {
+// keypoints only (mvfit_vertices): gather from the vertex buffer; a skeleton keypoint (model without a regressor) from the
+// skinning transforms prep_kernel wrote: G_t = A_t + G_r J (A_j = [G_r | G_t - G_r J], lbs.py:365-368), J = J_t + J_S beta
+// formed as pose_prep_elems forms it, + transl
+__global__ __launch_bounds__(64) void joints_kernel(DevModel M, const float* __restrict__ verts, const float* __restrict__ Amat,
+                                                    const float* __restrict__ params, float* __restrict__ joints) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const ModelLds& C = *M.mlds;
     if (tid < NKP * 3) {
         const int k = tid / 3, a = tid - 3 * k;
         float s = 0.f;
-        for (int t = C.kp_start[k]; t < C.kp_start[k + 1]; ++t)
-            s = fmaf(C.kp_w[t], verts[((size_t)b * M.nv + C.sel_v[C.kp_s[t]]) * 3 + a], s);
+        const int j = kp_joint_of(C, k);
+        if (j >= 0) {
+            const float* x = params + (size_t)b * DV;
+            const float* A = Amat + (size_t)b * 288 + j * 12 + 4 * a;
+            float J[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float v = C.J_t[3 * j + c];
+#pragma unroll
+                for (int l = 0; l < 10; ++l) v = fmaf(C.J_S[3 * j + c][l], x[X_BETAS + l], v);
+                J[c] = v;
+            }
+            s = A[3] + (A[0] * J[0] + A[1] * J[1] + A[2] * J[2]) + x[X_TR + a];
+        } else {
+            for (int t = C.kp_start[k]; t < C.kp_start[k + 1]; ++t)
+                s = fmaf(C.kp_w[t], verts[((size_t)b * M.nv + C.sel_v[C.kp_s[t]]) * 3 + a], s);
+        }
         joints[(size_t)b * NKP * 3 + tid] = s;      // rows of the selection sum to 1 (+transl already in verts)
     }
 }
@@ -845,7 +862,7 @@ extern "C" int mvfit_sdf_info(const mvfit_ctx* c, int* op_path, int* term_path) 
 
 extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, const mvfit_model* m, const mvfit_options* opts) {
     if (!out || !m || !m->v_template || !m->shapedirs || !m->posedirs || !m->J_regressor || !m->parents ||
-        !m->lbs_weights || !m->kp_regressor || !m->face_vertex_ids || !m->joint_map || m->num_verts <= 0) {
+        !m->lbs_weights || !m->face_vertex_ids || !m->joint_map || m->num_verts <= 0) {
         if (out) *out = nullptr;
         return MVFIT_E_ARG;
     }
@@ -991,15 +1008,29 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
             G.J_t[j * 3 + a] = (float)s;
             for (int l = 0; l < 10; ++l) G.J_S[j * 3 + a][l] = (float)sl[l];
         }
-    // the vertices the objective reads: non-zero columns of the mapped 17 x Nv selection
+    // the vertices the objective reads: non-zero columns of the mapped 17 x Nv selection.  joint_map indexes the model's
+    // joint tensor (include/mvfit.h): with a keypoint regressor 14 regressor rows + 5 face vertices ('smpllsp'), without one
+    // 24 posed skeleton joints + 5 face vertices ('smpl') - a skeleton keypoint has an empty selection row and its joint in
+    // kp_joint (closure_device.h: keypoints_from_xs, E6)
     {
+        const bool skel = m->kp_regressor == nullptr;
+        const int n_rows = skel ? NJ : 14;                        // joints before the five face vertices
+        for (int w = 0; w < 3; ++w) G.kp_joint[w] = 0x3fffffffu;  // 31 = vertex row, six per word
+        G.n_skel = 0;
         std::vector<double> ksel((size_t)NKP * nv, 0.0);
         for (int k = 0; k < NKP; ++k) {
             const int src = m->joint_map[k];
-            if (src < 0 || src >= 19) return fail(c, MVFIT_E_ARG, "joint_map entry out of range");
-            if (src < 14) for (int v = 0; v < nv; ++v) ksel[(size_t)k * nv + v] = m->kp_regressor[(size_t)src * nv + v];
-            else {
-                const int v = m->face_vertex_ids[src - 14];
+            if (src < 0 || src >= n_rows + 5) return fail(c, MVFIT_E_ARG, "joint_map entry %d out of range (0..%d)", src, n_rows + 4);
+            if (src < n_rows) {
+                if (skel) {
+                    G.kp_joint[k / 6] &= ~(31u << (5 * (k % 6)));
+                    G.kp_joint[k / 6] |= (unsigned)src << (5 * (k % 6));
+                    ++G.n_skel;
+                } else {
+                    for (int v = 0; v < nv; ++v) ksel[(size_t)k * nv + v] = m->kp_regressor[(size_t)src * nv + v];
+                }
+            } else {
+                const int v = m->face_vertex_ids[src - n_rows];
                 if (v < 0 || v >= nv) return fail(c, MVFIT_E_ARG, "face vertex id out of range");
                 ksel[(size_t)k * nv + v] = 1.0;
             }
@@ -1010,6 +1041,7 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
             for (int k = 0; k < NKP; ++k) nz |= ksel[(size_t)k * nv + v] != 0.0;
             if (nz) sel.push_back(v);
         }
+        if (sel.empty()) return fail(c, MVFIT_E_UNSUPPORTED, "the keypoints read no vertex (joint_map names no face vertex)");
         if ((int)sel.size() > NS_MAX) return fail(c, MVFIT_E_UNSUPPORTED, "keypoint regressor touches %d vertices (max %d)", (int)sel.size(), NS_MAX);
         M.ns = (int)sel.size();
         M.nc = 3 * M.ns;
@@ -1514,7 +1546,8 @@ extern "C" int mvfit_vertices(mvfit_ctx* c, const float* params, uint32_t flags,
     rc = run_vertex_pass(c, verts);
     if (rc) return rc;
     if (joints) {
-        hipLaunchKernelGGL(joints_kernel, dim3(c->B), dim3(64), 0, c->stream, c->M, (const float*)verts, joints);
+        hipLaunchKernelGGL(joints_kernel, dim3(c->B), dim3(64), 0, c->stream, c->M, (const float*)verts, (const float*)c->P.Amat,
+                           params, joints);
         HIP_OK(c, hipGetLastError());
     }
     return MVFIT_OK;

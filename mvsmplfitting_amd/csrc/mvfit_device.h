@@ -50,7 +50,11 @@ struct ModelLds {
     float kpp_w[NKP][KP_NZ];
     int vsp_k[NS_MAX][VS_NZ];
     float vsp_w[NS_MAX][VS_NZ];
-    int padded, padx0, padx1, padx2;
+    int padded;
+    // source of each keypoint, 5 bits per keypoint, six keypoints per word (kp_joint_of): a posed skeleton joint j < 24 (model
+    // without a keypoint regressor, 'smpl' / 'coco17': keypoint = G_j's translation column + transl) or 31 = a row of the
+    // vertex selection above (every keypoint of a model with a regressor); n_skel = keypoints of the first kind
+    unsigned kp_joint[3];
     int parents[NJ];
     int nlevels;
     int level_start[NJ + 1];
@@ -66,7 +70,7 @@ struct ModelLds {
     // pointer-jumping form of the forward chain: anc_tab[s][j] = the 2^s-th ancestor of joint j (-1: above the root);
     // n_jump = steps until every path product is complete (2^n_jump >= joints on the longest path)
     int anc_tab[5][NJ];
-    int n_jump, jpad0, jpad1, jpad2;
+    int n_jump, n_skel, jpad1, jpad2;
     int ns, nc, nc_pad, pad0;
     // the selected vertices' skinning weights as <= 4 (weight, joint) pairs in ascending joint order, zero-padded (the
     // non-zero products of the dense row in the same order: the same bits); sel_sparse = 0 when a row has more than 4
@@ -75,6 +79,13 @@ struct ModelLds {
     int sel_sparse, spad0, spad1, spad2;
 };
 static_assert(sizeof(ModelLds) % 16 == 0, "ModelLds is bulk-copied as 16-byte words");
+static_assert(NKP <= 18 && NJ < 31, "kp_joint packs six 5-bit entries per word");
+
+// skeleton joint whose posed position is keypoint k, or -1 (a vertex-selection row)
+__host__ __device__ __forceinline__ int kp_joint_of(const ModelLds& C, int k) {
+    const int j = (int)((C.kp_joint[k / 6] >> (5 * (k % 6))) & 31u);
+    return j == 31 ? -1 : j;
+}
 
 struct DevModel {
     int nv, nv_pad, ntiles;

@@ -94,7 +94,8 @@ class MvFit:
         m.J_regressor = fp(model['J_regressor'])
         m.parents = ip(model['parents'])
         m.lbs_weights = fp(model['lbs_weights'])
-        m.kp_regressor = fp(model['kp_regressor'])
+        # None: model_type 'smpl' - joint_map then indexes the posed skeleton joints + face vertices (include/mvfit.h)
+        m.kp_regressor = fp(model['kp_regressor']) if model.get('kp_regressor') is not None else None
         m.face_vertex_ids = ip(model['face_vertex_ids'])
         m.joint_map = ip(model['joint_map'])
         m.faces = ip(model['faces']) if model.get('faces') is not None else None

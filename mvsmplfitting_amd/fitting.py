@@ -44,9 +44,10 @@ def _np(t, dtype=np.float32):
 
 
 def model_arrays(body_model) -> dict:
-    """The constant arrays libmvfit needs, from a reference ``SMPL`` module of the 'smpllsp' kind
-    (buffers registered by reference code/smplx/body_models_scale.py:197-305) or from a
-    :class:`BodyModel`.  Raises AttributeError naming the missing buffer otherwise."""
+    """The constant arrays libmvfit needs, from a reference ``SMPL`` module (buffers registered by reference
+    code/smplx/body_models_scale.py:197-305) or from a :class:`BodyModel`.  A module of the 'smpllsp' kind carries its
+    ``joint_regressor``; one of the 'smpl' kind has none (keypoints are its posed skeleton joints, lbs.py:370):
+    kp_regressor is then None.  Raises AttributeError naming a missing buffer otherwise."""
     if isinstance(body_model, BodyModel):
         return body_model.arrays
     sel = body_model.vertex_joint_selector.extra_joints_idxs          # vertex_joint_selector.py:38-43
@@ -55,7 +56,8 @@ def model_arrays(body_model) -> dict:
         v_template=_np(body_model.v_template), shapedirs=_np(body_model.shapedirs),
         posedirs=_np(body_model.posedirs), J_regressor=_np(body_model.J_regressor),
         parents=_np(body_model.parents, np.int32), lbs_weights=_np(body_model.lbs_weights),
-        kp_regressor=_np(body_model.joint_regressor), face_vertex_ids=_np(sel, np.int32),
+        kp_regressor=_np(body_model.joint_regressor) if hasattr(body_model, 'joint_regressor') else None,
+        face_vertex_ids=_np(sel, np.int32),
         joint_map=_np(maps, np.int32),
         faces=_np(body_model.faces_tensor, np.int32) if hasattr(body_model, 'faces_tensor') else None)
 

@@ -49,6 +49,15 @@ FACE_VERTEX_IDS = np.array([332, 2800, 6260, 583, 4071], dtype=np.int32)
 LSP_JOINT_MAP = np.array([14, 15, 16, 17, 18, 9, 8, 10, 7, 11, 6, 3, 2, 4, 1, 5, 0],
                          dtype=np.int32)
 
+# 29 = 24 posed skeleton joints + 5 face keypoints -> 17 COCO keypoints
+# (reference code/utils/utils.py:444-449, 'coco17' + 'smpl').
+COCO17_JOINT_MAP = np.array([24, 25, 26, 27, 28, 16, 17, 18, 19, 20, 21, 1, 2, 4, 5, 7, 8],
+                            dtype=np.int32)
+
+# joint weights per pose format: the hips (11, 12) only take part with 'lsp14' and use_hip
+# (reference code/utils/data_parser.py:340-357)
+COCO17_JOINT_WEIGHTS = np.array([1.0] * 11 + [0.0, 0.0] + [1.0] * 4, dtype=np.float32)
+
 # Approximate SMPL rest-pose joint locations (metres, y up), only used to lay out
 # the synthetic skeleton.
 _REST_JOINTS = np.array([
@@ -109,7 +118,7 @@ def dense_from_triplets(rows, cols, vals, shape=(14, NUM_VERTS)):
     return m
 
 
-def make_body_model(seed: int = 0, skin_topk: int | None = None, kp_regressor=None):
+def make_body_model(seed: int = 0, skin_topk: int | None = None, kp_regressor=None, model_type: str = 'smpllsp'):
     """Synthetic SMPL-shaped model.
 
     Returns a dict of float32 / int32 arrays:
@@ -121,7 +130,14 @@ def make_body_model(seed: int = 0, skin_topk: int | None = None, kp_regressor=No
     ``skin_topk``: keep only the k largest skinning weights per vertex (real SMPL has
     <= 4 non-zeros per row); None keeps the dense softmax rows.
     ``kp_regressor``: (rows, cols, vals) triplets; default = make_lsp_regressor().
+    ``model_type``: 'smpllsp' (keypoints from the LSP regressor, joint_map = LSP_JOINT_MAP) or
+    'smpl' (keypoints = posed skeleton joints + face vertices: kp_regressor None,
+    joint_map = COCO17_JOINT_MAP; reference code/init.py:63-69).
     """
+    if model_type not in ('smpllsp', 'smpl'):
+        raise ValueError('Unknown model type: {}'.format(model_type))
+    if model_type == 'smpl' and kp_regressor is not None:
+        raise ValueError("model_type 'smpl' takes its keypoints from the skeleton: no kp_regressor")
     rng = np.random.default_rng(seed)
     sph, faces = _uv_sphere()
     assert sph.shape[0] == NUM_VERTS and faces.shape[0] == NUM_FACES
@@ -158,9 +174,11 @@ def make_body_model(seed: int = 0, skin_topk: int | None = None, kp_regressor=No
     posedirs_v = rng.normal(0.0, 0.0005, size=(NUM_VERTS, 3, NUM_POSE_BASIS))
     posedirs = posedirs_v.reshape(NUM_VERTS * 3, NUM_POSE_BASIS).T          # [207, 20670]
 
-    if kp_regressor is None:
-        kp_regressor = make_lsp_regressor()
-    kp_dense = dense_from_triplets(*kp_regressor)
+    kp_dense = None
+    if model_type == 'smpllsp':
+        if kp_regressor is None:
+            kp_regressor = make_lsp_regressor()
+        kp_dense = dense_from_triplets(*kp_regressor)
 
     f32 = np.float32
     return dict(
@@ -172,7 +190,7 @@ def make_body_model(seed: int = 0, skin_topk: int | None = None, kp_regressor=No
         lbs_weights=np.ascontiguousarray(W, f32),
         kp_regressor=kp_dense,
         face_vertex_ids=FACE_VERTEX_IDS.copy(),
-        joint_map=LSP_JOINT_MAP.copy(),
+        joint_map=(LSP_JOINT_MAP if model_type == 'smpllsp' else COCO17_JOINT_MAP).copy(),
         faces=faces,
     )
 
@@ -293,5 +311,6 @@ def model_checksum(model) -> float:
     s = 0.0
     for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'lbs_weights',
               'kp_regressor'):
-        s += float(np.abs(model[k].astype(np.float64)).sum())
+        if model[k] is not None:
+            s += float(np.abs(model[k].astype(np.float64)).sum())
     return s
