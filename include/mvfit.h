@@ -91,7 +91,7 @@ typedef struct mvfit_model {
                                       *   kp_regressor NULL ('smpl', 'coco17'): 0..23 posed skeleton joints (the translation
                                       *   column of the chained transforms, lbs.py:316-370, + transl), 24..28 face vertices.
                                       * An entry outside its range: MVFIT_E_ARG. */
-    const int32_t* faces;            /* [Nf,3] or NULL */
+    const int32_t* faces;            /* [Nf,3] or NULL; kept on the device for mvfit_render_overlay */
     /* optional VPoser decoder (code/model/VPoser.py:188-195), NULL if unused */
     const float* vp_fc1_w; const float* vp_fc1_b;   /* [512,32],[512] */
     const float* vp_fc2_w; const float* vp_fc2_b;   /* [512,512],[512] */
@@ -358,6 +358,51 @@ int mvfit_umeyama(mvfit_ctx* ctx, int B, int npts, const double* src, const doub
  *   points[B,num_points,3] dev (e.g. the vertices of mvfit_vertices, num_points = 6890) ->
  *   uv[B,V,num_points,2] dev, float pixels (the reference truncates to int32 on the host afterwards). */
 int mvfit_project_points(mvfit_ctx* ctx, const float* points, int num_points, float* uv);
+
+/* The fitted body drawn over each view's image, with the 17 model keypoints as red dots: the reference's save_images
+ * output (code/utils/utils.py:866-883 save_results -> :574-597 project_to_img -> :659-712 visualize_results ->
+ * :977-1028 Renderer.__call__, pyrender + OpenCV on the host), as a depth-tested rasteriser with a fixed operation order
+ * (csrc/render.hip; tests/render_oracle.py restates it in NumPy and reproduces the face-ID image bit for bit).
+ *   vertices[B,Nv,3] dev (e.g. mvfit_vertices); points[B,num_points,3] dev or NULL (no dots), 0 <= num_points <= 64;
+ *   image i (0 <= i < num_images) is problem image_problem[i] seen by view image_view[i] (both host arrays) with the
+ *   cameras of mvfit_set_problems (the shared rig or the per-problem cameras);
+ *   images[num_images,H,W,3] RGB uint8 dev -> out[num_images,H,W,3] dev (out == images renders in place);
+ *   face_id[num_images,H,W] int32 dev or NULL: the visible face per pixel, -1 where no face is.  1 <= H, W <= 8192.
+ * Contract (geometry without FP contraction, fp32 divides correctly rounded):
+ *   transform  p = ((R0 X + R1 Y) + R2 Z) + t row by row in fp32; u = f (px / pz) + cx, v = f (py / pz) + cy.
+ *   coverage   U = rintf(256 u), V = rintf(256 v) (int32); pixel (row y, column x) is sampled at (256 x + 128, 256 y + 128);
+ *              the three edge functions in int64, oriented by the sign of the area (area 0: no pixels); covered when all
+ *              three are >= 0 (inclusive edges).  A triangle is dropped when a vertex has pz <= znear or lies more than
+ *              16384 px outside the image; nothing is clipped.
+ *   depth      float64 from the exact edge values e_i (e_i = 0 on the edge opposite vertex i):
+ *              w = ((e0 (1/z0) + e1 (1/z1)) + e2 (1/z2)), z = area / w, rounded to fp32; drawn when znear <= z <= zfar,
+ *              [znear, zfar] = [0.05, 8000] (pyrender's default near plane; IntrinsicsCamera(zfar=8000), utils.py:998).
+ *              The visible face is the minimum of (fp32 bits of z) << 32 | face id: ties go to the lower face id.
+ *   shading    (a documented stand-in for pyrender's material, grey 0.5, one colour on all channels, no specular term)
+ *              vertex normals = normalised sum, in ascending face id, of the un-normalised (p1 - p0) x (p2 - p0) of the
+ *              vertex's faces, float64 in world space, rotated by R; at a covered pixel the normal and the camera-space
+ *              point q are interpolated with the perspective-correct barycentrics (e_i / z_i) / w, the normal normalised
+ *              and flipped when n.q > 0 (two-sided).  Nine point lights (add_pointLight, utils.py:937-950) at c + r d_k,
+ *              c / r = centre / norm of the half-extent of the axis-aligned box of the image's camera-space vertices,
+ *              d_k = (sin t cos p, sin t sin p, cos t), t in {pi/6, pi/2, 5pi/6}, p in {0, 2pi/3, 4pi/3};
+ *              s = 0.5 * 0.3 + (0.5 / pi) sum_k r^2 max(0, n.l_k) / |L_k - q|^2 (l_k the unit vector to the light);
+ *              value = floor(255 min(1, s)^(1/2.2) + 0.5).  Covered pixels take the value (opaque, visible_weight = 1),
+ *              every other pixel keeps the input bytes.
+ *   dots       drawn last (visualize_results' cv2.circle(radius 3, thickness 10) in BGR red): each point projected with
+ *              the same fp32 sequence, truncated toward zero like astype(np.int32) to (cx, cy); every pixel with
+ *              (x - cx)^2 + (y - cy)^2 <= 64 becomes (255, 0, 0).  Points with pz <= znear or more than 16384 px outside
+ *              the image are skipped.
+ * MVFIT_E_STATE: the model was created without faces (or with faces that index outside the vertices), or
+ * mvfit_set_problems has not been called.  MVFIT_E_ARG: a problem or view index out of range, H or W outside 1..8192,
+ * num_points outside 0..64, num_images < 1, or a NULL vertices / images / out / index array.  Asynchronous on the ctx
+ * stream.  Images are processed in groups of at most 64; a group's workspace (per image 8 H W bytes of visibility,
+ * 56 B x Nv of vertex records and 4 B x Nf of face list) is at most 256 MB, or one image's when a single image needs
+ * more (512 MB of visibility at 8192 x 8192: images are not tiled).  On top of that the vertex normals take
+ * 24 B x B x Nv.  Both buffers are kept in the ctx, grown to the largest call.  The result does not depend on the
+ * grouping.  A face whose pixel box exceeds 1024 pixels is rasterised by a whole workgroup instead of one thread. */
+int mvfit_render_overlay(mvfit_ctx* ctx, const float* vertices, const float* points, int num_points, int num_images,
+                         const int32_t* image_problem, const int32_t* image_view, int height, int width,
+                         const uint8_t* images, uint8_t* out, int32_t* face_id);
 
 /* The path's only collective (north_star: "RCCL over xGMI only for the final gather"; in the Python adapters it is one
  * torch.distributed.all_gather, mvsmplfitting_amd/sharding.py): all-gather over the caller's RCCL communicator on the ctx

@@ -17,13 +17,18 @@ frame of a serial fitted in ONE batched device fit (the refer
          decoded and feet / hands zeroed) and, with save_meshes, `<mesh_folder>/<serial>/<frame>/000.obj` of the model at the
          SAVED (zeroed) pose (utils.py:866-890).
 
-Images, rendering and the interactive viewer of main.py are out of scope; nothing here reads images, so
-the image height the data weight 500 / H refers to (non_linear_solver.py:150,177) is an argument.
+With save_images, the fitted body is drawn over each view's image with the 17 model keypoints as red dots
+(utils.py:866-883 -> project_to_img / visualize_results / Renderer.__call__) by the renderer of csrc/render.hip
+(MvFit.render_overlay): input `<image_root>/<serial>/<camera>/<frame>.jpg|.png` (data_parser.py's layout), output
+`<image_folder>/<serial>/<frame>/<camera>.jpg` for the views that had a keypoint file in that frame (main.py:44-66).
+The interactive viewer of main.py is out of scope; the fit itself reads no image, so the image height
+the data weight 500 / H refers to (non_linear_solver.py:150,177) is an argument.
 """
 from __future__ import annotations
 
 import os
 import warnings
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -94,15 +99,83 @@ def load_serial_joints3d(frames, person=0):
     return j3, has
 
 
+IMAGE_EXTS = ('.jpg', '.png')
+RENDER_BATCH = 64          # images per render_overlay call
+IO_WORKERS = 16            # decode / encode threads
+
+
+def image_path(image_root, serial, camera, frame):
+    """The input image of one view of one frame, or ValueError naming the paths tried."""
+    base = os.path.join(image_root, serial, camera, frame)
+    for ext in IMAGE_EXTS:
+        if os.path.isfile(base + ext):
+            return base + ext
+    raise ValueError('save_images: no image for serial %s camera %s frame %s (looked for %s)'
+                     % (serial, camera, frame, ' / '.join(base + e for e in IMAGE_EXTS)))
+
+
+def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool):
+    """jobs: [(frame index f, view v, input path, (serial, frame name, camera))]; draws problem f seen by view v over the
+    input image and writes `<out_folder>/<serial>/<frame>/<camera>.jpg`.  Returns the written paths in job order.
+    Streamed: the jobs are grouped by image size (read from the file headers) and go through in chunks of at most
+    RENDER_BATCH images - decode on the thread pool, one GPU call, encode on the thread pool.  Before the next chunk is
+    decoded, the encodes of the chunk before the current one have finished, so at most two chunks of images are held on
+    the host whatever the length of the serial."""
+    paths = [None] * len(jobs)
+    by_size = {}
+    for i, j in enumerate(jobs):
+        by_size.setdefault(iof.image_size(j[2]), []).append(i)
+
+    def wait(futures):
+        for fu in futures:
+            fu.result()
+    prev = []
+    try:
+        for (H, W), idx in sorted(by_size.items()):
+            for s0 in range(0, len(idx), RENDER_BATCH):
+                part = idx[s0:s0 + RENDER_BATCH]
+                imgs = np.empty((len(part), H, W, 3), np.uint8)
+
+                def decode(k, path):
+                    im = iof.read_image(path)
+                    if im.shape != imgs.shape[1:]:
+                        raise ValueError('save_images: %s decoded to %s, its header says %s' % (path, im.shape, (H, W)))
+                    imgs[k] = im
+                wait([pool.submit(decode, k, jobs[i][2]) for k, i in enumerate(part)])
+                out = eng.render_overlay(verts, joints, imgs, [jobs[i][0] for i in part], [jobs[i][1] for i in part])
+                out = out.cpu().numpy()
+                del imgs
+                cur = []
+                for k, i in enumerate(part):
+                    serial, frame, camera = jobs[i][3]
+                    d = os.path.join(out_folder, serial, frame)
+                    os.makedirs(d, exist_ok=True)
+                    paths[i] = os.path.join(d, camera + '.jpg')
+                    cur.append(pool.submit(iof.save_image, paths[i], out[k]))
+                del out
+                wait(prev)
+                prev = cur
+        wait(prev)
+    finally:
+        for fu in prev:
+            fu.cancel()
+    return paths
+
+
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
-               mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None):
+               mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
+               save_images=False, image_root=None, image_folder=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
     term, views_per_frame [F])}.  ``timing``: a dict that receives the wall-clock seconds of the four steps of the pipeline
     (read = directory walk + keypoint / camera files, init_guess, fit, write = decoded pose + result files [+ meshes]),
-    summed over the serials - the end-to-end figure next to the reference's only timer (code/main.py:27,91-94)."""
+    summed over the serials - the end-to-end figure next to the reference's only timer (code/main.py:27,91-94).
+    save_images: draw the fitted body (the saved parameters, as save_meshes) and its keypoints over each view's image;
+    inputs under ``image_root`` (default: the ``images`` folder next to ``keyp_root``, the reference's data layout),
+    outputs under ``image_folder`` (default ``<result_folder>/images``); a missing input image is a ValueError.  The
+    serial's result gains ``images`` [written paths] and ``timing`` a 'render' entry (decode + GPU + encode)."""
     import time as _time
 
     def _tick(key, t0):
@@ -131,6 +204,9 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     if pose_format != 'lsp14' or not use_hip:                      # data_parser.py:353-356
         jw[11] = jw[12] = 0.0
     results = {}
+    if save_images and image_root is None:
+        image_root = os.path.join(os.path.dirname(os.path.normpath(keyp_root)), 'images')
+    pool = ThreadPoolExecutor(max_workers=IO_WORKERS) if save_images else None
     try:
         _t = _tick('read', _t)
         for serial, cams, frames in list_frames(keyp_root):
@@ -140,6 +216,10 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             if V > len(extris):
                 raise ValueError('serial %s has %d camera folders, the camera file %s holds %d cameras' % (serial, V, cam_file, len(extris)))
             kp, vmask = load_serial(frames, V, return_mask=True)
+            if save_images:
+                # the views that had a keypoint file in the frame (main.py:44-66); a missing image fails before the fit
+                jobs = [(f, v, image_path(image_root, serial, cams[v], frames[f][0]), (serial, frames[f][0], cams[v]))
+                        for f in range(F) for v in range(V) if frames[f][1][v] is not None]
             if not vmask.any(1).all():
                 raise ValueError('serial %s: frames %s have no keypoint file in any camera folder'
                                  % (serial, [frames[f][0] for f in np.flatnonzero(~vmask.any(1))]))
@@ -222,12 +302,14 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
                    for f in range(F)]
             files = [iof.save_result_pkl(result_folder, serial, frames[f][0], res[f]) for f in range(F)]
-            if save_meshes:
-                # the mesh of the SAVED parameters: zeroed feet / hands, model(global_orient, transl, body_pose, betas)
+            if save_meshes or save_images:
+                # the body of the SAVED parameters: zeroed feet / hands, model(global_orient, transl, body_pose, betas)
+                # (utils.py:866-874); its joints are the keypoints save_images draws
                 xm = xf_h.copy()
                 xm[:, 13:82] = np.stack([r['body_pose'][0] for r in res])
-                verts, _ = eng.vertices(xm, flags=flags & ~_lib.F_VPOSER)
-                verts = verts.cpu().numpy()
+                verts_d, joints_d = eng.vertices(xm, flags=flags & ~_lib.F_VPOSER)
+            if save_meshes:
+                verts = verts_d.cpu().numpy()
                 for f in range(F):
                     d = os.path.join(mesh_folder or os.path.join(result_folder, 'meshes'), serial, frames[f][0])
                     os.makedirs(d, exist_ok=True)
@@ -236,10 +318,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                                    n_closure=ncl.cpu().numpy(), files=files, init=x0.cpu().numpy(), restarted=restarted,
                                    used_3d=has.copy(), views_per_frame=vmask.sum(1))
             _t = _tick('write', _t)
+            if save_images:
+                results[serial]['images'] = render_serial_images(
+                    eng, verts_d, joints_d, jobs, image_folder or os.path.join(result_folder, 'images'), pool)
+                _t = _tick('render', _t)
     finally:
+        if pool is not None:
+            pool.shutdown()
         if own:
             eng.close()
     return results
 
 
-__all__ = ['list_frames', 'load_serial', 'fit_folder', 'POSE_FORMATS']
+__all__ = ['list_frames', 'load_serial', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS']

@@ -52,6 +52,13 @@ hipError_t launch_umeyama(const double* src, const double* dst, int B, int npts,
 hipError_t launch_project_points(const DevProblems& Q, const float* pts, int N, float* uv, hipStream_t stream);
 hipError_t launch_sdf_voxelize(const int32_t* faces, int num_faces, const float* vertices, int B, int num_vertices, int G,
                                float* phi, hipStream_t stream);
+size_t render_ws_bytes(int G, int Nv, int Nf, int H, int W);
+hipError_t launch_render_normals(const float* verts, int B, int Nv, const int32_t* faces, const int32_t* vf_ptr,
+                                 const int32_t* vf_idx, double* nrm, hipStream_t stream);
+hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int* view, int n, const float* verts,
+                               const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points, int num_points,
+                               int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,
+                               hipStream_t stream);
 
 struct StageWeights { DevWeights w[MVFIT_MAX_STAGES]; };
 
@@ -746,6 +753,15 @@ struct mvfit_ctx {
     // list or lists switched off), 1 face lists, 2 walk because the lists' workspace did not fit
     int sdf_op_path = 0, sdf_term_path = 0;
     bool sdf_cull_refused = false;      // the term's workspace did not fit for the current (batch, face list)
+    // overlay rendering (mvfit_render_overlay): the model's faces and the vertex -> face CSR (faces in ascending id), kept
+    // from mvfit_create when the model has faces; the workspace grows to the largest group seen
+    int32_t* d_faces = nullptr;
+    int32_t *d_vf_ptr = nullptr, *d_vf_idx = nullptr;
+    int num_faces = 0;
+    double* d_render_nrm = nullptr;    // [B][nv][3] vertex normals of the call
+    size_t render_nrm_bytes = 0;
+    void* d_render_ws = nullptr;
+    size_t render_ws_size = 0;
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -1271,6 +1287,25 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
         c->gmm_M = m->gmm_M;
     }
     for (void* p : c->allocs) if (!p) return fail(c, MVFIT_E_HIP, "device allocation failed");
+    // faces for mvfit_render_overlay, with the vertex -> face CSR its normals gather through (a model whose faces index
+    // outside the vertices keeps none: the renderer then reports MVFIT_E_STATE, nothing else uses them)
+    if (m->faces && m->num_faces > 0) {
+        const int nf = m->num_faces;
+        bool valid = true;
+        for (size_t i = 0; i < (size_t)nf * 3 && valid; ++i) valid = m->faces[i] >= 0 && m->faces[i] < nv;
+        if (valid) {
+            std::vector<int32_t> fc(m->faces, m->faces + (size_t)nf * 3), ptr(nv + 1, 0), idx((size_t)nf * 3);
+            for (int32_t i : fc) ++ptr[i + 1];
+            for (int i = 0; i < nv; ++i) ptr[i + 1] += ptr[i];
+            std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+            for (int f = 0; f < nf; ++f)                          // ascending face id within each vertex's list
+                for (int k = 0; k < 3; ++k) idx[fill[fc[f * 3 + k]]++] = f;
+            c->d_faces = dev_upload(c, fc);
+            c->d_vf_ptr = dev_upload(c, ptr);
+            c->d_vf_idx = dev_upload(c, idx);
+            c->num_faces = nf;
+        }
+    }
     if (c->upload_failed) return fail(c, MVFIT_E_HIP, "copying the model constants to the device failed");
     HIP_OK(c, vertex_pass_configure());
     HIP_OK(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -1324,6 +1359,8 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     if (c->d_sdf_faces) hipFree(c->d_sdf_faces);
     if (c->d_sdf_op_ws) hipFree(c->d_sdf_op_ws);
     if (c->d_vp_log) hipFree(c->d_vp_log);
+    if (c->d_render_nrm) hipFree(c->d_render_nrm);
+    if (c->d_render_ws) hipFree(c->d_render_ws);
     for (void* p : c->allocs) if (p) hipFree(p);
     if (c->h_done) hipHostFree(c->h_done);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
@@ -2382,6 +2419,56 @@ extern "C" int mvfit_project_points(mvfit_ctx* c, const float* points, int num_p
     HIP_OK(c, hipSetDevice(c->device));
     hipError_t e = launch_project_points(c->Q, points, num_points, uv, c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "projection launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_render_overlay(mvfit_ctx* c, const float* vertices, const float* points, int num_points, int num_images,
+                                    const int32_t* image_problem, const int32_t* image_view, int height, int width,
+                                    const uint8_t* images, uint8_t* out, int32_t* face_id) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_render_overlay: the model was created without (valid) faces");
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first (the cameras come from there)");
+    if (!vertices || !images || !out || !image_problem || !image_view || num_images < 1 || height < 1 || height > 8192 ||
+        width < 1 || width > 8192 || num_points < 0 || num_points > 64)
+        return fail(c, MVFIT_E_ARG, "mvfit_render_overlay: bad argument (num_images=%d height=%d width=%d num_points=%d)",
+                    num_images, height, width, num_points);
+    for (int i = 0; i < num_images; ++i)
+        if (image_problem[i] < 0 || image_problem[i] >= c->B || image_view[i] < 0 || image_view[i] >= c->V)
+            return fail(c, MVFIT_E_ARG, "mvfit_render_overlay: image %d names problem %d / view %d (B=%d V=%d)", i,
+                        image_problem[i], image_view[i], c->B, c->V);
+    HIP_OK(c, hipSetDevice(c->device));
+    // images per group: at most RENDER_GROUP_MAX and a workspace of at most 256 MB - or one image's, when a single image
+    // needs more (8 H W bytes of visibility, 512 MB at 8192 x 8192; images are not tiled)
+    const size_t cap = (size_t)256 << 20;
+    int G = std::min(num_images, RENDER_GROUP_MAX);
+    while (G > 1 && render_ws_bytes(G, c->nv, c->num_faces, height, width) > cap) --G;
+    const size_t ws = render_ws_bytes(G, c->nv, c->num_faces, height, width);
+    const size_t nb = (size_t)c->B * c->nv * 3 * sizeof(double);
+    if (ws > c->render_ws_size || nb > c->render_nrm_bytes) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));             // earlier calls may still read the old buffers
+        if (ws > c->render_ws_size) {
+            if (c->d_render_ws) hipFree(c->d_render_ws);
+            c->d_render_ws = nullptr; c->render_ws_size = 0;
+            HIP_OK(c, hipMalloc(&c->d_render_ws, ws));
+            c->render_ws_size = ws;
+        }
+        if (nb > c->render_nrm_bytes) {
+            if (c->d_render_nrm) hipFree(c->d_render_nrm);
+            c->d_render_nrm = nullptr; c->render_nrm_bytes = 0;
+            HIP_OK(c, hipMalloc(&c->d_render_nrm, nb));
+            c->render_nrm_bytes = nb;
+        }
+    }
+    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->d_render_nrm, c->stream);
+    const size_t px = (size_t)height * width;
+    for (int i0 = 0; i0 < num_images && e == hipSuccess; i0 += G) {
+        const int n = std::min(G, num_images - i0);
+        e = launch_render_group(c->Q, image_problem + i0, image_view + i0, n, vertices, c->d_render_nrm, c->nv, c->d_faces,
+                                c->num_faces, points, points ? num_points : 0, height, width, images + (size_t)i0 * px * 3,
+                                out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr, c->d_render_ws,
+                                c->stream);
+    }
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "render launch: %s", hipGetErrorString(e));
     return MVFIT_OK;
 }
 

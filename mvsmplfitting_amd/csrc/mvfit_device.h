@@ -11,6 +11,7 @@ namespace mvfit {
 
 constexpr int NJ = 24;            // SMPL joints
 constexpr int NKP = 17;           // dataset keypoints
+constexpr int RENDER_GROUP_MAX = 64;   // images per launch group of mvfit_render_overlay (render.hip)
 constexpr int KROWS = 224;        // blendshape rows: 207 pose + 10 shape, padded to 28*8
 constexpr int KGROUPS = 28;       // groups of 4 MFMA k-steps (8 rows) each
 constexpr int TILE_V = 32;        // vertices per MFMA tile

@@ -424,6 +424,50 @@ class MvFit:
         self._check(self._lib.mvfit_project_points(self._ctx, p.data_ptr(), int(p.shape[1]), uv.data_ptr()))
         return uv
 
+    def render_overlay(self, vertices, points, images, problems, views, face_id=False, out=None):
+        """The body drawn over each view's image with the keypoints as red dots (include/mvfit.h:mvfit_render_overlay;
+        reference save_images, utils/utils.py:574-597,659-712,977-1028).  vertices [B, Nv, 3] (e.g. ``vertices()``),
+        points [B, P, 3] (P <= 64) or None, images uint8 [n, H, W, 3] RGB (torch tensor or NumPy array); image i is problem
+        problems[i] seen by view views[i] of set_problems' cameras.  Returns a uint8 device tensor [n, H, W, 3] (``out``:
+        a contiguous uint8 tensor of that shape on this engine's device to write into; ``out=images`` renders in place and
+        needs ``images`` to be such a tensor) and, with face_id, also the int32 [n, H, W] visible face per pixel (-1: none)."""
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[0] != self.B or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [B, %d, 3] with B = %d' % (self.nv, self.B))
+        p = None
+        if points is not None:
+            p = self._dev(points)
+            if p.dim() != 3 or p.shape[0] != self.B or p.shape[2] != 3:
+                raise MvFitError('points must be [B, P, 3] with B = %d' % self.B)
+        if isinstance(images, torch.Tensor):
+            img = images
+        else:
+            a = np.ascontiguousarray(images)
+            img = torch.from_numpy(a if a.flags.writeable else a.copy())     # (e.g. np.asarray of a PIL image)
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+            raise MvFitError('images must be uint8 [n, H, W, 3]')
+        img = img.to(self.device).contiguous()
+        n, H, W = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+        prob, view = _i32(np.asarray(problems).reshape(-1)), _i32(np.asarray(views).reshape(-1))
+        if prob.size != n or view.size != n:
+            raise MvFitError('problems and views need one entry per image (%d)' % n)
+        if out is None:
+            out = torch.empty_like(img)
+        elif out is images:
+            if img is not images:
+                raise MvFitError('out=images renders in place: images must be a contiguous uint8 tensor on %s' % self.device)
+            out = img
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != tuple(img.shape) or out.device != self.device
+              or not out.is_contiguous()):
+            raise MvFitError('out must be a contiguous uint8 device tensor of the images\' shape')
+        fid = torch.empty(n, H, W, dtype=torch.int32, device=self.device) if face_id else None
+        ip = C.POINTER(C.c_int32)
+        self._check(self._lib.mvfit_render_overlay(
+            self._ctx, v.data_ptr(), p.data_ptr() if p is not None else None, int(p.shape[1]) if p is not None else 0, n,
+            prob.ctypes.data_as(ip), view.ctypes.data_as(ip), H, W, img.data_ptr(), out.data_ptr(),
+            fid.data_ptr() if face_id else None))
+        return (out, fid) if face_id else out
+
     def gather(self, rccl_comm, send, nranks):
         """All-gather of a contiguous device tensor over a raw RCCL communicator (include/mvfit.h:mvfit_gather) - the
         entry point of hosts that own an ncclComm_t; the Python adapters use torch.distributed (sharding.py), which does

@@ -14,6 +14,11 @@ and fitted parameters written the way the reference's tools read them.
                      VPoser body_pose has the foot / hand joints zeroed ([18:24], [27:33], [57:]) before it is stored
   save_result_pkl    pickle protocol 2, `<folder>/<serial>/<fn>/000.pkl` (utils.py:859-864)
   save_obj           Wavefront obj, 1-based faces (code/utils/FileLoaders.py:154-160)
+  read_image         image file -> RGB uint8 [H,W,3], EXIF orientation applied like cv2.imread's default (the
+                     reference: cv2.imread, BGR; data_parser.py)
+  image_size         (H, W) read_image will return, from the file header (no pixel decode)
+  save_image         RGB uint8 [H,W,3] -> file, JPEG quality 95 like cv2.imwrite's default (utils.py:700-712)
+                     (both through PIL, imported when first used)
 """
 from __future__ import annotations
 
@@ -103,5 +108,38 @@ def save_obj(path, vertices, faces):
             fp.write('f %d %d %d\n' % (f[0], f[1], f[2]))
 
 
-__all__ = ['load_camera_para', 'read_keypoints', 'read_joints3d', 'problem_tensors', 'result_dict',
+def _pil():
+    try:
+        from PIL import Image
+    except ImportError as e:                     # pragma: no cover - depends on the installation
+        raise ImportError('reading and writing images needs the Pillow package (PIL), which is not installed') from e
+    return Image
+
+
+_EXIF_ORIENTATION = 0x0112
+
+
+def read_image(path):
+    from PIL import ImageOps
+    with _pil().open(path) as im:
+        return np.asarray(ImageOps.exif_transpose(im).convert('RGB'), dtype=np.uint8)
+
+
+def image_size(path):
+    with _pil().open(path) as im:                # opening reads the header only
+        w, h = im.size
+        if im.getexif().get(_EXIF_ORIENTATION, 1) in (5, 6, 7, 8):     # a quarter turn: exif_transpose swaps the axes
+            w, h = h, w
+    return h, w
+
+
+def save_image(path, rgb, quality=95):
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError('save_image: expected RGB uint8 [H, W, 3], got %s' % (a.shape,))
+    _pil().fromarray(a, 'RGB').save(path, quality=int(quality))
+    return path
+
+
+__all__ = ['read_image', 'image_size', 'save_image', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'problem_tensors', 'result_dict',
            'save_result_pkl', 'save_obj']
