@@ -1,0 +1,73 @@
+// Layout of the model constants the kernels read: the sizes their tables depend on and the ModelLds image.  Shared by the
+// device code (mvfit_device.h, vposer_service.h) and the host builder of the tables (model_prep.cpp), so it includes no
+// HIP header.
+#pragma once
+#include <stdint.h>
+
+namespace mvfit {
+
+constexpr int NJ = 24;            // SMPL joints
+constexpr int NKP = 17;           // dataset keypoints
+constexpr int KROWS = 224;        // blendshape rows: 207 pose + 10 shape, padded to 28*8
+constexpr int KGROUPS = 28;       // groups of 4 MFMA k-steps (8 rows) each
+constexpr int TILE_V = 32;        // vertices per MFMA tile
+constexpr int NS_MAX = 96;        // selected (objective-relevant) vertices
+constexpr int NS_STRIDE = 112;    // row stride of the transposed skinning weights (== 16 mod 32: the four
+                                  // 16-lane rows of a wave hit disjoint LDS banks)
+constexpr int NC_MAX = NS_MAX * 3;
+constexpr int KNNZ_MAX = 160;     // non-zeros of the 17 x ns keypoint selection
+constexpr int KP_NZ = 12;         // padded per-keypoint list length (LSP regressor rows have 4-9 non-zeros)
+constexpr int VS_NZ = 2;          // padded per-vertex list length (a vertex usually feeds one keypoint)
+constexpr int VPS_SLICES = 8;     // VPoser decoder helpers per set = slices of the 512 fc2 units (vposer_service.h)
+
+// Model constants every per-problem workgroup keeps in LDS (bulk-copied once per launch).
+struct ModelLds {
+    float wT[NJ][NS_STRIDE];          // lbs_weights of the selected vertices, transposed: wT[j][s]
+    float J_t[NJ * 3];                // J_regressor . v_template
+    float J_S[NJ * 3][11];            // J_regressor . shapedirs  (row padded to 11: conflict-free by lane)
+    float vt_sub[NC_MAX];             // v_template of the selected vertices, c = 3 s + a
+    int sel_v[NS_MAX];                // vertex id of selected vertex s
+    int kp_start[NKP + 1];            // keypoint k = sum_t kp_w[t] * xs[kp_s[t]]  (ascending s)
+    int kp_s[KNNZ_MAX];
+    float kp_w[KNNZ_MAX];
+    int vs_start[NS_MAX + 1];         // transpose: selected vertex s feeds keypoints vs_k[t] (ascending k)
+    int vs_k[KNNZ_MAX];
+    float vs_w[KNNZ_MAX];
+    // the same selection as fixed-length zero-padded lists (all index loads of a thread in one LDS round
+    // trip instead of one per CSR entry); padded = 0 when a row is longer than the padding (CSR is used)
+    int kpp_s[NKP][KP_NZ];
+    float kpp_w[NKP][KP_NZ];
+    int vsp_k[NS_MAX][VS_NZ];
+    float vsp_w[NS_MAX][VS_NZ];
+    int padded;
+    // source of each keypoint, 5 bits per keypoint, six keypoints per word (kp_joint_of): a posed skeleton joint j < 24 (model
+    // without a keypoint regressor, 'smpl' / 'coco17': keypoint = G_j's translation column + transl) or 31 = a row of the
+    // vertex selection above (every keypoint of a model with a regressor); n_skel = keypoints of the first kind
+    unsigned kp_joint[3];
+    int parents[NJ];
+    int nlevels;
+    int level_start[NJ + 1];
+    int level_joints[NJ];
+    int child_start[NJ + 1];
+    int child_list[NJ];
+    // kinematic chain schedules for ONE wave (12 lanes per joint, 5 joints per pass):
+    //   fwd_tab[pass][q] = j | parent << 8 (or -1): joints whose parent transform is complete
+    //   bwd_tab[pass][q] = parent | 0x80 if not its first entry | c0 << 8 | c1 << 16 | c2 << 24 (or -1), child 31 = none
+    int n_fwd, n_bwd;
+    int fwd_tab[NJ][5];
+    int bwd_tab[NJ][5];
+    // pointer-jumping form of the forward chain: anc_tab[s][j] = the 2^s-th ancestor of joint j (-1: above the root);
+    // n_jump = steps until every path product is complete (2^n_jump >= joints on the longest path)
+    int anc_tab[5][NJ];
+    int n_jump, n_skel, jpad1, jpad2;
+    int ns, nc, nc_pad, pad0;
+    // the selected vertices' skinning weights as <= 4 (weight, joint) pairs in ascending joint order, zero-padded (the
+    // non-zero products of the dense row in the same order: the same bits); sel_sparse = 0 when a row has more than 4
+    float selw[NS_MAX][4];
+    unsigned selj[NS_MAX];            // four joint indices, one per byte
+    int sel_sparse, spad0, spad1, spad2;
+};
+static_assert(sizeof(ModelLds) % 16 == 0, "ModelLds is bulk-copied as 16-byte words");
+static_assert(NKP <= 18 && NJ < 31, "kp_joint packs six 5-bit entries per word");
+
+}  // namespace mvfit

@@ -6,9 +6,11 @@
 //   fit_step_kernel    one closure round of the device-resident fit: objective + adjoint from the
 //                      vertex-pass output, L-BFGS state-machine advance, pose operands of the next
 //                      trial point
-//   fit_sparse_kernel  the whole fit of one problem in a single launch (objective restricted to the
-//                      vertices it reads; no vertex pass inside the loop)
+//   fit_persistent_kernel  the whole fit of one problem in a single launch: closures restricted to the vertices
+//                      the objective reads, or full closures whose vertex passes run beside it (asynchronous fit:
+//                      AsyncRing); optionally VPoser decoder helpers behind the problems' workgroups
 //   lbfgs_kat_kernel   float64 instantiation of the state machine on analytic objectives
+// Host side: the C ABI; the model's tables are built by model_prep.cpp and uploaded by mvfit_create_ex.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "closure_device.h"
+#include "model_prep.h"
 
 namespace mvfit {
 
@@ -782,13 +785,62 @@ static int fail(mvfit_ctx* c, int code, const char* fmt, ...) {
         if (e__ != hipSuccess) return fail(c, MVFIT_E_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
     } while (0)
 
+// one model table to the device (null for an empty one: a part the model does not have)
 template <typename T>
-static T* dev_upload(mvfit_ctx* c, const std::vector<T>& h) {
+static T* dev_upload(mvfit_ctx* c, const T* h, size_t n) {
+    if (n == 0) return nullptr;
     T* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(h.size(), 1) * sizeof(T)) != hipSuccess) d = nullptr;
-    c->allocs.push_back(d);                 // a null entry makes mvfit_create fail (checked after all uploads)
-    if (d && !h.empty() && hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) c->upload_failed = true;
+    if (hipMalloc(&d, n * sizeof(T)) != hipSuccess) d = nullptr;
+    c->allocs.push_back(d);                 // a null entry makes mvfit_create_ex fail (checked after all uploads)
+    if (d && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) c->upload_failed = true;
     return d;
+}
+template <typename T>
+static T* dev_upload(mvfit_ctx* c, const std::vector<T>& h) { return dev_upload(c, h.data(), h.size()); }
+template <typename D, typename T>
+static const D* dev_upload_as(mvfit_ctx* c, const std::vector<T>& h) { return reinterpret_cast<const D*>(dev_upload(c, h)); }
+
+// HostModel -> c->M and the renderer's faces; a failed allocation or copy is only recorded (mvfit_create_ex checks once)
+static void upload_model(mvfit_ctx* c, const HostModel& h) {
+    DevModel& M = c->M;
+    c->nv = M.nv = h.nv;
+    M.nv_pad = h.nv_pad;
+    M.ntiles = h.ntiles;
+    M.bs4 = dev_upload(c, h.bs4);
+    M.bs_h2 = dev_upload_as<float4>(c, h.bs_h2);
+    M.bs_scale = h.bs_scale;
+    M.half_basis = h.half_basis;
+    M.vt_planes = dev_upload(c, h.vt_planes);
+    M.wt_tiles = dev_upload(c, h.wt_tiles);
+    M.wsp_w = dev_upload_as<float4>(c, h.wsp_w);
+    M.wsp_j = dev_upload_as<int4>(c, h.wsp_j);
+    M.bs_vm = dev_upload(c, h.bs_vm);
+    M.w_vm = dev_upload(c, h.w_vm);
+    M.ns = h.ns; M.nc = h.nc; M.nc_pad = h.nc_pad;
+    M.sel_v = dev_upload(c, h.sel_v);
+    M.pd_sub = dev_upload(c, h.pd_sub);
+    M.pd_subT = dev_upload(c, h.pd_subT);
+    M.tile_sel_start = dev_upload(c, h.tile_sel_start);
+    M.tile_sel_local = dev_upload(c, h.tile_sel_local);
+    M.tile_sel_slot = dev_upload(c, h.tile_sel_slot);
+    M.mlds = dev_upload(c, &h.lds, 1);
+    M.vp_w1 = dev_upload(c, h.vp_w1); M.vp_b1 = dev_upload(c, h.vp_b1);
+    M.vp_w2 = dev_upload(c, h.vp_w2); M.vp_b2 = dev_upload(c, h.vp_b2);
+    M.vp_w3 = dev_upload(c, h.vp_w3); M.vp_b3 = dev_upload(c, h.vp_b3);
+    M.vp_w1T = dev_upload(c, h.vp_w1T); M.vp_w2T = dev_upload(c, h.vp_w2T); M.vp_w3T = dev_upload(c, h.vp_w3T);
+    M.vpt.tw2 = dev_upload_as<float4>(c, h.vp_tw2);
+    M.vpt.tw3 = dev_upload_as<float4>(c, h.vp_tw3);
+    M.vpt.w1T = M.vp_w1T; M.vpt.b1 = M.vp_b1; M.vpt.b2 = M.vp_b2;
+    c->has_vposer = h.has_vposer;
+    c->gmm_M = M.gmm_M = h.gmm_M;
+    M.gmm_means = dev_upload(c, h.gmm_means);
+    M.gmm_prec = dev_upload(c, h.gmm_prec);
+    M.gmm_precT = dev_upload(c, h.gmm_precT);
+    M.gmm_lognw = dev_upload(c, h.gmm_lognw);
+    c->d_faces = dev_upload(c, h.faces);
+    c->d_vf_ptr = dev_upload(c, h.vf_ptr);
+    c->d_vf_idx = dev_upload(c, h.vf_idx);
+    c->num_faces = h.num_faces;
 }
 
 static size_t step_lds() { return (sizeof(ClosureLds) + 15) & ~(size_t)15; }
@@ -889,423 +941,20 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
     c->device = device;
     HIP_OK(c, hipSetDevice(device));
     c->stream = (hipStream_t)hip_stream;
-    {
-        const int rc = read_options(c, opts, c->opt);
-        if (rc) return rc;
-    }
-    const int nv = m->num_verts;
-    c->nv = nv;
-    DevModel& M = c->M;
-    M.nv = nv;
-    M.ntiles = (nv + TILE_V - 1) / TILE_V;
-    M.nv_pad = M.ntiles * TILE_V;
-    if (m->parents[0] >= 0) return fail(c, MVFIT_E_ARG, "parents[0] must be -1");
+    if (const int rc = read_options(c, opts, c->opt)) return rc;
     if (persistent_lds(false) > 160 * 1024 || persistent_lds(true) > 160 * 1024)
         return fail(c, MVFIT_E_UNSUPPORTED, "LDS budget exceeded (%zu / %zu B)", persistent_lds(false), persistent_lds(true));
     static_assert(sizeof(VpHelperLds) <= sizeof(ClosureLds), "the decoder helpers share the fit kernel's dynamic LDS");
-
-    // ---- blendshape basis, re-tiled in MFMA B-operand order: [tile][coord][group][lane][4] ----
-    // element (tile T, coord k, group g, lane l, q): row p = 2*(4g+q) + (l>>5), vertex v = 32T + (l&31)
-    // rows 0..206 posedirs, 207..216 shapedirs (beta index), rest zero.
     {
-        std::vector<float> bs((size_t)M.ntiles * 3 * KGROUPS * 64 * 4, 0.f);
-        for (int T = 0; T < M.ntiles; ++T)
-            for (int k = 0; k < 3; ++k)
-                for (int g = 0; g < KGROUPS; ++g)
-                    for (int l = 0; l < 64; ++l)
-                        for (int q = 0; q < 4; ++q) {
-                            const int p = 2 * (4 * g + q) + (l >> 5);
-                            const int v = TILE_V * T + (l & 31);
-                            float val = 0.f;
-                            if (v < nv) {
-                                if (p < 207) val = m->posedirs[(size_t)p * nv * 3 + 3 * v + k];
-                                else if (p < 217) val = m->shapedirs[((size_t)v * 3 + k) * 10 + (p - 207)];
-                            }
-                            bs[((((size_t)T * 3 + k) * KGROUPS + g) * 64 + l) * 4 + q] = val;
-                        }
-        M.bs4 = dev_upload(c, bs);
-        // the same basis as split-fp16 MFMA B operands (vertex_pass.hip: lbs_vertex_pass_split_kernel):
-        // x * scale = hi + lo, scale = the power of two that brings max |x| into [2^13, 2^14)
-        M.bs_h2 = nullptr; M.bs_scale = 1.f; M.half_basis = 0;
-        // MVFIT_CONTRACTION_HALF_BASIS (BASELINE configs[4]: half-width blendshape operands): the contraction streams only the
-        // fp16 hi halves of the basis - 2 bytes per element like bf16, with 11 instead of 8 significant bits
-        M.half_basis = c->opt.contraction == MVFIT_CONTRACTION_HALF_BASIS ? 1 : 0;
-        if (c->opt.contraction != MVFIT_CONTRACTION_EXACT_FP32) {
-            float mx = 0.f;
-            for (float v : bs) mx = std::max(mx, std::fabs(v));
-            int ex = 0;
-            if (mx > 0.f) std::frexp(mx, &ex);                 // mx = f * 2^ex, f in [0.5, 1)
-            const float scale = std::ldexp(1.f, 14 - ex);       // max |x| * scale in [2^13, 2^14)
-            constexpr int NB = KROWS / 16;
-            std::vector<_Float16> h2((size_t)M.ntiles * 3 * NB * 2 * 64 * 8);
-            for (int T = 0; T < M.ntiles; ++T)
-                for (int k = 0; k < 3; ++k)
-                    for (int G16 = 0; G16 < NB; ++G16)
-                        for (int l = 0; l < 64; ++l)
-                            for (int t = 0; t < 8; ++t) {
-                                const int pr = 16 * G16 + 8 * (l >> 5) + t;
-                                const int v = TILE_V * T + (l & 31);
-                                float val = 0.f;
-                                if (v < nv) {
-                                    if (pr < 207) val = m->posedirs[(size_t)pr * nv * 3 + 3 * v + k];
-                                    else if (pr < 217) val = m->shapedirs[((size_t)v * 3 + k) * 10 + (pr - 207)];
-                                }
-                                val *= scale;
-                                const _Float16 hi = (_Float16)val;
-                                const _Float16 lo = (_Float16)(val - (float)hi);
-                                const size_t at = ((((size_t)(T * 3 + k) * NB + G16) * 2) * 64 + l) * 8 + t;
-                                h2[at] = hi;
-                                h2[at + 64 * 8] = lo;
-                            }
-            M.bs_h2 = reinterpret_cast<const float4*>(dev_upload(c, h2));
-            M.bs_scale = scale;
-        }
-        std::vector<float> vtp((size_t)3 * M.nv_pad, 0.f);
-        for (int v = 0; v < nv; ++v)
-            for (int k = 0; k < 3; ++k) vtp[(size_t)k * M.nv_pad + v] = m->v_template[3 * v + k];
-        M.vt_planes = dev_upload(c, vtp);
-        std::vector<float> wt((size_t)M.ntiles * NJ * 32, 0.f);
-        for (int v = 0; v < nv; ++v)
-            for (int j = 0; j < NJ; ++j)
-                wt[((size_t)(v / 32) * NJ + j) * 32 + (v % 32)] = m->lbs_weights[(size_t)v * NJ + j];
-        M.wt_tiles = dev_upload(c, wt);
-        // sparse skinning table when the model allows it (SMPL-family weights have <= 4 non-zeros per vertex);
-        // mvfit_options::dense_skinning keeps the dense blend (tests compare the two bit for bit)
-        {
-            bool sparse_ok = true;
-            for (int v = 0; v < nv && sparse_ok; ++v) {
-                int nz = 0;
-                for (int j = 0; j < NJ; ++j) nz += m->lbs_weights[(size_t)v * NJ + j] != 0.f;
-                sparse_ok = nz <= 4;
-            }
-            if (c->opt.dense_skinning) sparse_ok = false;
-            M.wsp_w = nullptr; M.wsp_j = nullptr;
-            if (sparse_ok) {
-                std::vector<float> sw((size_t)M.nv_pad * 4, 0.f);
-                std::vector<int> sj((size_t)M.nv_pad * 4, 0);
-                for (int v = 0; v < nv; ++v) {
-                    int t = 0;
-                    for (int j = 0; j < NJ; ++j) {
-                        const float w = m->lbs_weights[(size_t)v * NJ + j];
-                        if (w != 0.f) { sw[(size_t)v * 4 + t] = w; sj[(size_t)v * 4 + t] = j; ++t; }
-                    }
-                }
-                M.wsp_w = reinterpret_cast<const float4*>(dev_upload(c, sw));
-                M.wsp_j = reinterpret_cast<const int4*>(dev_upload(c, sj));
-            }
-        }
-        // vertex-major copies (SDF term pull-back): coefficient row order (posedirs 0..206, shapedirs 207..216)
-        std::vector<float> bsv((size_t)nv * 3 * KROWS, 0.f);
-        for (int v = 0; v < nv; ++v)
-            for (int k = 0; k < 3; ++k) {
-                float* row = &bsv[((size_t)v * 3 + k) * KROWS];
-                for (int pp = 0; pp < 207; ++pp) row[pp] = m->posedirs[(size_t)pp * nv * 3 + 3 * v + k];
-                for (int l = 0; l < 10; ++l) row[207 + l] = m->shapedirs[((size_t)v * 3 + k) * 10 + l];
-            }
-        M.bs_vm = dev_upload(c, bsv);
-        std::vector<float> wv((size_t)nv * NJ);
-        for (size_t i = 0; i < wv.size(); ++i) wv[i] = m->lbs_weights[i];
-        M.w_vm = dev_upload(c, wv);
+        HostModel h;
+        if (const int rc = prepare_model(*m, c->opt.contraction, c->opt.dense_skinning, h, c->err)) return rc;
+        upload_model(c, h);
     }
-    // ---- the LDS image of the per-problem kernels ----
-    std::vector<ModelLds> imgv(1);
-    ModelLds& G = imgv[0];
-    memset(&G, 0, sizeof(G));
-    // joints as an affine function of beta (float64 accumulation on the host)
-    for (int j = 0; j < NJ; ++j)
-        for (int a = 0; a < 3; ++a) {
-            double s = 0.0, sl[10] = {0};
-            for (int v = 0; v < nv; ++v) {
-                const double w = m->J_regressor[(size_t)j * nv + v];
-                if (w == 0.0) continue;
-                s += w * m->v_template[3 * v + a];
-                for (int l = 0; l < 10; ++l) sl[l] += w * m->shapedirs[((size_t)v * 3 + a) * 10 + l];
-            }
-            G.J_t[j * 3 + a] = (float)s;
-            for (int l = 0; l < 10; ++l) G.J_S[j * 3 + a][l] = (float)sl[l];
-        }
-    // the vertices the objective reads: non-zero columns of the mapped 17 x Nv selection.  joint_map indexes the model's
-    // joint tensor (include/mvfit.h): with a keypoint regressor 14 regressor rows + 5 face vertices ('smpllsp'), without one
-    // 24 posed skeleton joints + 5 face vertices ('smpl') - a skeleton keypoint has an empty selection row and its joint in
-    // kp_joint (closure_device.h: keypoints_from_xs, E6)
-    {
-        const bool skel = m->kp_regressor == nullptr;
-        const int n_rows = skel ? NJ : 14;                        // joints before the five face vertices
-        for (int w = 0; w < 3; ++w) G.kp_joint[w] = 0x3fffffffu;  // 31 = vertex row, six per word
-        G.n_skel = 0;
-        std::vector<double> ksel((size_t)NKP * nv, 0.0);
-        for (int k = 0; k < NKP; ++k) {
-            const int src = m->joint_map[k];
-            if (src < 0 || src >= n_rows + 5) return fail(c, MVFIT_E_ARG, "joint_map entry %d out of range (0..%d)", src, n_rows + 4);
-            if (src < n_rows) {
-                if (skel) {
-                    G.kp_joint[k / 6] &= ~(31u << (5 * (k % 6)));
-                    G.kp_joint[k / 6] |= (unsigned)src << (5 * (k % 6));
-                    ++G.n_skel;
-                } else {
-                    for (int v = 0; v < nv; ++v) ksel[(size_t)k * nv + v] = m->kp_regressor[(size_t)src * nv + v];
-                }
-            } else {
-                const int v = m->face_vertex_ids[src - n_rows];
-                if (v < 0 || v >= nv) return fail(c, MVFIT_E_ARG, "face vertex id out of range");
-                ksel[(size_t)k * nv + v] = 1.0;
-            }
-        }
-        std::vector<int> sel;
-        for (int v = 0; v < nv; ++v) {
-            bool nz = false;
-            for (int k = 0; k < NKP; ++k) nz |= ksel[(size_t)k * nv + v] != 0.0;
-            if (nz) sel.push_back(v);
-        }
-        if (sel.empty()) return fail(c, MVFIT_E_UNSUPPORTED, "the keypoints read no vertex (joint_map names no face vertex)");
-        if ((int)sel.size() > NS_MAX) return fail(c, MVFIT_E_UNSUPPORTED, "keypoint regressor touches %d vertices (max %d)", (int)sel.size(), NS_MAX);
-        M.ns = (int)sel.size();
-        M.nc = 3 * M.ns;
-        M.nc_pad = (M.nc + 3) & ~3;
-        G.ns = M.ns; G.nc = M.nc; G.nc_pad = M.nc_pad;
-        M.sel_v = dev_upload(c, sel);
-        std::vector<float> pds((size_t)KROWS * M.nc_pad, 0.f), pdsT((size_t)M.nc_pad * KROWS, 0.f);
-        int sel_sparse = 1;
-        for (int s = 0; s < M.ns; ++s) {
-            const int v = sel[s];
-            G.sel_v[s] = v;
-            for (int a = 0; a < 3; ++a) {
-                const int cidx = 3 * s + a;
-                G.vt_sub[cidx] = m->v_template[3 * v + a];
-                for (int p = 0; p < 217; ++p) {
-                    const float val = p < 207 ? m->posedirs[(size_t)p * nv * 3 + 3 * v + a]
-                                              : m->shapedirs[((size_t)v * 3 + a) * 10 + (p - 207)];
-                    pds[(size_t)p * M.nc_pad + cidx] = val;
-                    pdsT[(size_t)cidx * KROWS + p] = val;
-                }
-            }
-            for (int j = 0; j < NJ; ++j) G.wT[j][s] = m->lbs_weights[(size_t)v * NJ + j];
-            int np = 0;
-            G.selj[s] = 0u;
-            for (int t = 0; t < 4; ++t) G.selw[s][t] = 0.f;
-            for (int j = 0; j < NJ; ++j) {
-                const float w = m->lbs_weights[(size_t)v * NJ + j];
-                if (w == 0.f) continue;
-                if (np < 4) { G.selw[s][np] = w; G.selj[s] |= (unsigned)j << (8 * np); }
-                ++np;
-            }
-            if (np > 4) sel_sparse = 0;
-        }
-        G.sel_sparse = sel_sparse;
-        M.pd_sub = dev_upload(c, pds);
-        M.pd_subT = dev_upload(c, pdsT);
-        // selection in CSR form, both ways
-        int nnz = 0;
-        for (int k = 0; k < NKP; ++k) {
-            G.kp_start[k] = nnz;
-            for (int s = 0; s < M.ns; ++s) {
-                const double w = ksel[(size_t)k * nv + sel[s]];
-                if (w == 0.0) continue;
-                if (nnz >= KNNZ_MAX) return fail(c, MVFIT_E_UNSUPPORTED, "keypoint selection has more than %d non-zeros", KNNZ_MAX);
-                G.kp_s[nnz] = s; G.kp_w[nnz] = (float)w; ++nnz;
-            }
-        }
-        G.kp_start[NKP] = nnz;
-        nnz = 0;
-        for (int s = 0; s < M.ns; ++s) {
-            G.vs_start[s] = nnz;
-            for (int k = 0; k < NKP; ++k) {
-                const double w = ksel[(size_t)k * nv + sel[s]];
-                if (w == 0.0) continue;
-                G.vs_k[nnz] = k; G.vs_w[nnz] = (float)w; ++nnz;
-            }
-        }
-        for (int s = M.ns; s <= NS_MAX; ++s) G.vs_start[s] = nnz;
-        // fixed-length zero-padded copies (entry 0 / weight 0 pads: fmaf(0, x, acc) == acc)
-        G.padded = 1;
-        for (int k = 0; k < NKP; ++k) {
-            const int n0 = G.kp_start[k], cnt = G.kp_start[k + 1] - n0;
-            if (cnt > KP_NZ) G.padded = 0;
-            for (int t = 0; t < KP_NZ; ++t) { G.kpp_s[k][t] = t < cnt ? G.kp_s[n0 + t] : 0; G.kpp_w[k][t] = t < cnt ? G.kp_w[n0 + t] : 0.f; }
-        }
-        for (int s = 0; s < NS_MAX; ++s) {
-            const int n0 = G.vs_start[s], cnt = G.vs_start[s + 1] - n0;
-            if (cnt > VS_NZ) G.padded = 0;
-            for (int t = 0; t < VS_NZ; ++t) { G.vsp_k[s][t] = t < cnt ? G.vs_k[n0 + t] : 0; G.vsp_w[s][t] = t < cnt ? G.vs_w[n0 + t] : 0.f; }
-        }
-        // per-tile lists for the vertex pass side outputs
-        std::vector<int> tstart(M.ntiles + 1, 0), tlocal(std::max(M.ns, 1)), tslot(std::max(M.ns, 1));
-        int pos = 0;
-        for (int T = 0; T < M.ntiles; ++T) {
-            tstart[T] = pos;
-            for (int s = 0; s < M.ns; ++s)
-                if (sel[s] / TILE_V == T) { tlocal[pos] = sel[s] % TILE_V; tslot[pos] = s; ++pos; }
-        }
-        tstart[M.ntiles] = pos;
-        M.tile_sel_start = dev_upload(c, tstart);
-        M.tile_sel_local = dev_upload(c, tlocal);
-        M.tile_sel_slot = dev_upload(c, tslot);
-    }
-    // kinematic tree: levels and child lists
-    {
-        int depth[NJ];
-        for (int j = 0; j < NJ; ++j) {
-            G.parents[j] = m->parents[j];
-            if (j > 0 && (m->parents[j] < 0 || m->parents[j] >= j)) return fail(c, MVFIT_E_ARG, "parents must be topologically ordered");
-            depth[j] = j == 0 ? 0 : depth[m->parents[j]] + 1;
-        }
-        int maxd = 0;
-        for (int j = 0; j < NJ; ++j) maxd = std::max(maxd, depth[j]);
-        G.nlevels = maxd + 1;
-        int pos = 0;
-        for (int lv = 0; lv <= maxd; ++lv) {
-            G.level_start[lv] = pos;
-            for (int j = 0; j < NJ; ++j) if (depth[j] == lv) G.level_joints[pos++] = j;
-        }
-        for (int lv = maxd + 1; lv <= NJ; ++lv) G.level_start[lv] = pos;
-        pos = 0;
-        for (int p = 0; p < NJ; ++p) {
-            G.child_start[p] = pos;
-            for (int j = 1; j < NJ; ++j) if (m->parents[j] == p) G.child_list[pos++] = j;
-        }
-        G.child_start[NJ] = pos;
-        // forward schedule: each level in groups of 5 joints (one wave = 5 x 12 lanes)
-        memset(G.fwd_tab, 0xff, sizeof(G.fwd_tab));
-        memset(G.bwd_tab, 0xff, sizeof(G.bwd_tab));
-        int np = 0;
-        for (int lv = 1; lv <= maxd; ++lv)
-            for (int base = G.level_start[lv]; base < G.level_start[lv + 1]; base += 5, ++np) {
-                if (np >= NJ) return fail(c, MVFIT_E_UNSUPPORTED, "kinematic tree needs more than %d chain passes", NJ);
-                for (int q = 0; q < 5 && base + q < G.level_start[lv + 1]; ++q) {
-                    const int j = G.level_joints[base + q];
-                    G.fwd_tab[np][q] = j | (m->parents[j] << 8);
-                }
-            }
-        G.n_fwd = np;
-        // pointer-jumping tables (chain_forward_block)
-        {
-            for (int j = 0; j < NJ; ++j) G.anc_tab[0][j] = m->parents[j];
-            for (int st = 1; st < 5; ++st)
-                for (int j = 0; j < NJ; ++j) {
-                    const int a = G.anc_tab[st - 1][j];
-                    G.anc_tab[st][j] = a < 0 ? -1 : G.anc_tab[st - 1][a];
-                }
-            int nj = 0;
-            while ((1 << nj) < maxd + 1) ++nj;
-            if (nj > 5) return fail(c, MVFIT_E_UNSUPPORTED, "kinematic tree deeper than 32 joints");
-            G.n_jump = nj;
-        }
-        // backward schedule: parents with children, deepest level first; <= 3 children per entry
-        // (a parent with more children appears in consecutive passes), <= 5 entries per pass.
-        // Two entries of the same parent never share a pass (they would race on its row).
-        np = 0;
-        for (int lv = maxd - 1; lv >= 0; --lv) {
-            std::vector<int> entries;     // packed words of this level
-            for (int i = G.level_start[lv]; i < G.level_start[lv + 1]; ++i) {
-                const int p = G.level_joints[i];
-                const int nc = G.child_start[p + 1] - G.child_start[p];
-                for (int k = 0; k < nc; k += 3) {
-                    int ch[3] = {31, 31, 31};
-                    for (int t = 0; t < 3 && k + t < nc; ++t) ch[t] = G.child_list[G.child_start[p] + k + t];
-                    entries.push_back(p | (k > 0 ? 0x80 : 0) | (ch[0] << 8) | (ch[1] << 16) | (ch[2] << 24));
-                }
-            }
-            // greedy packing into passes: at most 5 entries, no repeated parent inside a pass
-            std::vector<bool> used(entries.size(), false);
-            size_t left = entries.size();
-            while (left > 0) {
-                if (np >= NJ) return fail(c, MVFIT_E_UNSUPPORTED, "kinematic tree needs more than %d adjoint passes", NJ);
-                int q = 0;
-                std::vector<int> parents_in_pass;
-                for (size_t i = 0; i < entries.size() && q < 5; ++i) {
-                    if (used[i]) continue;
-                    const int p = entries[i] & 0x1f;
-                    bool clash = false;
-                    for (int pp : parents_in_pass) clash |= pp == p;
-                    if (clash) continue;
-                    G.bwd_tab[np][q++] = entries[i];
-                    parents_in_pass.push_back(p);
-                    used[i] = true;
-                    --left;
-                }
-                ++np;
-            }
-        }
-        G.n_bwd = np;
-    }
-    M.mlds = dev_upload(c, imgv);
-    // ---- VPoser decoder ----
-    if (m->vp_fc1_w) {
-        if (!m->vp_fc1_b || !m->vp_fc2_w || !m->vp_fc2_b || !m->vp_out_w || !m->vp_out_b) return fail(c, MVFIT_E_ARG, "incomplete vposer weights");
-        std::vector<float> w1(m->vp_fc1_w, m->vp_fc1_w + 512 * 32), b1(m->vp_fc1_b, m->vp_fc1_b + 512),
-            w2(m->vp_fc2_w, m->vp_fc2_w + 512 * 512), b2(m->vp_fc2_b, m->vp_fc2_b + 512),
-            w3(m->vp_out_w, m->vp_out_w + 138 * 512), b3(m->vp_out_b, m->vp_out_b + 138);
-        std::vector<float> w1T(32 * 512), w2T(512 * 512), w3T(512 * 144, 0.f);
-        for (int o = 0; o < 512; ++o) for (int i = 0; i < 32; ++i) w1T[i * 512 + o] = w1[o * 32 + i];
-        for (int o = 0; o < 512; ++o) for (int i = 0; i < 512; ++i) w2T[i * 512 + o] = w2[o * 512 + i];
-        for (int o = 0; o < 138; ++o) for (int i = 0; i < 512; ++i) w3T[i * 144 + o] = w3[o * 512 + i];
-        M.vp_w1 = dev_upload(c, w1); M.vp_b1 = dev_upload(c, b1);
-        M.vp_w2 = dev_upload(c, w2); M.vp_b2 = dev_upload(c, b2);
-        M.vp_w3 = dev_upload(c, w3); M.vp_b3 = dev_upload(c, b3);
-        M.vp_w1T = dev_upload(c, w1T); M.vp_w2T = dev_upload(c, w2T); M.vp_w3T = dev_upload(c, w3T);
-        {   // register tiles of the decoder helpers (vposer_service.h: VpTiles), 16-byte words, thread-minor
-            std::vector<float> tw2((size_t)VPS_SLICES * 16 * 512 * 4), tw3((size_t)VPS_SLICES * 6 * 512 * 4, 0.f);
-            for (int h = 0; h < VPS_SLICES; ++h)
-                for (int tid = 0; tid < 512; ++tid) {
-                    const int w = tid >> 6, l = tid & 63;
-                    for (int j = 0; j < 16; ++j)
-                        for (int q = 0; q < 4; ++q)
-                            tw2[(((size_t)h * 16 + j) * 512 + tid) * 4 + q] = w2[(size_t)(64 * h + 8 * w + (j >> 1)) * 512 + 8 * l + 4 * (j & 1) + q];
-                    for (int j = 0; j < 6; ++j) {
-                        const int o = l + 64 * (j >> 1);
-                        if (o < 138)
-                            for (int q = 0; q < 4; ++q)
-                                tw3[(((size_t)h * 6 + j) * 512 + tid) * 4 + q] = w3[(size_t)o * 512 + 64 * h + 8 * w + 4 * (j & 1) + q];
-                    }
-                }
-            M.vpt.tw2 = reinterpret_cast<const float4*>(dev_upload(c, tw2));
-            M.vpt.tw3 = reinterpret_cast<const float4*>(dev_upload(c, tw3));
-            M.vpt.w1T = M.vp_w1T; M.vpt.b1 = M.vp_b1; M.vpt.b2 = M.vp_b2;
-            // request / answer granules of one launch (re-initialised before every launch that has helpers)
-            c->vps_words = (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN * (1 + VPS_SLICES);
-            std::vector<unsigned long long> zero(c->vps_words + 1, 0ull);
-            c->vps_mem = dev_upload(c, zero);
-        }
-        c->has_vposer = true;
-    }
-    // ---- GMM ----
-    if (m->gmm_M > 0) {
-        if (m->gmm_M > 8 || !m->gmm_means || !m->gmm_precisions || !m->gmm_nll_weights) return fail(c, MVFIT_E_ARG, "gmm: M <= 8 and all arrays required");
-        M.gmm_M = m->gmm_M;
-        std::vector<float> mu(m->gmm_means, m->gmm_means + m->gmm_M * 69), lw(m->gmm_M),
-            pr((size_t)m->gmm_M * 69 * 72, 0.f), prT((size_t)m->gmm_M * 69 * 72, 0.f);
-        for (int g = 0; g < m->gmm_M; ++g)
-            for (int r = 0; r < 69; ++r)
-                for (int q = 0; q < 69; ++q) {
-                    const float v = m->gmm_precisions[((size_t)g * 69 + r) * 69 + q];
-                    pr[((size_t)g * 69 + r) * 72 + q] = v;
-                    prT[((size_t)g * 69 + q) * 72 + r] = v;
-                }
-        for (int i = 0; i < m->gmm_M; ++i) lw[i] = logf(m->gmm_nll_weights[i]);
-        M.gmm_means = dev_upload(c, mu); M.gmm_prec = dev_upload(c, pr); M.gmm_precT = dev_upload(c, prT);
-        M.gmm_lognw = dev_upload(c, lw);
-        c->gmm_M = m->gmm_M;
+    if (c->has_vposer) {    // request / answer granules of the decoder helpers (re-initialised before every launch that has them)
+        c->vps_words = (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN * (1 + VPS_SLICES);
+        c->vps_mem = dev_upload(c, std::vector<unsigned long long>(c->vps_words + 1, 0ull));
     }
     for (void* p : c->allocs) if (!p) return fail(c, MVFIT_E_HIP, "device allocation failed");
-    // faces for mvfit_render_overlay, with the vertex -> face CSR its normals gather through (a model whose faces index
-    // outside the vertices keeps none: the renderer then reports MVFIT_E_STATE, nothing else uses them)
-    if (m->faces && m->num_faces > 0) {
-        const int nf = m->num_faces;
-        bool valid = true;
-        for (size_t i = 0; i < (size_t)nf * 3 && valid; ++i) valid = m->faces[i] >= 0 && m->faces[i] < nv;
-        if (valid) {
-            std::vector<int32_t> fc(m->faces, m->faces + (size_t)nf * 3), ptr(nv + 1, 0), idx((size_t)nf * 3);
-            for (int32_t i : fc) ++ptr[i + 1];
-            for (int i = 0; i < nv; ++i) ptr[i + 1] += ptr[i];
-            std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-            for (int f = 0; f < nf; ++f)                          // ascending face id within each vertex's list
-                for (int k = 0; k < 3; ++k) idx[fill[fc[f * 3 + k]]++] = f;
-            c->d_faces = dev_upload(c, fc);
-            c->d_vf_ptr = dev_upload(c, ptr);
-            c->d_vf_idx = dev_upload(c, idx);
-            c->num_faces = nf;
-        }
-    }
     if (c->upload_failed) return fail(c, MVFIT_E_HIP, "copying the model constants to the device failed");
     HIP_OK(c, vertex_pass_configure());
     HIP_OK(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));

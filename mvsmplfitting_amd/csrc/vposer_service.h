@@ -30,11 +30,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "model_layout.h"
 #include "wave_ops.h"
 
 namespace mvfit {
 
-constexpr int VPS_SLICES = 8;           // helpers per set = slices of the 512 fc2 units
+// VPS_SLICES (helpers per set = slices of the 512 fc2 units): model_layout.h
 constexpr int VPS_PMAX = 24;            // problems per set (wave w polls the slots w, w + 8, w + 16)
 constexpr int VPS_MAX_SETS = 16;          // 16 for launches of <= 32 problems, else 8
 constexpr int VPS_GRAN = 144;           // granules per request / per answer (138 used)
@@ -140,9 +141,8 @@ struct VpHelperLds {
     int quit;
 };
 
-// Host-side layout of the register tiles (mvfit_create): float4 words, thread-minor, so that a helper's start-up loads
-// are contiguous 8 KB rows.  tw2[h][j = 2a + half][tid] = W2[64h + 8w + a][8l + 4 half .. + 3];
-// tw3[h][j = 2r + half][tid] = W3[l + 64r][64h + 8w + 4 half .. + 3] (zero rows for o >= 138).
+// The register tiles: float4 words, thread-minor, so that a helper's start-up loads are contiguous 8 KB rows (layout:
+// HostModel::vp_tw2 / vp_tw3, model_prep.h).
 struct VpTiles { const float4* tw2; const float4* tw3; const float* w1T; const float* b1; const float* b2; };
 
 // The helper's main loop; returns when every problem of its set has said goodbye (or nothing arrived for 0.2 s).
