@@ -239,6 +239,20 @@ int mvfit_full_pose(mvfit_ctx* ctx, const float* params, uint32_t flags, float* 
 int mvfit_vertices(mvfit_ctx* ctx, const float* params /*[B,MVFIT_D] dev*/, uint32_t flags,
                    float* verts /*[B,Nv,3] dev*/, float* joints /*[B,17,3] dev or NULL*/);
 
+/* Reverse mode of mvfit_vertices: the vector-Jacobian product of (vertices, joints) at params.
+ *   g_verts[B,Nv,3] dev or NULL, g_joints[B,17,3] dev or NULL (NULL = zero cotangent);
+ *   g_params[B,MVFIT_D] dev, overwritten.
+ * flags as mvfit_vertices: MVFIT_F_VPOSER -> gradient in the embedding slots [86:118], body_pose slots 0
+ * (otherwise the embedding slots are 0); MVFIT_F_FIX_SHAPE / MVFIT_F_FIX_SCALE zero those slots as in
+ * mvfit_closure; the other bits have no effect. Needs mvfit_set_problems (for B) like mvfit_vertices.
+ * The result is the gradient of exactly what mvfit_vertices returns (vertices and keypoints both include transl; the root
+ * transform carries the scale, Rm[0] = s R[0]), for either model kind and skinning form.  It is the adjoint of the fp32
+ * model in every contraction mode: with MVFIT_CONTRACTION_HALF_BASIS the forward is the approximation, not this.
+ * Deterministic: no float atomics, every sum in a fixed order; a problem's gradient does not depend on B, its position
+ * in the batch or the call.  The workspace is allocated by the first call with g_verts and grows with B. */
+int mvfit_vertices_backward(mvfit_ctx* ctx, const float* params, uint32_t flags,
+                            const float* g_verts, const float* g_joints, float* g_params);
+
 /* The whole staged fit, device resident: for each stage (non_linear_solver.py:156-211) a fresh
  * LBFGS (lbfgs_ls.py:256-445, strong-Wolfe :39-167) driven by run_fitting (fitting.py:99-142),
  * every problem advancing its own state machine, no host synchronisation per closure.

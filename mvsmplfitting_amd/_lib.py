@@ -66,7 +66,7 @@ class Options(C.Structure):
 
 
 EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'mvfit_set_problems', 'mvfit_set_joints3d',
-           'mvfit_closure', 'mvfit_vertices', 'mvfit_full_pose', 'mvfit_fit', 'mvfit_fit_trace', 'mvfit_fit_stats', 'mvfit_decoder_stats', 'mvfit_debug_capture_pass', 'mvfit_sdf', 'mvfit_set_sdf', 'mvfit_sdf_term_read', 'mvfit_triangulate', 'mvfit_depth_guess', 'mvfit_umeyama', 'mvfit_project_points', 'mvfit_gather', 'mvfit_profile', 'mvfit_profile_read', 'mvfit_profile_vertex_pass', 'mvfit_profile_vertex_pass_ex', 'mvfit_pass_profile',
+           'mvfit_closure', 'mvfit_vertices', 'mvfit_vertices_backward', 'mvfit_full_pose', 'mvfit_fit', 'mvfit_fit_trace', 'mvfit_fit_stats', 'mvfit_decoder_stats', 'mvfit_debug_capture_pass', 'mvfit_sdf', 'mvfit_set_sdf', 'mvfit_sdf_term_read', 'mvfit_triangulate', 'mvfit_depth_guess', 'mvfit_umeyama', 'mvfit_project_points', 'mvfit_gather', 'mvfit_profile', 'mvfit_profile_read', 'mvfit_profile_vertex_pass', 'mvfit_profile_vertex_pass_ex', 'mvfit_pass_profile',
            'mvfit_options_default', 'mvfit_create_ex', 'mvfit_set_options', 'mvfit_get_options', 'mvfit_sdf_info',
            'mvfit_lbfgs_kat', 'mvfit_render_overlay']
 
@@ -108,6 +108,8 @@ def load(path=None):
     lib.mvfit_closure.restype = C.c_int
     lib.mvfit_vertices.argtypes = [vp, vp, C.c_uint32, vp, vp]
     lib.mvfit_vertices.restype = C.c_int
+    lib.mvfit_vertices_backward.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+    lib.mvfit_vertices_backward.restype = C.c_int
     lib.mvfit_fit.argtypes = [vp, C.POINTER(Weights), C.POINTER(LbfgsOpts), vp, vp, vp, vp]
     lib.mvfit_fit.restype = C.c_int
     lib.mvfit_debug_capture_pass.argtypes = [vp, C.c_int, vp]

@@ -58,6 +58,11 @@ hipError_t launch_sdf_voxelize(const int32_t* faces, int num_faces, const float*
 size_t render_ws_bytes(int G, int Nv, int Nf, int H, int W);
 hipError_t launch_render_normals(const float* verts, int B, int Nv, const int32_t* faces, const int32_t* vf_ptr,
                                  const int32_t* vf_idx, double* nrm, hipStream_t stream);
+hipError_t vertex_backward_configure();
+hipError_t launch_vertices_backward(const DevModel& M, const DevPose& P, int B, int Bpad, const float* params, uint32_t flags,
+                                    const float* g_verts, const float* g_joints, float* part, SdfAdj* rec, float* g_params,
+                                    hipStream_t stream);
+size_t vjp_part_bytes(int Bpad, int nv);
 hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int* view, int n, const float* verts,
                                const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points, int num_points,
                                int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,
@@ -765,6 +770,12 @@ struct mvfit_ctx {
     size_t render_nrm_bytes = 0;
     void* d_render_ws = nullptr;
     size_t render_ws_size = 0;
+    // mvfit_vertices_backward (vertex_backward.hip): slice partials and one record per problem, allocated by its first call,
+    // grown with the batch
+    float* d_vjp_part = nullptr;
+    size_t vjp_part_size = 0;
+    SdfAdj* d_vjp_rec = nullptr;
+    int vjp_rec_n = 0;
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -957,6 +968,7 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
     for (void* p : c->allocs) if (!p) return fail(c, MVFIT_E_HIP, "device allocation failed");
     if (c->upload_failed) return fail(c, MVFIT_E_HIP, "copying the model constants to the device failed");
     HIP_OK(c, vertex_pass_configure());
+    HIP_OK(c, vertex_backward_configure());
     HIP_OK(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
     HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds()));
     HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(closure_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds()));
@@ -1010,6 +1022,8 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     if (c->d_vp_log) hipFree(c->d_vp_log);
     if (c->d_render_nrm) hipFree(c->d_render_nrm);
     if (c->d_render_ws) hipFree(c->d_render_ws);
+    if (c->d_vjp_part) hipFree(c->d_vjp_part);
+    if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
     for (void* p : c->allocs) if (p) hipFree(p);
     if (c->h_done) hipHostFree(c->h_done);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
@@ -1236,6 +1250,40 @@ extern "C" int mvfit_vertices(mvfit_ctx* c, const float* params, uint32_t flags,
                            params, joints);
         HIP_OK(c, hipGetLastError());
     }
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_vertices_backward(mvfit_ctx* c, const float* params, uint32_t flags, const float* g_verts,
+                                       const float* g_joints, float* g_params) {
+    if (!c || !params || !g_params) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    flags &= MVFIT_F_VPOSER | MVFIT_F_FIX_SHAPE | MVFIT_F_FIX_SCALE;       // the other bits have no effect here
+    int rc = check_flags(c, flags);
+    if (rc) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (g_verts) {
+        const size_t need = vjp_part_bytes(c->Bpad, c->nv);
+        if (need > c->vjp_part_size || c->B > c->vjp_rec_n) {
+            HIP_OK(c, hipStreamSynchronize(c->stream));          // (a previous call may still read the old buffers)
+            if (need > c->vjp_part_size) {
+                if (c->d_vjp_part) hipFree(c->d_vjp_part);
+                c->d_vjp_part = nullptr; c->vjp_part_size = 0;
+                HIP_OK(c, hipMalloc(&c->d_vjp_part, need));
+                c->vjp_part_size = need;
+            }
+            if (c->B > c->vjp_rec_n) {
+                if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
+                c->d_vjp_rec = nullptr; c->vjp_rec_n = 0;
+                HIP_OK(c, hipMalloc(&c->d_vjp_rec, (size_t)c->B * sizeof(SdfAdj)));
+                c->vjp_rec_n = c->B;
+            }
+        }
+    }
+    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, params, flags,
+                       (float*)nullptr);
+    HIP_OK(c, hipGetLastError());
+    HIP_OK(c, launch_vertices_backward(c->M, c->P, c->B, c->Bpad, params, flags, g_verts, g_joints, c->d_vjp_part, c->d_vjp_rec,
+                                       g_params, c->stream));
     return MVFIT_OK;
 }
 

@@ -252,6 +252,18 @@ class MvFit:
                                              joints.data_ptr()))
         return verts, joints
 
+    def vertices_backward(self, params, grad_verts=None, grad_joints=None, flags=0):
+        """Vector-Jacobian product of vertices(params, flags) (include/mvfit.h:mvfit_vertices_backward): the cotangents
+        grad_verts[B,Nv,3] / grad_joints[B,17,3] (None = zero) -> grad[B,118] (CUDA tensor)."""
+        x = self._dev(params, (self.B, D))
+        gv = None if grad_verts is None else self._dev(grad_verts, (self.B, self.nv, 3))
+        gj = None if grad_joints is None else self._dev(grad_joints, (self.B, 17, 3))
+        out = torch.empty(self.B, D, device=self.device)
+        self._check(self._lib.mvfit_vertices_backward(self._ctx, x.data_ptr(), int(flags),
+                                                      None if gv is None else gv.data_ptr(),
+                                                      None if gj is None else gj.data_ptr(), out.data_ptr()))
+        return out
+
     def full_pose(self, params, flags=0):
         """ModelOutput.full_pose [B,72] = global_orient | body_pose (decoded from the embedding with F_VPOSER):
         include/mvfit.h:mvfit_full_pose."""
