@@ -418,6 +418,38 @@ int mvfit_render_overlay(mvfit_ctx* ctx, const float* vertices, const float* poi
                          const int32_t* image_problem, const int32_t* image_view, int height, int width,
                          const uint8_t* images, uint8_t* out, int32_t* face_id);
 
+/* Several bodies in one image (the reference's Renderer.render_multiperson, utils.py:1030-1099, which nothing in the
+ * reference calls: its save_images path is single-person).  Image i shows the problems
+ * body_problem[image_first[i] .. image_first[i+1]) (host arrays, CSR) seen by view image_view[i], and is rendered EXACTLY
+ * AS mvfit_render_overlay WOULD RENDER THE ONE MESH THAT CONCATENATES THE IMAGE'S BODIES IN LIST ORDER: body k of the image
+ * (slot k = 0 .. n_i - 1) contributes vertex k Nv + j for its vertex j and face k Nf + f for its face f.  Hence
+ *   transform, coverage, depth, znear / zfar, guard band: as above, per vertex and face;
+ *   visibility key = (fp32 bits of z) << 32 | (k Nf + f), one 64-bit minimum per covered sample into the image's one
+ *              visibility buffer: bodies occlude one another, a depth tie goes to the lower slot, then the lower face;
+ *   vertex normals per body (bodies share no vertex);
+ *   lights     placed from the axis-aligned box of the camera-space vertices of ALL bodies of the image;
+ *   shading    with acc the light sum above and c the body's colour channel (float, widened to double):
+ *              s = c * 0.3 + (c / pi) acc, byte = floor(255 min(1, s)^(1/2.2) + 0.5) per channel (c = 0.5: the grey of
+ *              mvfit_render_overlay, term for term);
+ *   colours    body_color[image_first[num_images]][3] host, RGB in [0, 1], or NULL: slot k takes entry k mod 7 of the
+ *              reference's palette in its dictionary order (utils.py:904-912): (.8,.1,.1) (.1,.1,.8) (.1,.8,.1) (.7,.7,.9)
+ *              (.9,.9,.8) (.7,.75,.5) (.5,.7,.75);
+ *   dots       the num_points points of every body of the image, same rule, drawn last;
+ *   outputs    face_id[num_images,H,W] = f (within the body), body_id[num_images,H,W] = slot k, int32 dev or NULL, both -1
+ *              where nothing is drawn;
+ *   cameras    the shared rig, or with per-problem cameras those of the image's first body's problem.
+ * An image with an empty list is copied through (ids -1).  A problem may appear in several images and twice in one.
+ * MVFIT_E_STATE as mvfit_render_overlay.  MVFIT_E_ARG: a NULL image_first / image_view (or body_problem with a body
+ * listed), image_first not starting at 0 or decreasing, a problem or view out of range, a colour outside [0, 1] or not
+ * finite, more than 256 bodies in one image, and the size limits of mvfit_render_overlay.  Asynchronous on the ctx stream
+ * (the host arrays have been read when the call returns).  Consecutive images are processed in groups of at most 64 whose
+ * workspace - per (image, body) instance 56 B x Nv + 4 B x Nf, per image 8 H W bytes - is at most 256 MB, or one image's
+ * when that alone is larger; the result does not depend on the grouping. */
+int mvfit_render_scene(mvfit_ctx* ctx, const float* vertices, const float* points, int num_points, int num_images,
+                       const int32_t* image_first, const int32_t* body_problem, const int32_t* image_view,
+                       const float* body_color, int height, int width, const uint8_t* images, uint8_t* out,
+                       int32_t* face_id, int32_t* body_id);
+
 /* The path's only collective (north_star: "RCCL over xGMI only for the final gather"; in the Python adapters it is one
  * torch.distributed.all_gather, mvsmplfitting_amd/sharding.py): all-gather over the caller's RCCL communicator on the ctx
  * stream - rank r's bytes_per_rank bytes at `send` land at recv + r * bytes_per_rank on every rank.  For hosts that own

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib
 from . import io_formats as iof
-from .engine import MvFit, stage_weights
+from .engine import MvFit, SCENE_PALETTE, stage_weights
 from .init_guess import init_guess_batch, initial_params
 from .sequence import fit_sequences
 
@@ -99,6 +99,44 @@ def load_serial_joints3d(frames, person=0):
     return j3, has
 
 
+def load_serial_people(frames, num_views):
+    """Every person of one serial: (ids, kp [F, P, V, 17, 3] float32, mask [F, P, V] bool) with ``ids`` the sorted person
+    ids that occur anywhere in the serial (io_formats.read_people: the ``person_id`` field when every entry of a file has
+    one, else the index in ``people``; an all-zero entry is absent) and mask[f, p, v]: view v lists person ids[p] in frame
+    f.  Missing entries are zeros, i.e. zero confidence."""
+    seen = {}
+    for f, (_, paths) in enumerate(frames):
+        for v, p in enumerate(paths[:num_views]):
+            if p is not None:
+                for pid, a in iof.read_people(p).items():
+                    seen[(f, pid, v)] = a
+    ids = sorted({k[1] for k in seen})
+    col = {pid: i for i, pid in enumerate(ids)}
+    kp = np.zeros((len(frames), len(ids), num_views, 17, 3), np.float32)
+    mask = np.zeros((len(frames), len(ids), num_views), bool)
+    for (f, pid, v), a in seen.items():
+        kp[f, col[pid], v, :a.shape[0]] = a
+        mask[f, col[pid], v] = True
+    return ids, kp, mask
+
+
+def load_serial_people3d(frames, ids):
+    """use_3d annotation per person: [F, P, 17, 4] float32 (x, y, z, confidence) and has [F, P] - for person ids[p] in
+    frame f the ``pose_keypoints_3d`` entry of the first camera whose file carries one for that id (same id rule)."""
+    col = {pid: i for i, pid in enumerate(ids)}
+    j3 = np.zeros((len(frames), len(ids), 17, 4), np.float32)
+    has = np.zeros((len(frames), len(ids)), bool)
+    for f, (_, paths) in enumerate(frames):
+        for p in paths:
+            if p is None:
+                continue
+            for pid, a in iof.read_people3d(p).items():
+                if pid in col and not has[f, col[pid]]:
+                    j3[f, col[pid], :a.shape[0]] = a
+                    has[f, col[pid]] = True
+    return j3, has
+
+
 IMAGE_EXTS = ('.jpg', '.png')
 RENDER_BATCH = 64          # images per render_overlay call
 IO_WORKERS = 16            # decode / encode threads
@@ -114,9 +152,11 @@ def image_path(image_root, serial, camera, frame):
                      % (serial, camera, frame, ' / '.join(base + e for e in IMAGE_EXTS)))
 
 
-def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool):
+def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scene=None):
     """jobs: [(frame index f, view v, input path, (serial, frame name, camera))]; draws problem f seen by view v over the
     input image and writes `<out_folder>/<serial>/<frame>/<camera>.jpg`.  Returns the written paths in job order.
+    ``scene`` = {f: (problems, colours [n, 3])}: frame f shows these problems, each in its colour, in one depth-tested
+    image (MvFit.render_scene) instead of problem f alone in grey.
     Streamed: the jobs are grouped by image size (read from the file headers) and go through in chunks of at most
     RENDER_BATCH images - decode on the thread pool, one GPU call, encode on the thread pool.  Before the next chunk is
     decoded, the encodes of the chunk before the current one have finished, so at most two chunks of images are held on
@@ -142,7 +182,12 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool):
                         raise ValueError('save_images: %s decoded to %s, its header says %s' % (path, im.shape, (H, W)))
                     imgs[k] = im
                 wait([pool.submit(decode, k, jobs[i][2]) for k, i in enumerate(part)])
-                out = eng.render_overlay(verts, joints, imgs, [jobs[i][0] for i in part], [jobs[i][1] for i in part])
+                if scene is None:
+                    out = eng.render_overlay(verts, joints, imgs, [jobs[i][0] for i in part], [jobs[i][1] for i in part])
+                else:
+                    out = eng.render_scene(verts, joints, imgs, [scene[jobs[i][0]][0] for i in part],
+                                           [jobs[i][1] for i in part],
+                                           colors=np.concatenate([scene[jobs[i][0]][1] for i in part]))
                 out = out.cpu().numpy()
                 del imgs
                 cur = []
@@ -165,7 +210,7 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool):
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
-               save_images=False, image_root=None, image_folder=None):
+               save_images=False, image_root=None, image_folder=None, persons=0):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -175,7 +220,17 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     save_images: draw the fitted body (the saved parameters, as save_meshes) and its keypoints over each view's image;
     inputs under ``image_root`` (default: the ``images`` folder next to ``keyp_root``, the reference's data layout),
     outputs under ``image_folder`` (default ``<result_folder>/images``); a missing input image is a ValueError.  The
-    serial's result gains ``images`` [written paths] and ``timing`` a 'render' entry (decode + GPU + encode)."""
+    serial's result gains ``images`` [written paths] and ``timing`` a 'render' entry (decode + GPU + encode).
+    persons: which entries of the files' ``people`` lists are fitted.  0 (the default): person 0 only, everything above.
+    A list of ids, 'all' (every id that occurs anywhere in the serial; ids as io_formats.read_people defines them) or
+    another int p (= [p]): every (frame, person) pair that at least one view lists is one problem, all problems of a serial
+    go through one batched fit in frame-major, ascending-id order, and the files are `<frame>/<id:03d>.pkl` / `.obj` with
+    the single-person content.  A frame without any of the requested persons is skipped with a RuntimeWarning.  The
+    result rows are then per problem, with ``problem_frame`` (index into ``frames``), ``problem_person`` (id) and
+    ``persons`` (the sorted ids fitted).  With is_seq the persons are the sequences of fit_sequences: a person's chain
+    skips the frames they are absent from and starts cold at their first one.  save_images draws all fitted persons of a
+    frame into every view that had a keypoint file, depth-tested, person p in palette colour p mod 7.  fix_scale /
+    fix_shape: one value for everybody or a dict {id: value} holding every requested id."""
     import time as _time
 
     def _tick(key, t0):
@@ -190,6 +245,18 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     if POSE_FORMATS[pose_format] != model_type:                   # utils.py:444-457
         raise ValueError("pose_format '%s' needs a model of type '%s'; this model is of type '%s'"
                          % (pose_format, POSE_FORMATS[pose_format], model_type))
+    multi = not (isinstance(persons, (int, np.integer)) and not isinstance(persons, bool) and int(persons) == 0)
+    want = None                                                    # 'all'
+    if multi and not (isinstance(persons, str) and persons == 'all'):
+        if isinstance(persons, (str, bool)):
+            raise ValueError("persons: an id, a list of ids or 'all', not %r" % (persons,))
+        want = sorted({int(p) for p in (persons if isinstance(persons, (list, tuple, set, np.ndarray)) else [persons])})
+    for name, val in (('fix_scale', fix_scale), ('fix_shape', fix_shape)):
+        if isinstance(val, dict) and want is not None and not set(want) <= set(val):
+            raise ValueError('%s holds no value for persons %s' % (name, sorted(set(want) - set(val))))
+    if not multi:
+        fix_scale = fix_scale[0] if isinstance(fix_scale, dict) else fix_scale
+        fix_shape = fix_shape[0] if isinstance(fix_shape, dict) else fix_shape
     extris, intris = iof.load_camera_para(cam_file)
     use_vposer = vposer is not None
     flags = _lib.F_VPOSER if use_vposer else 0
@@ -203,6 +270,168 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     jw = np.ones(17, np.float32)
     if pose_format != 'lsp14' or not use_hip:                      # data_parser.py:353-356
         jw[11] = jw[12] = 0.0
+    def stages_for(with_3d):
+        if user_stages is None:
+            return stage_weights(float(image_height), flags=flags | (_lib.F_USE_3D if with_3d else 0))
+        # caller's stage list: the 3-D term follows the group being fitted (annotated frames carry it, the others
+        # must not run it against absent targets), whatever the caller's flag words say
+        out = []
+        for st_ in user_stages:
+            st_ = dict(st_)
+            f_ = int(st_.get('flags', 0))
+            st_['flags'] = (f_ | _lib.F_USE_3D) if with_3d else (f_ & ~_lib.F_USE_3D)
+            out.append(st_)
+        return out
+
+    def per_problem(val, pp, width, name):
+        """fix_scale / fix_shape as one row per problem (None: not fixed)."""
+        if val is None:
+            return None
+        if isinstance(val, dict):
+            missing = sorted(set(pp.tolist()) - set(val))
+            if missing:
+                raise ValueError('%s holds no value for persons %s' % (name, missing))
+            return np.stack([np.asarray(val[int(p)], np.float32).reshape(width) for p in pp])
+        return np.tile(np.asarray(val, np.float32).reshape(1, width), (len(pp), 1))
+
+    def fit_people(serial, cams, frames, V):
+        """The multi-person path of one serial -> its result dict, or None when no requested person occurs."""
+        nonlocal _t
+        F = len(frames)
+        ids_all, kpp, pmask = load_serial_people(frames, V)
+        col = {p: i for i, p in enumerate(ids_all)}
+        ids = [p for p in (ids_all if want is None else want) if p in col]
+        prob = [(f, p) for f in range(F) for p in ids if pmask[f, col[p]].any()]
+        empty = sorted(set(range(F)) - {f for f, _ in prob})
+        if empty:
+            warnings.warn('serial %s: frames %s list none of the persons %s in any view; skipped'
+                          % (serial, [frames[f][0] for f in empty], 'all' if want is None else want), RuntimeWarning)
+        if not prob:
+            return None
+        N = len(prob)
+        pf, pp = np.array([f for f, _ in prob]), np.array([p for _, p in prob])
+        kp = np.stack([kpp[f, col[p]] for f, p in prob])
+        vmask = np.stack([pmask[f, col[p]] for f, p in prob])
+        if save_images:
+            jobs = [(f, v, image_path(image_root, serial, cams[v], frames[f][0]), (serial, frames[f][0], cams[v]))
+                    for f in sorted(set(pf.tolist())) for v in range(V) if frames[f][1][v] is not None]
+        ex, it = np.asarray(extris[:V], np.float64), np.asarray(intris[:V], np.float64)
+        rig = (ex[:, :3, :3].astype(np.float32), ex[:, :3, 3].astype(np.float32),
+               it[:, 0, 0].astype(np.float32), it[:, :2, 2].astype(np.float32))
+        gt_xy = kp[..., :2].copy()
+        conf = kp[..., 2] * jw[None, None, :]
+        eng.set_problems(rig, gt_xy, conf)
+        _t = _tick('read', _t)
+        ann, has = np.zeros((N, 17, 4), np.float32), np.zeros(N, bool)
+        if use_3d:
+            j3p, hasp = load_serial_people3d(frames, ids_all)
+            ann = np.stack([j3p[f, col[p]] for f, p in prob])
+            has = np.array([hasp[f, col[p]] for f, p in prob])
+        if is_seq and has.any() and not has.all():
+            warnings.warn('serial %s: %d of %d problems carry no 3-D annotation; the is_seq chain runs on one objective - '
+                          'fitting the whole serial from the 2-D keypoints only' % (serial, int((~has).sum()), N))
+            has[:] = False
+        c3 = None
+        if has.any():
+            c3 = ann[:, :, 3].copy()
+            if not use_hip:
+                c3[:, 11] = c3[:, 12] = 0.0
+        scales = per_problem(fix_scale, pp, 1, 'fix_scale')
+        shapes = per_problem(fix_shape, pp, 10, 'fix_shape')
+        guess = {}
+
+        def guess_rows(rows, with_3d):
+            # one init_guess_batch per distinct fixed scale: one call when everybody shares it
+            groups = [rows] if scales is None else [rows[scales[rows, 0] == v_] for v_ in np.unique(scales[rows, 0])]
+            for g in groups:
+                if g.size < N:
+                    eng.set_problems(rig, gt_xy[g], conf[g])
+                r = init_guess_batch(eng, ex, it, kp[g], est_scale=scales is None,
+                                     fixed_scale=None if scales is None else float(scales[g[0], 0]),
+                                     joints3d=ann[g][:, :, :3].astype(np.float64) if with_3d else None,
+                                     view_mask=None if with_3d else vmask[g])
+                idx = torch.as_tensor(g, device=eng.device)
+                for k in ('global_orient', 'transl', 'scale', 'joints3d', 'rot'):
+                    if k not in guess:
+                        guess[k] = torch.zeros((N,) + tuple(r[k].shape[1:]), dtype=r[k].dtype, device=r[k].device)
+                    guess[k][idx] = r[k]
+                if g.size < N:
+                    eng.set_problems(rig, gt_xy, conf)
+        guess_rows(np.arange(N), bool(has.all()))
+        if has.any() and not has.all():
+            guess_rows(np.flatnonzero(has), True)
+        x0 = initial_params(guess, use_vposer)
+        if shapes is not None:
+            x0[:, 0:10] = torch.as_tensor(shapes, device=x0.device)
+        _t = _tick('init_guess', _t)
+        xf = torch.empty_like(x0)
+        final = torch.empty(N, device=eng.device)
+        ncl = torch.zeros(N, dtype=torch.int32, device=eng.device)
+        if is_seq:
+            # the persons are the sequences; a person's chain runs over the frames they are in
+            seq = sorted(set(pp.tolist()))
+            row = {p: s_ for s_, p in enumerate(seq)}
+            S = len(seq)
+            ps = np.array([row[p] for p in pp.tolist()])
+            present = np.zeros((S, F), bool)
+            present[ps, pf] = True
+            gt_s = np.zeros((S, F) + gt_xy.shape[1:], np.float32)
+            conf_s = np.zeros((S, F) + conf.shape[1:], np.float32)
+            gt_s[ps, pf], conf_s[ps, pf] = gt_xy, conf
+            x0_s = torch.zeros(S, F, x0.shape[1], dtype=x0.dtype, device=x0.device)
+            x0_s[torch.as_tensor(ps), torch.as_tensor(pf)] = x0
+            t3 = None
+            if has.all():
+                a3, c3_s = np.zeros((S, F, 17, 3), np.float32), np.zeros((S, F, 17), np.float32)
+                a3[ps, pf], c3_s[ps, pf] = ann[:, :, :3], c3
+                t3 = (a3, c3_s)
+            xs, st = fit_sequences(eng, rig, gt_s, conf_s, x0_s, stages_for(has.all()), joints3d=t3, present=present)
+            si, fi = torch.as_tensor(ps, device=xs.device), torch.as_tensor(pf, device=xs.device)
+            xf = xs[si, fi].to(x0.dtype)
+            final, ncl = st['final_loss'][si, fi], st['n_closure'][si, fi]
+            restarted = st['restarted'][ps, pf]
+            eng.set_problems(rig, gt_xy, conf)
+        else:
+            for sel, with_3d in ((np.flatnonzero(has), True), (np.flatnonzero(~has), False)):
+                if sel.size == 0:
+                    continue
+                if sel.size < N:
+                    eng.set_problems(rig, gt_xy[sel], conf[sel])
+                if with_3d:
+                    eng.set_joints3d(ann[sel][:, :, :3], c3[sel])
+                idx = torch.as_tensor(sel, device=eng.device)
+                xs_, st = eng.fit(x0[idx], stages_for(with_3d))
+                xf[idx], final[idx], ncl[idx] = xs_.to(xf.dtype), st['final_loss'].to(final.dtype), st['n_closure'].to(ncl.dtype)
+            if has.any() and not has.all():
+                eng.set_problems(rig, gt_xy, conf)
+            restarted = np.ones(N, bool)
+        _t = _tick('fit', _t)
+        full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
+        xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
+        res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
+               for n in range(N)]
+        files = [iof.save_result_pkl(result_folder, serial, frames[pf[n]][0], res[n], person_id=int(pp[n])) for n in range(N)]
+        if save_meshes or save_images:
+            xm = xf_h.copy()
+            xm[:, 13:82] = np.stack([r['body_pose'][0] for r in res])
+            verts_d, joints_d = eng.vertices(xm, flags=flags & ~_lib.F_VPOSER)
+        if save_meshes:
+            verts = verts_d.cpu().numpy()
+            for n in range(N):
+                d = os.path.join(mesh_folder or os.path.join(result_folder, 'meshes'), serial, frames[pf[n]][0])
+                os.makedirs(d, exist_ok=True)
+                iof.save_obj(os.path.join(d, '%03d.obj' % int(pp[n])), verts[n], model['faces'])
+        out = dict(frames=[fr[0] for fr in frames], params=xf_h, final_loss=final_h, n_closure=ncl.cpu().numpy(), files=files,
+                   init=x0.cpu().numpy(), restarted=restarted, used_3d=has.copy(), views_per_frame=vmask.sum(1),
+                   problem_frame=pf, problem_person=pp, persons=sorted(set(pp.tolist())))
+        _t = _tick('write', _t)
+        if save_images:
+            palette = np.asarray(SCENE_PALETTE, np.float32)
+            scene = {f: (np.flatnonzero(pf == f).tolist(), palette[pp[pf == f] % 7]) for f in set(pf.tolist())}
+            out['images'] = render_serial_images(eng, verts_d, joints_d, jobs,
+                                                 image_folder or os.path.join(result_folder, 'images'), pool, scene=scene)
+            _t = _tick('render', _t)
+        return out
     results = {}
     if save_images and image_root is None:
         image_root = os.path.join(os.path.dirname(os.path.normpath(keyp_root)), 'images')
@@ -215,6 +444,11 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 continue
             if V > len(extris):
                 raise ValueError('serial %s has %d camera folders, the camera file %s holds %d cameras' % (serial, V, cam_file, len(extris)))
+            if multi:
+                r_ = fit_people(serial, cams, frames, V)
+                if r_ is not None:
+                    results[serial] = r_
+                continue
             kp, vmask = load_serial(frames, V, return_mask=True)
             if save_images:
                 # the views that had a keypoint file in the frame (main.py:44-66); a missing image fails before the fit
@@ -259,18 +493,6 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             x0 = initial_params(guess, use_vposer, fixed_shape=fix_shape)
             _t = _tick('init_guess', _t)
 
-            def stages_for(with_3d):
-                if user_stages is None:
-                    return stage_weights(float(image_height), flags=flags | (_lib.F_USE_3D if with_3d else 0))
-                # caller's stage list: the 3-D term follows the group being fitted (annotated frames carry it, the others
-                # must not run it against absent targets), whatever the caller's flag words say
-                out = []
-                for st_ in user_stages:
-                    st_ = dict(st_)
-                    f_ = int(st_.get('flags', 0))
-                    st_['flags'] = (f_ | _lib.F_USE_3D) if with_3d else (f_ & ~_lib.F_USE_3D)
-                    out.append(st_)
-                return out
             if is_seq:
                 if has.all():
                     eng.set_joints3d(ann[:, :, :3], c3)
@@ -330,4 +552,4 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     return results
 
 
-__all__ = ['list_frames', 'load_serial', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS']
+__all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS']

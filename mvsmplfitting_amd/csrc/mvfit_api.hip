@@ -67,6 +67,11 @@ hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int*
                                const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points, int num_points,
                                int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,
                                hipStream_t stream);
+size_t scene_ws_bytes(int n, int m, int Nv, int Nf, int H, int W);
+hipError_t launch_scene_group(const DevProblems& Q, const int32_t* tab, int num_images, int i0, int n, int j0, int m,
+                              const float* verts, const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points,
+                              int num_points, int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, int32_t* body_id,
+                              void* ws_mem, hipStream_t stream);
 
 struct StageWeights { DevWeights w[MVFIT_MAX_STAGES]; };
 
@@ -770,6 +775,13 @@ struct mvfit_ctx {
     size_t render_nrm_bytes = 0;
     void* d_render_ws = nullptr;
     size_t render_ws_size = 0;
+    int32_t* d_scene_tab = nullptr;    // image / instance tables of the last mvfit_render_scene
+    size_t scene_tab_bytes = 0;
+    // their pinned host staging, two slots used in turn: a slot is rewritten once the copy out of it (two calls back) is done
+    int32_t* h_scene_tab[2] = {nullptr, nullptr};
+    size_t h_scene_tab_bytes[2] = {0, 0};
+    hipEvent_t scene_copied[2] = {nullptr, nullptr};
+    int scene_slot = 0;
     // mvfit_vertices_backward (vertex_backward.hip): slice partials and one record per problem, allocated by its first call,
     // grown with the batch
     float* d_vjp_part = nullptr;
@@ -1022,6 +1034,11 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     if (c->d_vp_log) hipFree(c->d_vp_log);
     if (c->d_render_nrm) hipFree(c->d_render_nrm);
     if (c->d_render_ws) hipFree(c->d_render_ws);
+    if (c->d_scene_tab) hipFree(c->d_scene_tab);
+    for (int k = 0; k < 2; ++k) {
+        if (c->h_scene_tab[k]) hipHostFree(c->h_scene_tab[k]);
+        if (c->scene_copied[k]) hipEventDestroy(c->scene_copied[k]);
+    }
     if (c->d_vjp_part) hipFree(c->d_vjp_part);
     if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
     for (void* p : c->allocs) if (p) hipFree(p);
@@ -2119,6 +2136,26 @@ extern "C" int mvfit_project_points(mvfit_ctx* c, const float* points, int num_p
     return MVFIT_OK;
 }
 
+// grows the renderer's workspace and normal buffer (kept in the ctx) to at least ws / nb bytes
+static int render_reserve(mvfit_ctx* c, size_t ws, size_t nb) {
+    if (ws > c->render_ws_size || nb > c->render_nrm_bytes) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));             // earlier calls may still read the old buffers
+        if (ws > c->render_ws_size) {
+            if (c->d_render_ws) hipFree(c->d_render_ws);
+            c->d_render_ws = nullptr; c->render_ws_size = 0;
+            HIP_OK(c, hipMalloc(&c->d_render_ws, ws));
+            c->render_ws_size = ws;
+        }
+        if (nb > c->render_nrm_bytes) {
+            if (c->d_render_nrm) hipFree(c->d_render_nrm);
+            c->d_render_nrm = nullptr; c->render_nrm_bytes = 0;
+            HIP_OK(c, hipMalloc(&c->d_render_nrm, nb));
+            c->render_nrm_bytes = nb;
+        }
+    }
+    return MVFIT_OK;
+}
+
 extern "C" int mvfit_render_overlay(mvfit_ctx* c, const float* vertices, const float* points, int num_points, int num_images,
                                     const int32_t* image_problem, const int32_t* image_view, int height, int width,
                                     const uint8_t* images, uint8_t* out, int32_t* face_id) {
@@ -2141,21 +2178,7 @@ extern "C" int mvfit_render_overlay(mvfit_ctx* c, const float* vertices, const f
     while (G > 1 && render_ws_bytes(G, c->nv, c->num_faces, height, width) > cap) --G;
     const size_t ws = render_ws_bytes(G, c->nv, c->num_faces, height, width);
     const size_t nb = (size_t)c->B * c->nv * 3 * sizeof(double);
-    if (ws > c->render_ws_size || nb > c->render_nrm_bytes) {
-        HIP_OK(c, hipStreamSynchronize(c->stream));             // earlier calls may still read the old buffers
-        if (ws > c->render_ws_size) {
-            if (c->d_render_ws) hipFree(c->d_render_ws);
-            c->d_render_ws = nullptr; c->render_ws_size = 0;
-            HIP_OK(c, hipMalloc(&c->d_render_ws, ws));
-            c->render_ws_size = ws;
-        }
-        if (nb > c->render_nrm_bytes) {
-            if (c->d_render_nrm) hipFree(c->d_render_nrm);
-            c->d_render_nrm = nullptr; c->render_nrm_bytes = 0;
-            HIP_OK(c, hipMalloc(&c->d_render_nrm, nb));
-            c->render_nrm_bytes = nb;
-        }
-    }
+    if (int rc = render_reserve(c, ws, nb)) return rc;
     hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->d_render_nrm, c->stream);
     const size_t px = (size_t)height * width;
     for (int i0 = 0; i0 < num_images && e == hipSuccess; i0 += G) {
@@ -2164,6 +2187,107 @@ extern "C" int mvfit_render_overlay(mvfit_ctx* c, const float* vertices, const f
                                 c->num_faces, points, points ? num_points : 0, height, width, images + (size_t)i0 * px * 3,
                                 out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr, c->d_render_ws,
                                 c->stream);
+    }
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "render launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+// utils.py:904-912 Renderer.colors in dictionary order
+static const float SCENE_PALETTE[7][3] = {{.8f, .1f, .1f}, {.1f, .1f, .8f}, {.1f, .8f, .1f}, {.7f, .7f, .9f},
+                                          {.9f, .9f, .8f}, {.7f, .75f, .5f}, {.5f, .7f, .75f}};
+
+extern "C" int mvfit_render_scene(mvfit_ctx* c, const float* vertices, const float* points, int num_points, int num_images,
+                                  const int32_t* image_first, const int32_t* body_problem, const int32_t* image_view,
+                                  const float* body_color, int height, int width, const uint8_t* images, uint8_t* out,
+                                  int32_t* face_id, int32_t* body_id) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_render_scene: the model was created without (valid) faces");
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first (the cameras come from there)");
+    if (!vertices || !images || !out || !image_first || !image_view || num_images < 1 || height < 1 || height > 8192 ||
+        width < 1 || width > 8192 || num_points < 0 || num_points > 64)
+        return fail(c, MVFIT_E_ARG, "mvfit_render_scene: bad argument (num_images=%d height=%d width=%d num_points=%d)",
+                    num_images, height, width, num_points);
+    if (image_first[0] != 0) return fail(c, MVFIT_E_ARG, "mvfit_render_scene: image_first[0] = %d, not 0", image_first[0]);
+    for (int i = 0; i < num_images; ++i) {
+        const long long cnt = (long long)image_first[i + 1] - image_first[i];
+        if (cnt < 0) return fail(c, MVFIT_E_ARG, "mvfit_render_scene: image_first decreases at image %d", i);
+        if (cnt > SCENE_BODIES_MAX)
+            return fail(c, MVFIT_E_ARG, "mvfit_render_scene: image %d lists %lld bodies (at most %d)", i, cnt, SCENE_BODIES_MAX);
+        if (image_view[i] < 0 || image_view[i] >= c->V)
+            return fail(c, MVFIT_E_ARG, "mvfit_render_scene: image %d names view %d (V=%d)", i, image_view[i], c->V);
+    }
+    const int total = image_first[num_images];
+    if (total > 0 && !body_problem) return fail(c, MVFIT_E_ARG, "mvfit_render_scene: body_problem is NULL");
+    for (int j = 0; j < total; ++j) {
+        if (body_problem[j] < 0 || body_problem[j] >= c->B)
+            return fail(c, MVFIT_E_ARG, "mvfit_render_scene: body %d names problem %d (B=%d)", j, body_problem[j], c->B);
+        if (body_color)
+            for (int k = 0; k < 3; ++k)
+                if (!(body_color[j * 3 + k] >= 0.f && body_color[j * 3 + k] <= 1.f))        // NaN fails both
+                    return fail(c, MVFIT_E_ARG, "mvfit_render_scene: colour of body %d outside [0, 1]", j);
+    }
+    HIP_OK(c, hipSetDevice(c->device));
+    // the call's tables, built in a pinned staging slot so that the copy to the device does not block the host
+    const size_t tab_words = (size_t)num_images * SCENE_IMAGE_WORDS + (size_t)total * SCENE_INST_WORDS;
+    const size_t tb = tab_words * sizeof(int32_t);
+    const int slot = c->scene_slot;
+    c->scene_slot ^= 1;
+    if (c->scene_copied[slot]) HIP_OK(c, hipEventSynchronize(c->scene_copied[slot]));
+    else HIP_OK(c, hipEventCreateWithFlags(&c->scene_copied[slot], hipEventDisableTiming));
+    if (tb > c->h_scene_tab_bytes[slot]) {
+        if (c->h_scene_tab[slot]) hipHostFree(c->h_scene_tab[slot]);
+        c->h_scene_tab[slot] = nullptr; c->h_scene_tab_bytes[slot] = 0;
+        HIP_OK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_scene_tab[slot]), tb));
+        c->h_scene_tab_bytes[slot] = tb;
+    }
+    int32_t* ti = c->h_scene_tab[slot];
+    int32_t* tj = ti + (size_t)num_images * SCENE_IMAGE_WORDS;
+    for (int i = 0; i < num_images; ++i) {
+        const int first = image_first[i], cnt = image_first[i + 1] - first;
+        ti[i * 4 + 0] = first; ti[i * 4 + 1] = cnt; ti[i * 4 + 2] = image_view[i];
+        ti[i * 4 + 3] = cnt ? body_problem[first] : 0;
+        for (int k = 0; k < cnt; ++k) {
+            int32_t* r = tj + (size_t)(first + k) * SCENE_INST_WORDS;
+            r[0] = body_problem[first + k]; r[1] = i; r[2] = k;
+            const float* col = body_color ? body_color + (size_t)(first + k) * 3 : SCENE_PALETTE[k % 7];
+            memcpy(r + 3, col, 12);
+        }
+    }
+    // groups of consecutive images: at most RENDER_GROUP_MAX images and a workspace of at most 256 MB counting instances -
+    // or one image's, when that alone needs more
+    const size_t cap = (size_t)256 << 20;
+    std::vector<int> group_end;
+    size_t ws = 0;
+    for (int i0 = 0; i0 < num_images;) {
+        int i1 = i0 + 1;
+        while (i1 < num_images && i1 - i0 < RENDER_GROUP_MAX &&
+               scene_ws_bytes(i1 + 1 - i0, image_first[i1 + 1] - image_first[i0], c->nv, c->num_faces, height, width) <= cap)
+            ++i1;
+        ws = std::max(ws, scene_ws_bytes(i1 - i0, image_first[i1] - image_first[i0], c->nv, c->num_faces, height, width));
+        group_end.push_back(i1);
+        i0 = i1;
+    }
+    const size_t nb = (size_t)c->B * c->nv * 3 * sizeof(double);
+    if (int rc = render_reserve(c, ws, nb)) return rc;
+    if (tb > c->scene_tab_bytes) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (c->d_scene_tab) hipFree(c->d_scene_tab);
+        c->d_scene_tab = nullptr; c->scene_tab_bytes = 0;
+        HIP_OK(c, hipMalloc(&c->d_scene_tab, tb));
+        c->scene_tab_bytes = tb;
+    }
+    HIP_OK(c, hipMemcpyAsync(c->d_scene_tab, c->h_scene_tab[slot], tb, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipEventRecord(c->scene_copied[slot], c->stream));
+    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->d_render_nrm, c->stream);
+    const size_t px = (size_t)height * width;
+    int i0 = 0;
+    for (size_t g = 0; g < group_end.size() && e == hipSuccess; ++g) {
+        const int i1 = group_end[g], j0 = image_first[i0], m = image_first[i1] - j0;
+        e = launch_scene_group(c->Q, c->d_scene_tab, num_images, i0, i1 - i0, j0, m, vertices, c->d_render_nrm, c->nv, c->d_faces,
+                               c->num_faces, points, points ? num_points : 0, height, width, images + (size_t)i0 * px * 3,
+                               out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr,
+                               body_id ? body_id + (size_t)i0 * px : nullptr, c->d_render_ws, c->stream);
+        i0 = i1;
     }
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "render launch: %s", hipGetErrorString(e));
     return MVFIT_OK;

@@ -12,6 +12,10 @@ namespace mvfit {
 
 // NJ, NKP, KROWS, TILE_V, NS_MAX, ... and ModelLds: model_layout.h
 constexpr int RENDER_GROUP_MAX = 64;   // images per launch group of mvfit_render_overlay (render.hip)
+// mvfit_render_scene: device tables of int32 words - per image {first instance, count, view, camera problem}, per instance
+// {problem, image, slot, colour r g b as float bits}
+constexpr int SCENE_IMAGE_WORDS = 4, SCENE_INST_WORDS = 6;
+constexpr int SCENE_BODIES_MAX = 256;  // bodies per image
 constexpr int DV = MVFIT_D;       // 118
 constexpr int DPAD = 128;
 constexpr int A_STRIDE = 288;     // per-problem stride of the 24x12 skinning transforms in LDS (vertex pass): the HBM stride, so that a chunk's

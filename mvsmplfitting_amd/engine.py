@@ -33,6 +33,10 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+# the reference's Renderer.colors in dictionary order (code/utils/utils.py:904-912): body k of a scene takes entry k mod 7
+SCENE_PALETTE = ((.8, .1, .1), (.1, .1, .8), (.1, .8, .1), (.7, .7, .9), (.9, .9, .8), (.7, .75, .5), (.5, .7, .75))
+
+
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
@@ -436,13 +440,8 @@ class MvFit:
         self._check(self._lib.mvfit_project_points(self._ctx, p.data_ptr(), int(p.shape[1]), uv.data_ptr()))
         return uv
 
-    def render_overlay(self, vertices, points, images, problems, views, face_id=False, out=None):
-        """The body drawn over each view's image with the keypoints as red dots (include/mvfit.h:mvfit_render_overlay;
-        reference save_images, utils/utils.py:574-597,659-712,977-1028).  vertices [B, Nv, 3] (e.g. ``vertices()``),
-        points [B, P, 3] (P <= 64) or None, images uint8 [n, H, W, 3] RGB (torch tensor or NumPy array); image i is problem
-        problems[i] seen by view views[i] of set_problems' cameras.  Returns a uint8 device tensor [n, H, W, 3] (``out``:
-        a contiguous uint8 tensor of that shape on this engine's device to write into; ``out=images`` renders in place and
-        needs ``images`` to be such a tensor) and, with face_id, also the int32 [n, H, W] visible face per pixel (-1: none)."""
+    def _render_inputs(self, vertices, points, images):
+        """Argument checks shared by render_overlay and render_scene -> (v, p or None, img on the device, n, H, W)."""
         v = self._dev(vertices)
         if v.dim() != 3 or v.shape[0] != self.B or v.shape[1] != self.nv or v.shape[2] != 3:
             raise MvFitError('vertices must be [B, %d, 3] with B = %d' % (self.nv, self.B))
@@ -460,9 +459,9 @@ class MvFit:
             raise MvFitError('images must be uint8 [n, H, W, 3]')
         img = img.to(self.device).contiguous()
         n, H, W = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
-        prob, view = _i32(np.asarray(problems).reshape(-1)), _i32(np.asarray(views).reshape(-1))
-        if prob.size != n or view.size != n:
-            raise MvFitError('problems and views need one entry per image (%d)' % n)
+        return v, p, img, n, H, W
+
+    def _render_out(self, images, img, out):
         if out is None:
             out = torch.empty_like(img)
         elif out is images:
@@ -472,6 +471,20 @@ class MvFit:
         elif (out.dtype != torch.uint8 or tuple(out.shape) != tuple(img.shape) or out.device != self.device
               or not out.is_contiguous()):
             raise MvFitError('out must be a contiguous uint8 device tensor of the images\' shape')
+        return out
+
+    def render_overlay(self, vertices, points, images, problems, views, face_id=False, out=None):
+        """The body drawn over each view's image with the keypoints as red dots (include/mvfit.h:mvfit_render_overlay;
+        reference save_images, utils/utils.py:574-597,659-712,977-1028).  vertices [B, Nv, 3] (e.g. ``vertices()``),
+        points [B, P, 3] (P <= 64) or None, images uint8 [n, H, W, 3] RGB (torch tensor or NumPy array); image i is problem
+        problems[i] seen by view views[i] of set_problems' cameras.  Returns a uint8 device tensor [n, H, W, 3] (``out``:
+        a contiguous uint8 tensor of that shape on this engine's device to write into; ``out=images`` renders in place and
+        needs ``images`` to be such a tensor) and, with face_id, also the int32 [n, H, W] visible face per pixel (-1: none)."""
+        v, p, img, n, H, W = self._render_inputs(vertices, points, images)
+        prob, view = _i32(np.asarray(problems).reshape(-1)), _i32(np.asarray(views).reshape(-1))
+        if prob.size != n or view.size != n:
+            raise MvFitError('problems and views need one entry per image (%d)' % n)
+        out = self._render_out(images, img, out)
         fid = torch.empty(n, H, W, dtype=torch.int32, device=self.device) if face_id else None
         ip = C.POINTER(C.c_int32)
         self._check(self._lib.mvfit_render_overlay(
@@ -479,6 +492,48 @@ class MvFit:
             prob.ctypes.data_as(ip), view.ctypes.data_as(ip), H, W, img.data_ptr(), out.data_ptr(),
             fid.data_ptr() if face_id else None))
         return (out, fid) if face_id else out
+
+    def render_scene(self, vertices, points, images, bodies, views, colors=None, face_id=False, body_id=False, out=None):
+        """Several bodies per image, depth-tested against one another (include/mvfit.h:mvfit_render_scene): image i shows the
+        problems ``bodies[i]`` (a list per image; may be empty) seen by view ``views[i]``, each in its own opaque colour -
+        ``colors``: None (slot k of an image takes entry k mod 7 of SCENE_PALETTE), one [3] RGB triple in [0, 1] per body in
+        the nesting of ``bodies``, or a flat [n_bodies, 3] array.  vertices, points, images, ``out`` and the in-place rule as
+        render_overlay.  Returns out, then with face_id the int32 [n, H, W] visible face within its body and with body_id
+        the slot of the visible body (both -1 where nothing is drawn)."""
+        v, p, img, n, H, W = self._render_inputs(vertices, points, images)
+        bodies = [list(np.asarray(b, np.int64).reshape(-1)) for b in bodies]
+        view = _i32(np.asarray(views).reshape(-1))
+        if len(bodies) != n or view.size != n:
+            raise MvFitError('bodies and views need one entry per image (%d)' % n)
+        first = _i32(np.concatenate([[0], np.cumsum([len(b) for b in bodies])]))
+        total = int(first[-1])
+        prob = _i32([b for lst in bodies for b in lst] or [0])
+        col = None
+        if colors is not None:
+            try:
+                col = np.asarray(colors, np.float32)
+            except ValueError:                              # ragged: the nesting of ``bodies``
+                col = None
+            if col is None or col.shape != (total, 3):
+                try:
+                    col = np.concatenate([np.asarray(c_, np.float32).reshape(-1, 3) for c_ in colors]
+                                         + [np.zeros((0, 3), np.float32)])
+                except (ValueError, TypeError):
+                    raise MvFitError('colors must hold one RGB triple per body (%d)' % total)
+            if col.ndim != 2 or col.shape != (total, 3):
+                raise MvFitError('colors must hold one RGB triple per body (%d)' % total)
+            col = np.ascontiguousarray(col if total else np.zeros((1, 3), np.float32), np.float32)
+        out = self._render_out(images, img, out)
+        fid = torch.empty(n, H, W, dtype=torch.int32, device=self.device) if face_id else None
+        bid = torch.empty(n, H, W, dtype=torch.int32, device=self.device) if body_id else None
+        ip = C.POINTER(C.c_int32)
+        self._check(self._lib.mvfit_render_scene(
+            self._ctx, v.data_ptr(), p.data_ptr() if p is not None else None, int(p.shape[1]) if p is not None else 0, n,
+            first.ctypes.data_as(ip), prob.ctypes.data_as(ip), view.ctypes.data_as(ip),
+            col.ctypes.data_as(C.POINTER(C.c_float)) if col is not None else None, H, W, img.data_ptr(), out.data_ptr(),
+            fid.data_ptr() if face_id else None, bid.data_ptr() if body_id else None))
+        res = (out,) + ((fid,) if face_id else ()) + ((bid,) if body_id else ())
+        return res if len(res) > 1 else out
 
     def gather(self, rccl_comm, send, nranks):
         """All-gather of a contiguous device tensor over a raw RCCL communicator (include/mvfit.h:mvfit_gather) - the

@@ -55,6 +55,40 @@ def read_joints3d(path):
     return [np.array(p['pose_keypoints_3d'], dtype=np.float32).reshape([-1, 4]) for p in data['people']]
 
 
+def _read_people(path, key, width):
+    with open(path) as f:
+        people = json.load(f)['people']
+    by_id = all(isinstance(p.get('person_id'), int) and not isinstance(p.get('person_id'), bool) for p in people)
+    out = {}
+    for k, p in enumerate(people):
+        if key not in p:
+            if key == 'pose_keypoints_2d':
+                raise KeyError(key)
+            continue
+        a = np.array(p[key], dtype=np.float32).reshape([-1, width])[:17]
+        if not a[:, width - 1].any():                      # every confidence zero: the person is not in this file
+            continue
+        pid = int(p['person_id']) if by_id else k
+        if pid in out:
+            raise ValueError('%s lists person %d twice' % (path, pid))
+        out[pid] = a
+    return out
+
+
+def read_people(path):
+    """{person id: [17, 3] float32 (x, y, confidence)} of one keypoint file.  The id of a ``people`` entry is its integer
+    ``person_id`` field when EVERY entry of the file carries one, else its index in the list.  An entry whose confidences
+    are all zero counts as absent - how an index-identified file says "person 1 is not in this view but person 2 is".
+    Two entries with one id: ValueError naming the file."""
+    return _read_people(path, 'pose_keypoints_2d', 3)
+
+
+def read_people3d(path):
+    """The 3-D twin of read_people: {person id: [17, 4] float32 (x, y, z, confidence)} from ``pose_keypoints_3d``, by the
+    same id rule; entries without the field are left out."""
+    return _read_people(path, 'pose_keypoints_3d', 4)
+
+
 def problem_tensors(extris, intris, keypoints_per_view):
     """extris [V,4,4], intris [V,3,3]; keypoints_per_view: list over views of [17,3] (one person, one frame).
     Returns cams = (R[V,3,3], t[V,3], f[V], c[V,2]) float32, gt_xy [1,V,17,2], conf [1,V,17]."""
@@ -141,5 +175,5 @@ def save_image(path, rgb, quality=95):
     return path
 
 
-__all__ = ['read_image', 'image_size', 'save_image', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'problem_tensors', 'result_dict',
+__all__ = ['read_image', 'image_size', 'save_image', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'read_people', 'read_people3d', 'problem_tensors', 'result_dict',
            'save_result_pkl', 'save_obj']

@@ -55,10 +55,13 @@ def carry_over(prev_x, prev_loss, x_init_t, use_vposer):
     return x0, cold
 
 
-def fit_sequences(engine: MvFit, cams, gt_xy, w_conf, x_init, stages, joints3d=None, **fit_kw):
+def fit_sequences(engine: MvFit, cams, gt_xy, w_conf, x_init, stages, joints3d=None, present=None, **fit_kw):
     """gt_xy [S, T, V, 17, 2], w_conf [S, T, V, 17]: S sequences of T frames of one rig (or per-sequence cameras
     [S, V, ...]); x_init [S, T, 118]: the full initial guess of every frame (used for frame 0 and after a restart).
     joints3d = (gt3d [S, T, 17, 3], conf3d [S, T, 17]): the use_3d targets of every frame (stages carrying F_USE_3D).
+    present [S, T] bool (None: every frame of every sequence): an absent (s, t) is not fitted and does not touch the
+    state sequence s carries - its chain continues from its last present frame, and its first present frame is a cold
+    start; the outputs of an absent (s, t) are NaN (n_closure 0, restarted False).
     Returns (x [S, T, 118] tensor, dict(final_loss [S, T], n_closure [S, T], restarted [S, T] bool))."""
     gt = np.asarray(gt_xy, np.float32)
     wc = np.asarray(w_conf, np.float32)
@@ -72,13 +75,22 @@ def fit_sequences(engine: MvFit, cams, gt_xy, w_conf, x_init, stages, joints3d=N
     restarted = np.zeros((S, T), bool)
     use_vposer = bool(int(stages[0].get('flags', 0)) & 1)
     prev_x, prev_loss = None, None
+    pres = None
+    if present is not None:
+        pres = np.asarray(present, bool).reshape(S, T)
+        xs.fill_(float('nan'))
+        final.fill_(float('nan'))
+        # carried state per sequence; an infinite loss makes carry_over start a sequence cold at its first present frame
+        prev_x = xi[:, 0].clone()
+        prev_loss = torch.full((S,), float('inf'), device=engine.device)
     for t in range(T):
-        if t == 0:
+        here = np.ones(S, bool) if pres is None else pres[:, t]
+        if t == 0 and pres is None:
             x_start, cold = xi[:, t], np.ones(S, bool)
         else:
             x_start, cold = carry_over(prev_x, prev_loss, xi[:, t], use_vposer)
-        restarted[:, t] = cold
-        for sel, stg in ((np.flatnonzero(cold), stages), (np.flatnonzero(~cold), warm)):
+        restarted[:, t] = cold & here
+        for sel, stg in ((np.flatnonzero(cold & here), stages), (np.flatnonzero(~cold & here), warm)):
             if sel.size == 0:
                 continue
             cam_sel = tuple(np.asarray(c)[sel] for c in cams) if np.ndim(cams[0]) == 4 else cams
@@ -90,7 +102,11 @@ def fit_sequences(engine: MvFit, cams, gt_xy, w_conf, x_init, stages, joints3d=N
             xs[idx, t] = xf
             final[idx, t] = st['final_loss']
             ncl[idx, t] = st['n_closure']
-        prev_x, prev_loss = xs[:, t], final[:, t]
+        if pres is None:
+            prev_x, prev_loss = xs[:, t], final[:, t]
+        elif here.any():
+            idx = torch.as_tensor(np.flatnonzero(here), device=engine.device)
+            prev_x[idx], prev_loss[idx] = xs[idx, t], final[idx, t]
     return xs, dict(final_loss=final, n_closure=ncl, restarted=restarted)
 
 

@@ -1,12 +1,13 @@
-"""Timing of the overlay renderer (include/mvfit.h:mvfit_render_overlay, csrc/render.hip) and of fit_folder's stages with and
-without save_images.
+"""Timing of the overlay renderer (include/mvfit.h:mvfit_render_overlay / mvfit_render_scene, csrc/render.hip) and of
+fit_folder's stages with and without save_images.
 
-  python tools/render_timing.py [--reps 20]
+  python tools/render_timing.py [--reps 20] [--bodies 4] [--no-folder]
 
 Prints (1) the render kernels' time per 2048 x 1536 image from hipEvents around render_overlay, for one image per call,
 64 images per call (the batch driver's largest call) and a close-up whose faces cover thousands of pixels each, and
 (2) fit_folder's stage times on the reference's demo inputs (tests/golden/demo_data) plus synthetic 2048 x 1536 JPEGs,
-once without and once with save_images."""
+once without and once with save_images.  With --bodies N > 0 also (3) render_scene with one body per image (the work of
+render_overlay through the other entry point) and with N bodies per image, 1 and 64 images per call."""
 import argparse
 import os
 import shutil
@@ -46,8 +47,38 @@ def kernel_time(eng, n, reps):
         t1.synchronize()
         per.append(t0.elapsed_time(t1) / n)
     per = np.asarray(per)
-    print('render_overlay 2048x1536, n=%-3d  per image: median %.3f ms  min %.3f ms  (%d reps)'
-          % (n, np.median(per), per.min(), reps))
+    print('render_overlay 2048x1536, n=%-3d  per image: median %.3f ms  min %.3f ms  max %.3f ms  (%d reps)'
+          % (n, np.median(per), per.min(), per.max(), reps))
+
+
+def scene_time(eng, n, bodies, reps):
+    """render_scene, ``bodies`` bodies per 2048 x 1536 image standing 0.7 m apart on a line through the ring's centre; with
+    one body the problems, views and vertices of kernel_time, i.e. the work of render_overlay."""
+    H, W, V = 1536, 2048, 8
+    cams = syn.make_camera_ring(V)
+    B = max(bodies, (n + V - 1) // V)
+    eng.set_problems(cams, np.zeros((B, V, 17, 2), np.float32), np.zeros((B, V, 17), np.float32))
+    x = pack_params(B=B, **syn.make_frames(B))
+    x[:, 82] += 0.7 * (np.arange(B) % bodies - 0.5 * (bodies - 1))
+    verts, joints = eng.vertices(x)
+    imgs = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device=eng.device)
+    out = torch.empty_like(imgs)
+    lists = [[(i // V + k) % B for k in range(bodies)] for i in range(n)]
+    view = [i % V for i in range(n)]
+    _, bid = eng.render_scene(verts, joints, imgs, lists, view, out=out, body_id=True)          # warm-up
+    covered = float((bid >= 0).float().mean())
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    per = []
+    for _ in range(reps):
+        t0.record()
+        eng.render_scene(verts, joints, imgs, lists, view, out=out)
+        t1.record()
+        t1.synchronize()
+        per.append(t0.elapsed_time(t1) / n)
+    per = np.asarray(per)
+    print('render_scene   2048x1536, n=%-3d bodies=%d  per image: median %.3f ms  min %.3f ms  max %.3f ms  (%d reps, '
+          '%.1f%% of the pixels covered)' % (n, bodies, np.median(per), per.min(), per.max(), reps, 100 * covered))
 
 
 def close_up_time(eng, model, reps):
@@ -104,13 +135,19 @@ def folder_stages(model):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--bodies', type=int, default=0, help='also time render_scene with 1 and with this many bodies per image')
+    ap.add_argument('--no-folder', action='store_true', help='skip the fit_folder stage times')
     a = ap.parse_args()
     model = body_model()
     with MvFit(model) as eng:
         for n in (1, 64):
             kernel_time(eng, n, a.reps)
+        for nb in sorted({1, a.bodies} if a.bodies > 0 else ()):
+            for n in (1, 64):
+                scene_time(eng, n, nb, a.reps)
         close_up_time(eng, model, a.reps)
-    folder_stages(model)
+    if not a.no_folder:
+        folder_stages(model)
 
 
 if __name__ == '__main__':
