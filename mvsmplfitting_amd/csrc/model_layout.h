@@ -1,6 +1,6 @@
 // Layout of the model constants the kernels read: the sizes their tables depend on and the ModelLds image.  Shared by the
-// device code (mvfit_device.h, vposer_service.h) and the host builder of the tables (model_prep.cpp), so it includes no
-// HIP header.
+// device code (mvfit_device.h, vposer_service.h), the host builder of the tables (model_prep.cpp) and the fit's planning
+// (fit_plan.cpp), so it includes no HIP header.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +19,8 @@ constexpr int KNNZ_MAX = 160;     // non-zeros of the 17 x ns keypoint selection
 constexpr int KP_NZ = 12;         // padded per-keypoint list length (LSP regressor rows have 4-9 non-zeros)
 constexpr int VS_NZ = 2;          // padded per-vertex list length (a vertex usually feeds one keypoint)
 constexpr int VPS_SLICES = 8;     // VPoser decoder helpers per set = slices of the 512 fc2 units (vposer_service.h)
+constexpr int VPS_PMAX = 24;      // problems per helper set (wave w polls the slots w, w + 8, w + 16)
+constexpr int VPS_MAX_SETS = 16;  // 16 for launches of <= 32 problems, else 8 (fit_plan.h)
 
 // Model constants every per-problem workgroup keeps in LDS (bulk-copied once per launch).
 struct ModelLds {

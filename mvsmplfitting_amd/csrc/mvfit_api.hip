@@ -10,7 +10,8 @@
 //                      the objective reads, or full closures whose vertex passes run beside it (asynchronous fit:
 //                      AsyncRing); optionally VPoser decoder helpers behind the problems' workgroups
 //   lbfgs_kat_kernel   float64 instantiation of the state machine on analytic objectives
-// Host side: the C ABI; the model's tables are built by model_prep.cpp and uploaded by mvfit_create_ex.
+// Host side: the C ABI; the model's tables are built by model_prep.cpp and uploaded by mvfit_create_ex; how a fit runs is
+// decided by fit_plan.cpp and executed by mvfit_fit.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "closure_device.h"
+#include "fit_plan.h"
 #include "model_prep.h"
 
 namespace mvfit {
@@ -885,6 +887,20 @@ static int debug_hook(const char* name) { const char* e = getenv(name); return e
 static constexpr int debug_hook(const char*) { return 0; }
 #endif
 
+// what the fit's plan (fit_plan.h) depends on in this ctx; mvfit_fit adds the fit's own stages and options
+static FitPlanIn plan_inputs(const mvfit_ctx* c) {
+    FitPlanIn in;
+    in.B = c->B; in.n_cu = c->n_cu; in.ntiles = c->M.ntiles;
+    in.half_basis = c->M.bs_h2 != nullptr; in.sparse_skinning = c->M.wsp_w != nullptr; in.nv_even = (c->M.nv & 1) == 0;
+    in.helper_memory = c->vps_mem != nullptr;
+    in.profile = c->profile; in.resident_auto_off = c->resident_auto_off;
+    in.debug_nopass = debug_hook("MVFIT_DEBUG_NOPASS") != 0;          // (hooks build only)
+    in.round_mode = c->opt.round_mode; in.resident_pass = c->opt.resident_pass; in.sdf_two_phase = c->opt.sdf_two_phase;
+    in.sdf_service = c->opt.sdf_service; in.vposer_helpers = c->opt.vposer_helpers; in.vposer_sets = c->opt.vposer_sets;
+    in.work_queue = c->opt.work_queue;
+    return in;
+}
+
 extern "C" void mvfit_options_default(mvfit_options* o) {
     if (!o) return;
     memset(o, 0, sizeof(*o));
@@ -914,7 +930,6 @@ static int read_options(mvfit_ctx* c, const mvfit_options* in, mvfit_options& o)
     return MVFIT_OK;
 }
 
-extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, const mvfit_model* m, const mvfit_options* opts);
 extern "C" int mvfit_create(mvfit_ctx** out, int device, void* hip_stream, const mvfit_model* m) {
     return mvfit_create_ex(out, device, hip_stream, m, nullptr);
 }
@@ -925,7 +940,6 @@ extern "C" int mvfit_get_options(const mvfit_ctx* c, mvfit_options* o) {
     return MVFIT_OK;
 }
 
-static void drop_graph(mvfit_ctx* c);
 extern "C" int mvfit_set_options(mvfit_ctx* c, const mvfit_options* opts) {
     if (!c || !opts) return MVFIT_E_ARG;
     mvfit_options o;
@@ -1316,14 +1330,30 @@ extern "C" int mvfit_full_pose(mvfit_ctx* c, const float* params, uint32_t flags
     return MVFIT_OK;
 }
 
-// decoder helpers (vposer_service.h): launch geometry, see launch_persistent
-constexpr int kVpsSets = 8;                                             // sets of a launch with more than 32 problems
-constexpr int kVpsHelpers = kVpsSets * VPS_SLICES;                      // 64 CUs
-constexpr int kVpsMaxSparse = 160, kVpsMaxAsync = 96;
-static_assert(kVpsMaxSparse <= kVpsSets * VPS_PMAX && kVpsMaxSparse + kVpsHelpers <= 256 && 32 + VPS_MAX_SETS * VPS_SLICES <= 160, "all workgroups resident");
-
+// Test route of mvfit_closure (MVFIT_CLOSURE_VP_HELPERS=1, read per call; VPoser flag, no SDF term): the closure decodes
+// the body pose on helper workgroups of its own launch - the decoder of the production single-launch fits
+// (vposer_service.h), whose summation order differs from the in-workgroup decoder - and, like those fits, evaluates the
+// objective from the vertices it computes itself while the full vertex pass runs on the operands it published.
 static int closure_via_helpers(mvfit_ctx* c, const mvfit_weights* w, const float* params, float* loss, float* grad,
-                               float* verts, float* joints);
+                               float* verts, float* joints) {
+    const int n = c->B;
+    if (n > kVpsMaxSparse) return fail(c, MVFIT_E_ARG, "MVFIT_CLOSURE_VP_HELPERS: at most %d problems (all workgroups resident)", kVpsMaxSparse);
+    DevModel M = c->M;
+    const int nsets = plan_nsets(plan_inputs(c), n, 0, false);       // (the automatic count: the route does not read vposer_sets)
+    HIP_OK(c, hipMemsetAsync(c->vps_mem, 0, c->vps_words * 8 + 8, c->stream));
+    M.vps.req = c->vps_mem;
+    M.vps.resp = c->vps_mem + (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN;
+    M.vps.stat = reinterpret_cast<unsigned*>(c->vps_mem + c->vps_words);
+    M.vps.nsets = nsets;
+    M.vps.nprob = n;
+    M.vps.fault = 0;
+    c->vps_stats[0] = 1;
+    hipLaunchKernelGGL(closure_kernel<true>, dim3(n + nsets * VPS_SLICES), dim3(STEP_NT), step_lds(), c->stream, M,
+                       (const ObsBlock*)c->d_obs, c->V, to_dev(*w), c->P, params, 0, loss, grad, joints, (const SdfAdj*)nullptr);
+    HIP_OK(c, hipGetLastError());
+    if (verts) return run_vertex_pass(c, verts);
+    return MVFIT_OK;
+}
 
 extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* params, float* loss, float* grad,
                              float* verts, float* joints) {
@@ -1361,40 +1391,21 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
     return MVFIT_OK;
 }
 
-// Test route of mvfit_closure (MVFIT_CLOSURE_VP_HELPERS=1, read per call; VPoser flag, no SDF term): the closure decodes
-// the body pose on helper workgroups of its own launch - the decoder of the production single-launch fits
-// (vposer_service.h), whose summation order differs from the in-workgroup decoder - and, like those fits, evaluates the
-// objective from the vertices it computes itself while the full vertex pass runs on the operands it published.
-static int closure_via_helpers(mvfit_ctx* c, const mvfit_weights* w, const float* params, float* loss, float* grad,
-                               float* verts, float* joints) {
-    const int n = c->B;
-    if (n > kVpsMaxSparse) return fail(c, MVFIT_E_ARG, "MVFIT_CLOSURE_VP_HELPERS: at most %d problems (all workgroups resident)", kVpsMaxSparse);
-    DevModel M = c->M;
-    const int cap = n <= 32 ? VPS_MAX_SETS : kVpsSets;
-    const int nsets = std::max((n + VPS_PMAX - 1) / VPS_PMAX, std::min(cap, n));
-    HIP_OK(c, hipMemsetAsync(c->vps_mem, 0, c->vps_words * 8 + 8, c->stream));
-    M.vps.req = c->vps_mem;
-    M.vps.resp = c->vps_mem + (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN;
-    M.vps.stat = reinterpret_cast<unsigned*>(c->vps_mem + c->vps_words);
-    M.vps.nsets = nsets;
-    M.vps.nprob = n;
-    M.vps.fault = 0;
-    c->vps_stats[0] = 1;
-    hipLaunchKernelGGL(closure_kernel<true>, dim3(n + nsets * VPS_SLICES), dim3(STEP_NT), step_lds(), c->stream, M,
-                       (const ObsBlock*)c->d_obs, c->V, to_dev(*w), c->P, params, 0, loss, grad, joints, (const SdfAdj*)nullptr);
-    HIP_OK(c, hipGetLastError());
-    if (verts) return run_vertex_pass(c, verts);
-    return MVFIT_OK;
+// the optimiser's scalar options (the gtol segments are the caller's)
+static LbOpts lb_opts(const mvfit_lbfgs_opts& o, int num_stages) {
+    LbOpts O;
+    memset(&O, 0, sizeof(O));
+    O.lr = o.lr; O.tol_grad = o.tolerance_grad; O.tol_change = o.tolerance_change; O.ftol = o.ftol; O.gtol = o.gtol;
+    O.max_iter = o.max_iter; O.max_eval = o.max_iter * 5 / 4; O.history = o.history; O.maxiters = o.maxiters;
+    O.num_stages = num_stages;
+    return O;
 }
 
 static int make_opts(mvfit_ctx* c, const mvfit_lbfgs_opts* o, uint32_t flags, LbOpts& O) {
     if (o->max_iter <= 0 || o->history <= 0 || o->history > MVFIT_HISTORY || o->maxiters <= 0 || o->num_stages <= 0 ||
         o->num_stages > MVFIT_MAX_STAGES)
         return fail(c, MVFIT_E_ARG, "bad lbfgs options");
-    memset(&O, 0, sizeof(O));
-    O.lr = o->lr; O.tol_grad = o->tolerance_grad; O.tol_change = o->tolerance_change; O.ftol = o->ftol; O.gtol = o->gtol;
-    O.max_iter = o->max_iter; O.max_eval = o->max_iter * 5 / 4; O.history = o->history; O.maxiters = o->maxiters;
-    O.num_stages = o->num_stages;
+    O = lb_opts(*o, o->num_stages);
     O.reuse_outer = (flags & MVFIT_F_REUSE_OUTER_VALUE) ? 1 : 0;
     // parameter tensors that take part in the gtol test (fitting.py:115-116): requires_grad ones,
     // as index ranges of the compact optimiser vector (reference final_params order)
@@ -1481,9 +1492,6 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
 // ---------------------------------------------------------------------------------------------------------
 static const int kRingSlots = 128;
 static const int kPassBatch = 24;
-static const int kAsyncMaxB = 160;        // one CU per problem for the optimiser: leave >= 96 CUs to the passes
-static const int kResidentMaxB = 128;     // with the resident pass: its workgroups (ntiles / 2 at this size) hold a CU each for the whole fit
-static const int kPassWords = 512;        // back-pressure words of the ring (one per resident-pass workgroup; the gate kernels use word 0)
 static const int kVpLogRounds = 1024;     // mvfit_profile: rounds of the resident pass that are stamped
 
 // The ring is sized by the SUB-BATCH (rb problems, a multiple of 32), not by the batch: only one sub-batch uses it at a
@@ -1524,122 +1532,81 @@ static int ensure_async(mvfit_ctx* c, int rb) {
     return MVFIT_OK;
 }
 
-// Decoder helpers (vposer_service.h) ride on the single-launch fits with the VPoser prior: min(8, n) sets of 8 helper
-// workgroups behind the n problems' ones, every set serving the problems b with b % nsets == s.  All workgroups of the
-// launch must be resident at once (the problems wait for their helpers' answers): such fits run in sub-batches of at most
-// kVpsMaxSparse problems (objective vertices only) / kVpsMaxAsync (asynchronous: the passes keep >= 96 CUs) - every
-// problem's arithmetic is the same whatever the slicing.  mvfit_options::vposer_helpers = 0 keeps the decoder in the
+// Decoder helpers (vposer_service.h) ride on the single-launch fits with the VPoser prior: `nsets` sets of 8 helper
+// workgroups behind the n problems' ones, every set serving the problems b with b % nsets == s (the count comes with the
+// plan: fit_plan.cpp).  All workgroups of the launch must be resident at once (the problems wait for their helpers' answers)
+// - every problem's arithmetic is the same whatever the slicing.  mvfit_options::vposer_helpers = 0 keeps the decoder in the
 // problems' own workgroups (another summation order: results differ in the last bits).
-static bool vps_enabled(const mvfit_ctx* c, const StageWeights& SW) {
-    return (SW.w[0].flags & MVFIT_F_VPOSER) && c->vps_mem && c->opt.vposer_helpers != 0;
-}
-
-static int resident_tiles_per_wg(const mvfit_ctx* c, int opt_grid);
-
-// decoder-helper sets a single-launch fit of n problems carries (0: none).  with_passes: the launch is an asynchronous fit
-// (vertex passes beside it) - the automatic choice then keeps the RESIDENT pass: 16 sets next to <= 32 problems are 160
-// optimiser-kernel workgroups, which leave no room for the pass's 108; 8 sets (96 workgroups) do, and measure the same closure
-// rate (the mode is bound by the decoder hand-offs, profiles/r5_progress.md) - so the shipped yaml's default mode no longer
-// runs its passes as per-round launches (round 6).  Results do not depend on the number of sets (fixed summation order).
-static int persistent_nsets(const mvfit_ctx* c, const StageWeights& SW, int n, bool with_passes) {
-    if (!(vps_enabled(c, SW) && n <= kVpsMaxSparse)) return 0;
-    // few problems: 16 sets (two problems per helper at 32: less queueing behind another problem's request)
-    const int cap = n <= 32 ? VPS_MAX_SETS : kVpsSets;
-    // at least ceil(n / VPS_PMAX) sets: a set has VPS_PMAX request / answer slots (the knob cannot push problems past them)
-    const int need = (n + VPS_PMAX - 1) / VPS_PMAX;
-    int want = c->opt.vposer_sets > 0 ? std::min(c->opt.vposer_sets, cap) : cap;
-    if (c->opt.vposer_sets <= 0 && with_passes && want > kVpsSets) {
-        const int full = std::max(need, std::min(want, n)), half = std::max(need, std::min(kVpsSets, n));
-        if (!resident_tiles_per_wg(c, n + full * VPS_SLICES) && resident_tiles_per_wg(c, n + half * VPS_SLICES)) want = kVpsSets;
-    }
-    return std::max(need, std::min(want, n));
-}
-// workgroups of that launch: one per problem + the helpers behind them, one CU each (LDS)
-static int persistent_grid(const mvfit_ctx* c, const StageWeights& SW, int n, bool with_passes) {
-    return n + persistent_nsets(c, SW, n, with_passes) * VPS_SLICES;
-}
-
-static int launch_persistent(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int cap, const AsyncRing& R, int b_lo,
-                             int b_hi, int done_target, int pause_stage, bool sdfs = false, int* queue = nullptr, int b_end = 0) {
-    const int n = b_hi - b_lo;
+static int launch_persistent(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int cap, const AsyncRing& R, const FitLaunch& L,
+                             int pause_stage, bool sdfs = false, int* queue = nullptr, int b_end = 0) {
+    const int n = L.b_hi - L.b_lo;
     DevModel M = c->M;
     int grid = n;
-    if (const int nsets = persistent_nsets(c, SW, n, R.tag != nullptr)) {
+    if (L.nsets) {
         HIP_OK(c, hipMemsetAsync(c->vps_mem, 0, c->vps_words * 8, c->stream));
         M.vps.req = c->vps_mem;
         M.vps.resp = c->vps_mem + (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN;
         M.vps.stat = reinterpret_cast<unsigned*>(c->vps_mem + c->vps_words);
-        M.vps.nsets = nsets;
+        M.vps.nsets = L.nsets;
         M.vps.nprob = n;
         M.vps.fault = debug_hook("MVFIT_VP_FAULT") != 0;                                     // test hook (hooks build only): helpers that never answer
-        grid = n + nsets * VPS_SLICES;
+        grid = n + L.nsets * VPS_SLICES;
         c->vps_stats[0] += 1;
     }
     const bool lean = !(SW.w[0].flags & (MVFIT_F_VPOSER | MVFIT_F_PRIOR_GMM | MVFIT_F_USE_3D));    // (flags are the same in all stages)
     // (service launches - the stages with the SDF term, mvfit_options::sdf_service - have their own instantiations: the other
-    // kernels carry no trace of the service; MVFIT_F_REUSE_OUTER_VALUE fits keep the chained rounds, see mvfit_fit)
+    // kernels carry no trace of the service; MVFIT_F_REUSE_OUTER_VALUE fits keep the chained rounds, see fit_plan.cpp)
     auto kern = sdfs ? (M.vps.nsets ? fit_persistent_kernel<true, false, false, true> : fit_persistent_kernel<false, false, false, true>)
                 : queue ? (lean ? fit_persistent_kernel<false, false, true, false, true> : fit_persistent_kernel<false, false, false, false, true>)
                 : M.vps.nsets ? (O.reuse_outer ? fit_persistent_kernel<true, true, false> : fit_persistent_kernel<true, false, false>)
                 : O.reuse_outer ? (lean ? fit_persistent_kernel<false, true, true> : fit_persistent_kernel<false, true, false>)
                 : lean ? fit_persistent_kernel<false, false, true> : fit_persistent_kernel<false, false, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(STEP_NT), persistent_lds((SW.w[0].flags & MVFIT_F_VPOSER) != 0), c->stream, M,
-                       (const ObsBlock*)c->d_obs, c->V, SW, O, c->P, c->F, cap, R, b_lo, done_target, pause_stage, queue, b_end);
+                       (const ObsBlock*)c->d_obs, c->V, SW, O, c->P, c->F, cap, R, L.b_lo, L.n_target, pause_stage, queue, b_end);
     HIP_OK(c, hipGetLastError());
     return MVFIT_OK;
 }
 
-// How the passes of an asynchronous (sub-batch) fit run: tiles per workgroup of the RESIDENT pass (one launch per fit, basis
-// stationary in registers; its ceil(ntiles / tpw) workgroups must all be resident next to the optimiser's `opt_grid` ones,
-// every one of them a CU), or 0 = a gate + a pass launch per closure round (dense skinning rows, exact-fp32 contraction,
-// launches that do not leave the CUs - e.g. 160 optimiser + helper workgroups with the VPoser prior).
-// mvfit_options::resident_pass = 0 / 1 / 2 forces the choice (a forced value that does not fit can stall the fit: the
-// optimiser then waits 20 ms for the ring once and stops waiting; fit() reports the lost passes).
-// workgroups of the resident pass: form 1 / 2 = tiles per workgroup; 3 = two tiles per workgroup split into contraction and
-// worker waves (lbs_vertex_pass_resident_roles_kernel)
-static int resident_grid(const mvfit_ctx* c, int form) {
-    if (!form) return 0;
-    const int tiles = form >= 2 ? 2 : 1;
-    return (c->M.ntiles + tiles - 1) / tiles;
+// mvfit_profile: the resident pass's stamp log -> per round: service span = last workgroup's stores drained - first workgroup saw
+// the operands; busy = a workgroup's own drained - seen (wall clock, 100 MHz)
+static int reduce_pass_log(mvfit_ctx* c, int res_grid) {
+    std::vector<unsigned long long> lg((size_t)kVpLogRounds * res_grid * 2);
+    HIP_OK(c, hipMemcpy(lg.data(), c->d_vp_log, lg.size() * 8, hipMemcpyDeviceToHost));
+    double span = 0.0, busy = 0.0, slowest = 0.0;
+    int n = 0;
+    for (int r = 0; r < kVpLogRounds; ++r) {
+        unsigned long long lo = ~0ull, hi = 0ull, bsum = 0ull, bmax = 0ull;
+        bool all = true;
+        for (int w = 0; w < res_grid; ++w) {
+            const unsigned long long a = lg[((size_t)r * res_grid + w) * 2], z = lg[((size_t)r * res_grid + w) * 2 + 1];
+            if (!z) { all = false; break; }
+            lo = std::min(lo, a); hi = std::max(hi, z); bsum += z - a; bmax = std::max(bmax, z - a);
+        }
+        if (!all) break;
+        span += (double)(hi - lo) * 1e-5; busy += (double)bsum / res_grid * 1e-5;      // ticks of 10 ns -> ms
+        slowest += (double)bmax * 1e-5;
+        ++n;
+    }
+    c->res_rounds = n;
+    c->res_span_ms = n ? span / n : 0.0;
+    c->res_busy_ms = n ? busy / n : 0.0;
+    c->res_slowest_ms = n ? slowest / n : 0.0;
+    return MVFIT_OK;
 }
 
-static int resident_tiles_per_wg(const mvfit_ctx* c, int opt_grid) {
-    if (!c->M.bs_h2 || !c->M.wsp_w || (c->M.nv & 1)) return 0;      // (the resident pass stores vertex pairs: even vertex count)
-    if (c->opt.resident_pass >= 0) return c->opt.resident_pass == 2 ? 3 : c->opt.resident_pass;      // (form 2 was dropped: it maps to 3)
-    // automatic mode: a fit on this ctx whose resident workgroups (or whose optimiser) gave up waiting has shown that the launch
-    // does not get the CUs the choice assumes (a shared device, a CU mask): later fits use the per-round launches
-    if (c->resident_auto_off) return 0;
-    const int room = c->n_cu - 4 - opt_grid;           // (4 CUs of slack: nothing in HIP promises that every CU takes a workgroup)
-    if (c->M.ntiles <= room) return 1;
-    if ((c->M.ntiles + 1) / 2 <= room) return 3;       // two tiles per workgroup, contraction / worker roles (15-20 % faster than form 2)
-    return 0;
-}
+// ---- the four drivers of a planned phase (fit_plan.h); *complete = problems that finished (a lead phase: that left it) ----
 
-// sdf_service: the launch continues fits that are paused in front of their first stage with the SDF term; every closure round
-// of such a stage asks for the term (closure_device.h: publish_sdf_request): per round the pass stream carries gate -> vertex
-// pass -> the term's kernels (launch_sdf_term, whose pull-back publishes the answer tag) - per-round launches by construction
-// (the term's kernels need the round's vertices complete: a launch boundary).
-static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int cap, int* seen_out, int pause_stage = MVFIT_MAX_STAGES + 1,
-                     bool sdf_service = false) {
-    const int B = c->B;
-    // More problems than the optimiser gets CUs (one workgroup per CU, >= 96 CUs left to the passes): time-sliced in
-    // sub-batches of whole 32-problem chunks, one after the other - every sub-batch is the same asynchronous fit (problems
-    // are independent: the results do not depend on the slicing, tests/test_gpu_large_batch.py).
-    // (the sub-batch size follows from the form the passes REALLY take for the optimiser grid it gives: 128 problems beside the
-    // resident pass, 160 when the passes run as per-round launches anyway - dense skinning rows, a forced resident_pass = 0, ...)
+// DRIVER_ASYNC / DRIVER_ASYNC_SDF: per planned launch one fit_persistent_kernel on the ctx stream and its vertex passes on the
+// pass stream (the mechanism: the block comment above; sub-batches, work queue and pass form come with the plan).  With the SDF
+// service the launch continues fits that are paused in front of their first stage with the term, and every round's pass is
+// followed by the term's kernels (launch_sdf_term, whose pull-back publishes the answer tag) - per-round launches by
+// construction (the term's kernels need the round's vertices complete: a launch boundary).
+static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
+    const int B = c->B, tpw = ph.form, res_grid = ph.res_grid;
+    const bool sdf_service = ph.driver == DRIVER_ASYNC_SDF, refill = ph.refill;
     const bool dbg_nopass = debug_hook("MVFIT_DEBUG_NOPASS") != 0;          // (hooks build only)
-    auto sub_batch = [&](int maxb) { const int nsub = (B + maxb - 1) / maxb; return ((B + nsub - 1) / nsub + 31) / 32 * 32; };
-    int per = sub_batch(vps_enabled(c, SW) ? kVpsMaxAsync : kResidentMaxB);
-    int tpw = (dbg_nopass || sdf_service) ? 0 : resident_tiles_per_wg(c, persistent_grid(c, SW, std::min(B, per), true));
-    if (!tpw && !vps_enabled(c, SW)) per = sub_batch(kAsyncMaxB);
-    // Round 6: more problems than optimiser workgroups run as ONE launch with a work queue when the resident pass serves it (its
-    // workgroups follow a ring row through the problems it takes; the per-round launch kernels address problems by row): `per`
-    // rows, a row takes the next unfitted problem when its own has finished - no serial sub-batches, no idle tail per sub-batch.
-    // (Not with decoder helpers: their request slots belong to problems; not in service launches.)
-    const bool refill = tpw != 0 && !vps_enabled(c, SW) && !sdf_service && B > per && c->opt.work_queue != 0 && !O.reuse_outer;
-    if (refill) per = kResidentMaxB;
-    const int launch_cap = refill ? (int)std::min<long long>((long long)cap * ((B + per - 1) / per + 1), 1 << 30) : cap;
-    int rc = ensure_async(c, per);
+    if (sdf_service) HIP_OK(c, hipMemsetAsync(c->F.n_done + 1, 0, 8, c->stream));       // (a lead phase has counted its leavers there)
+    int rc = ensure_async(c, ph.per);
     if (rc) return rc;
     AsyncRing R = c->ring;
     const size_t rb = (size_t)R.Bpad;                       // ring stride in problems (>= per)
@@ -1647,9 +1614,6 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
     // polled words: re-initialised every call
     HIP_OK(c, hipMemsetAsync(R.done_round, 0xff, (size_t)c->Bpad * 4, c->stream));
     HIP_OK(c, hipMemsetAsync(R.stats, 0, 16, c->stream));
-    const int res_grid = resident_grid(c, tpw);
-    if (res_grid > kPassWords) return fail(c, MVFIT_E_ARG, "resident vertex pass: %d workgroups > %d back-pressure words", res_grid, kPassWords);
-    if (tpw && per > kResidentMaxB) return fail(c, MVFIT_E_ARG, "resident vertex pass: %d ring rows > %d", per, kResidentMaxB);
     c->resident_tpw = tpw;
     R.npass = tpw ? res_grid : 1;
     c->res_rounds = 0; c->res_span_ms = c->res_busy_ms = c->res_slowest_ms = 0.0;
@@ -1663,9 +1627,8 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
             c->vp_log_words = words;
         }
     }
-    for (int b_lo = 0; b_lo < B; b_lo += refill ? B : per) {
-        const int b_hi = std::min(B, b_lo + per);                 // (refill: the rows of the one launch)
-        const int n_target = refill ? B : b_hi - b_lo;            // problems that leave this launch
+    for (const FitLaunch& L : ph.launches) {
+        const int b_lo = L.b_lo, b_hi = L.b_hi, n_target = L.n_target;
         *h_done = 0;
         // per sub-batch: its tags (the slots are reused by other problems), the pass counter and the count of problems
         // that left the launch (finished or paused) - a sub-batch that stops at the round cap does not keep the later ones
@@ -1686,7 +1649,7 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
             c->h_queue0 = b_hi;                                   // problems [0, rows) start on their rows, the queue hands out the rest
             HIP_OK(c, hipMemcpyAsync(c->d_queue, &c->h_queue0, 4, hipMemcpyHostToDevice, c->stream));
         }
-        rc = launch_persistent(c, SW, O, launch_cap, R, b_lo, b_hi, n_target, pause_stage, sdf_service, refill ? c->d_queue : nullptr, B);
+        rc = launch_persistent(c, SW, O, ph.launch_cap, R, L, ph.pause_stage, sdf_service, refill ? c->d_queue : nullptr, B);
         if (rc) return rc;
         int k = 0;
         if (tpw) {
@@ -1701,7 +1664,7 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
             RA.nslots = kRingSlots; RA.rb = (int)rb;
             RA.b_lo = b_lo; RA.n = b_hi - b_lo;
             RA.flags = (unsigned)debug_hook("MVFIT_DEBUG_NT_OFF");         // (hooks build only) bit 1 = plain vertex stores
-            RA.max_rounds = (unsigned)launch_cap;
+            RA.max_rounds = (unsigned)ph.launch_cap;
             hipError_t e = launch_vertex_pass_resident(c->M, RA, tpw, c->pass_stream);
             if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "resident vertex pass launch: %s", hipGetErrorString(e));
             HIP_OK(c, hipEventRecord(c->ev_batch[0], c->pass_stream));
@@ -1748,7 +1711,7 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
             HIP_OK(c, hipEventRecord(c->ev_batch[k & 3], c->pass_stream));
             if (k >= 2) HIP_OK(c, hipEventSynchronize(c->ev_batch[(k - 2) & 3]));
             if (*h_done >= n_target) break;
-            if ((k + 1) * kPassBatch >= launch_cap) break;
+            if ((k + 1) * kPassBatch >= ph.launch_cap) break;
         }
         }
         // behind the optimiser kernel (all problems of the sub-batch, or the round cap) the ctx stream continues behind the
@@ -1760,33 +1723,94 @@ static int fit_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, int 
     HIP_OK(c, hipMemcpyAsync(c->h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipMemcpyAsync(c->h_done + 1, c->F.n_done + 2, 4, hipMemcpyDeviceToHost, c->stream));   // problems that left, all sub-batches
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    *seen_out = c->h_done[0];
+    // a lead phase: every problem must have LEFT the single-launch kernel at the stage boundary (or finished): one that stopped
+    // at the round cap mid-history would be continued by the chained step kernel, whose two-loop direction reads Gram rows the
+    // single-launch kernel (compact direction form) does not maintain
+    *complete = c->h_done[ph.pause_stage <= MVFIT_MAX_STAGES ? 1 : 0];
+    // automatic mode: a fit whose resident workgroups (or whose optimiser) gave up waiting has shown that the launch does not get
+    // the CUs the choice assumes (a shared device, a CU mask): later fits on this ctx use the per-round launches
     if (tpw && c->opt.resident_pass < 0 && c->async_stats[3]) c->resident_auto_off = true;
-    if (log_on) {
-        // per round: service span = last workgroup's stores drained - first workgroup saw the operands; busy = a workgroup's own
-        // drained - seen (wall clock, 100 MHz)
-        std::vector<unsigned long long> lg((size_t)kVpLogRounds * res_grid * 2);
-        HIP_OK(c, hipMemcpy(lg.data(), c->d_vp_log, lg.size() * 8, hipMemcpyDeviceToHost));
-        double span = 0.0, busy = 0.0, slowest = 0.0;
-        int n = 0;
-        for (int r = 0; r < kVpLogRounds; ++r) {
-            unsigned long long lo = ~0ull, hi = 0ull, bsum = 0ull, bmax = 0ull;
-            bool all = true;
-            for (int w = 0; w < res_grid; ++w) {
-                const unsigned long long a = lg[((size_t)r * res_grid + w) * 2], z = lg[((size_t)r * res_grid + w) * 2 + 1];
-                if (!z) { all = false; break; }
-                lo = std::min(lo, a); hi = std::max(hi, z); bsum += z - a; bmax = std::max(bmax, z - a);
-            }
-            if (!all) break;
-            span += (double)(hi - lo) * 1e-5; busy += (double)bsum / res_grid * 1e-5;      // ticks of 10 ns -> ms
-            slowest += (double)bmax * 1e-5;
-            ++n;
+    if (log_on) return reduce_pass_log(c, res_grid);
+    return MVFIT_OK;
+}
+
+// DRIVER_SPARSE: the persistent kernel alone, sub-batch after sub-batch
+static int run_sparse(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
+    int* h_done = c->h_done;
+    *h_done = 0;
+    for (const FitLaunch& L : ph.launches) {
+        const int done_before = *h_done;          // (synchronised: problems finished by the earlier sub-batches)
+        for (int rounds = 0; rounds < ph.launch_cap;) {
+            const int chunk = std::min(ph.launch_cap - rounds, 1 << 20);
+            if (const int rc = launch_persistent(c, SW, O, chunk, AsyncRing{}, L, MVFIT_MAX_STAGES + 1)) return rc;
+            rounds += chunk;
+            HIP_OK(c, hipMemcpyAsync(h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(c, hipStreamSynchronize(c->stream));
+            if (*h_done >= done_before + (L.b_hi - L.b_lo)) break;      // this sub-batch is complete (an earlier one may have hit the cap)
         }
-        c->res_rounds = n;
-        c->res_span_ms = n ? span / n : 0.0;
-        c->res_busy_ms = n ? busy / n : 0.0;
-        c->res_slowest_ms = n ? slowest / n : 0.0;
     }
+    *complete = *h_done;
+    return MVFIT_OK;
+}
+
+// DRIVER_EAGER: chained rounds as eager launches bracketed by events (bench.py's per-launch timing of the vertex pass)
+static int run_eager(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
+    int* h_done = c->h_done;
+    for (int rounds = 0; rounds < ph.launch_cap;) {
+        for (int r = 0; r < kGraphRounds; ++r) {
+            int rc = run_vertex_pass(c, c->d_verts);
+            if (!rc && c->F.sdf_adj) rc = run_sdf_term(c, c->d_verts, c->F.sdf_gate, c->stream);
+            if (rc) return rc;
+            prof_begin(c, c->ev_step);
+            hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->V, SW, O,
+                               c->P, c->F);
+            prof_end(c, c->ev_step);
+        }
+        HIP_OK(c, hipGetLastError());
+        rounds += kGraphRounds;
+        HIP_OK(c, hipMemcpyAsync(h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (*h_done >= c->B) break;
+    }
+    *complete = *h_done;
+    return MVFIT_OK;
+}
+
+// DRIVER_GRAPH: chained rounds, kGraphRounds of them per graph replay
+static int run_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
+    const int B = c->B;
+    int* h_done = c->h_done;
+    if (const int rc = ensure_round_graph(c, SW, O)) return rc;
+    // While at most half of the problems have finished, the next replay is queued before the host looks at the
+    // done counter of the current one (the GPU does not idle through the ~30 us host turnaround); later the
+    // replays go one at a time, so that no replay runs after the last problem finished.
+    if (!c->ev_done[0]) {
+        HIP_OK(c, hipEventCreateWithFlags(&c->ev_done[0], hipEventDisableTiming));
+        HIP_OK(c, hipEventCreateWithFlags(&c->ev_done[1], hipEventDisableTiming));
+    }
+    auto enqueue = [&](int slot) -> hipError_t {
+        hipError_t e = hipGraphLaunch(c->round_graph, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h_done[slot], c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->ev_done[slot], c->stream);
+        return e;
+    };
+    int rounds = 0, launched = 0, waited = 0, seen = 0;
+    h_done[0] = h_done[1] = 0;
+    const bool ahead_ok = B >= 8;
+    while (true) {
+        while (launched - waited < ((ahead_ok && seen <= B / 2) ? 2 : 1) && rounds < ph.launch_cap) {
+            HIP_OK(c, enqueue(launched & 1));
+            rounds += c->graph_rounds;
+            ++launched;
+        }
+        if (launched == waited) break;                     // round cap reached
+        HIP_OK(c, hipEventSynchronize(c->ev_done[waited & 1]));
+        seen = h_done[waited & 1];
+        ++waited;
+        if (seen >= B) break;
+    }
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    *complete = seen;
     return MVFIT_OK;
 }
 
@@ -1820,17 +1844,19 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
     if (!c || !sw || !o || !params) return MVFIT_E_ARG;
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     HIP_OK(c, hipSetDevice(c->device));
+    // ---- validate ----
     StageWeights SW;
     memset(&SW, 0, sizeof(SW));
-    bool any_sdf = false;
+    FitPlanIn in = plan_inputs(c);
     if (o->num_stages <= 0 || o->num_stages > MVFIT_MAX_STAGES) return fail(c, MVFIT_E_ARG, "num_stages");
     for (int s = 0; s < o->num_stages; ++s) {
         int rc = check_flags(c, sw[s].flags);
         if (rc) return rc;
         if (sw[s].flags != sw[0].flags) return fail(c, MVFIT_E_ARG, "flags must be identical for all stages");
-        any_sdf = any_sdf || sw[s].coll_loss_weight > 0.f;
+        if (sw[s].coll_loss_weight > 0.f) in.sdf_stages |= 1u << s;
         SW.w[s] = to_dev(sw[s]);
     }
+    const bool any_sdf = in.sdf_stages != 0;
     if (any_sdf && !c->sdf_num_faces)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
     if (any_sdf) {
@@ -1842,24 +1868,12 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
     LbOpts O;
     int rc = make_opts(c, o, sw[0].flags, O);
     if (rc) return rc;
-    // the interpenetration term reads every vertex: it forces the (vertex pass, step) round structure
-    const bool sparse = (sw[0].flags & MVFIT_F_SPARSE_VERTS) != 0 && !any_sdf;
-    // mvfit_options::round_mode = 1 keeps the chained (vertex pass -> step kernel) round graph also without the SDF term
-    const bool serial = c->opt.round_mode == 1;
-    const bool async = !sparse && !any_sdf && c->M.bs_h2 != nullptr && !serial;
-    // With the SDF term: the leading stages whose coll_loss_weight is 0 (stages 1-2 of the yaml) do not need the vertices
-    // before the loss - they run asynchronously like a fit without the term, every problem leaves at the stage boundary,
-    // and the chained rounds take over from the stored optimiser / pose state (a fresh optimiser starts there anyway).
-    int lead = 0;
-    while (lead < o->num_stages && !(sw[lead].coll_loss_weight > 0.f)) ++lead;
-    const bool two_phase = any_sdf && lead >= 1 && lead < o->num_stages && c->M.bs_h2 != nullptr && !serial &&
-                           c->opt.sdf_two_phase != 0;
-    // Round 6: the stages that carry the term run in the single-launch kernel too, with the term as a service (fit_async with
-    // sdf_service; also when the FIRST stage carries it: no lead phase then).  mvfit_options::sdf_service = 0 keeps the chained
-    // rounds - pass -> term -> step kernel per round -, which stay the checker of this path and the structure of profiled fits
-    // and of MVFIT_F_REUSE_OUTER_VALUE fits; sdf_two_phase = 0 (chained rounds in every stage) switches it off as well
-    const bool service = any_sdf && c->M.bs_h2 != nullptr && !serial && c->opt.sdf_two_phase != 0 && c->opt.sdf_service != 0 &&
-                         !O.reuse_outer && !c->profile;
+    const int cap = o->max_rounds > 0 ? o->max_rounds : (o->num_stages * o->maxiters * (O.max_eval + 30) + 8);
+    // ---- plan: phases, drivers, sub-batches, pass form, queue (fit_plan.cpp; the table: DESIGN.md §4.4) ----
+    in.flags = sw[0].flags; in.num_stages = o->num_stages; in.reuse_outer = O.reuse_outer != 0; in.cap = cap;
+    const FitPlan plan = plan_fit(in);
+    if (plan.rc) return fail(c, plan.rc, "%s", plan.err.c_str());
+    // ---- initialise ----
     for (unsigned& v : c->async_stats) v = 0;
     for (unsigned& v : c->vps_stats) v = 0;
     if (c->vps_mem) HIP_OK(c, hipMemsetAsync(c->vps_mem + c->vps_words, 0, 8, c->stream));
@@ -1868,127 +1882,35 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
     HIP_OK(c, hipMemsetAsync(c->F.sdf_gate, sw[0].coll_loss_weight > 0.f ? 1 : 0, (size_t)B * 4, c->stream));
     hipLaunchKernelGGL(fit_init_kernel, dim3(B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, c->F,
                        (const float*)params,
-                       sw[0].flags, (sparse || async || two_phase || service) ? 0 : 1);
+                       sw[0].flags, plan.init_full_pass ? 1 : 0);
     HIP_OK(c, hipGetLastError());
-    int* h_done = c->h_done;
-    *h_done = 0;
-    int rounds = 0;
-    const int cap = o->max_rounds > 0 ? o->max_rounds : (o->num_stages * o->maxiters * (O.max_eval + 30) + 8);
-    if (two_phase) {
-        int seen = 0;
-        rc = fit_async(c, SW, O, cap, &seen, lead);
+    // ---- run the phases; one that does not complete (the round cap) ends the fit ----
+    static int (*const drivers[])(mvfit_ctx*, const StageWeights&, const LbOpts&, const FitPhase&, int*) = {run_async, run_async, run_sparse,
+                                                                                                           run_graph, run_eager};
+    unsigned stats[4] = {0, 0, 0, 0}, sv_lost = 0, sv_gave_up = 0;
+    const FitPhase* capped = nullptr;
+    for (int i = 0; i < plan.nphases && !capped; ++i) {
+        const FitPhase& ph = plan.phase[i];
+        int complete = 0;
+        rc = drivers[ph.driver](c, SW, O, ph, &complete);
         if (rc) return rc;
-        // every problem must have LEFT the single-launch kernel at the stage boundary (or finished): one that stopped at the
-        // round cap mid-history would be continued by the chained step kernel, whose two-loop direction reads Gram rows the
-        // single-launch kernel (compact direction form) does not maintain
-        if (c->h_done[1] < B) {
-            hipLaunchKernelGGL(fit_finish_kernel, dim3(B), dim3(128), 0, c->stream, c->F, params, final_loss, n_closure, n_iter, B,
-                               o->num_stages);
-            HIP_OK(c, hipGetLastError());
-            return fail(c, MVFIT_E_STATE, "fit hit the round cap (%d) before all problems finished the stages without the SDF term", cap);
-        }
+        if (ph.driver == DRIVER_ASYNC_SDF) { sv_lost = c->async_stats[2]; sv_gave_up = c->async_stats[3]; }
+        if (ph.driver <= DRIVER_ASYNC_SDF) for (int k = 0; k < 4; ++k) stats[k] += c->async_stats[k];
+        if (complete < B) capped = &ph;
     }
-    if (service) {
-        unsigned lead_stats[4];
-        for (int i = 0; i < 4; ++i) lead_stats[i] = c->async_stats[i];
-        int seen = 0;
-        HIP_OK(c, hipMemsetAsync(c->F.n_done + 1, 0, 8, c->stream));
-        rc = fit_async(c, SW, O, cap, &seen, MVFIT_MAX_STAGES + 1, true);
-        if (rc) return rc;
-        *h_done = seen;
-        hipLaunchKernelGGL(fit_finish_kernel, dim3(B), dim3(128), 0, c->stream, c->F, params, final_loss, n_closure, n_iter, B,
-                           o->num_stages);
-        HIP_OK(c, hipGetLastError());
-        // a gate that timed out lets the term's kernels run on another round's operands, a problem whose answer never came ends
-        // with a NaN loss: neither is a result
-        const unsigned sv_lost = c->async_stats[2], sv_gave_up = c->async_stats[3];
-        for (int i = 0; i < 4; ++i) c->async_stats[i] += lead_stats[i];               // mvfit_fit_stats: the whole fit
-        if (sv_lost || sv_gave_up)
-            return fail(c, MVFIT_E_STATE, "SDF service rounds degraded (%u operand sets lost, %u waits given up): the fit is not valid - "
-                        "is the GPU shared?  (mvfit_options::sdf_service = 0 runs these stages as chained rounds)", sv_lost, sv_gave_up);
-        if (seen < B) return fail(c, MVFIT_E_STATE, "fit hit the round cap (%d) before all problems finished", cap);
-        return MVFIT_OK;
-    }
-    if (async) {
-        int seen = 0;
-        rc = fit_async(c, SW, O, cap, &seen);
-        if (rc) return rc;
-        *h_done = seen;
-    } else if (sparse) {
-        // (with decoder helpers: sub-batches whose workgroups are all resident, one after the other)
-        const int maxb = vps_enabled(c, SW) ? kVpsMaxSparse : B;
-        const int nsub = (B + maxb - 1) / maxb, per = (B + nsub - 1) / nsub;
-        for (int b_lo = 0; b_lo < B; b_lo += per) {
-            const int b_hi = std::min(B, b_lo + per);
-            const int done_before = *h_done;          // (synchronised: problems finished by the earlier sub-batches)
-            rounds = 0;
-            while (rounds < cap) {
-                const int chunk = std::min(cap - rounds, 1 << 20);
-                rc = launch_persistent(c, SW, O, chunk, AsyncRing{}, b_lo, b_hi, b_hi, MVFIT_MAX_STAGES + 1);
-                if (rc) return rc;
-                rounds += chunk;
-                HIP_OK(c, hipMemcpyAsync(h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
-                HIP_OK(c, hipStreamSynchronize(c->stream));
-                if (*h_done >= done_before + (b_hi - b_lo)) break;      // this sub-batch is complete (an earlier one may have hit the cap)
-            }
-        }
-    } else if (c->profile) {
-        // eager launches bracketed by events (bench.py's per-launch timing of the vertex pass)
-        while (rounds < cap) {
-            for (int r = 0; r < kGraphRounds; ++r) {
-                rc = run_vertex_pass(c, c->d_verts);
-                if (!rc && any_sdf) rc = run_sdf_term(c, c->d_verts, c->F.sdf_gate, c->stream);
-                if (rc) return rc;
-                prof_begin(c, c->ev_step);
-                hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(B), dim3(STEP_NT), step_gram_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->V, SW, O,
-                                   c->P, c->F);
-                prof_end(c, c->ev_step);
-            }
-            HIP_OK(c, hipGetLastError());
-            rounds += kGraphRounds;
-            HIP_OK(c, hipMemcpyAsync(h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(c, hipStreamSynchronize(c->stream));
-            if (*h_done >= B) break;
-        }
-    } else {
-        rc = ensure_round_graph(c, SW, O);
-        if (rc) return rc;
-        // While at most half of the problems have finished, the next replay is queued before the host looks at the
-        // done counter of the current one (the GPU does not idle through the ~30 us host turnaround); later the
-        // replays go one at a time, so that no replay runs after the last problem finished.
-        if (!c->ev_done[0]) {
-            HIP_OK(c, hipEventCreateWithFlags(&c->ev_done[0], hipEventDisableTiming));
-            HIP_OK(c, hipEventCreateWithFlags(&c->ev_done[1], hipEventDisableTiming));
-        }
-        auto enqueue = [&](int slot) -> hipError_t {
-            hipError_t e = hipGraphLaunch(c->round_graph, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&h_done[slot], c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipEventRecord(c->ev_done[slot], c->stream);
-            return e;
-        };
-        int launched = 0, waited = 0, seen = 0;
-        h_done[0] = h_done[1] = 0;
-        const bool ahead_ok = B >= 8;
-        while (true) {
-            while (launched - waited < ((ahead_ok && seen <= B / 2) ? 2 : 1) && rounds < cap) {
-                HIP_OK(c, enqueue(launched & 1));
-                rounds += c->graph_rounds;
-                ++launched;
-            }
-            if (launched == waited) break;                     // round cap reached
-            HIP_OK(c, hipEventSynchronize(c->ev_done[waited & 1]));
-            seen = h_done[waited & 1];
-            ++waited;
-            if (seen >= B) break;
-        }
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        h_done[0] = seen;
-    }
-    const bool finished = *h_done >= B;
+    for (int k = 0; k < 4; ++k) c->async_stats[k] = stats[k];               // mvfit_fit_stats: the whole fit
+    // ---- results, then the verdict ----
     hipLaunchKernelGGL(fit_finish_kernel, dim3(B), dim3(128), 0, c->stream, c->F, params, final_loss, n_closure, n_iter, B,
                        o->num_stages);
     HIP_OK(c, hipGetLastError());
-    if (!finished) return fail(c, MVFIT_E_STATE, "fit hit the round cap (%d) before all problems finished", cap);
+    // a gate that timed out lets the term's kernels run on another round's operands, a problem whose answer never came ends
+    // with a NaN loss: neither is a result
+    if (sv_lost || sv_gave_up)
+        return fail(c, MVFIT_E_STATE, "SDF service rounds degraded (%u operand sets lost, %u waits given up): the fit is not valid - "
+                    "is the GPU shared?  (mvfit_options::sdf_service = 0 runs these stages as chained rounds)", sv_lost, sv_gave_up);
+    if (capped)
+        return fail(c, MVFIT_E_STATE, "fit hit the round cap (%d) before all problems finished%s", cap,
+                    capped->pause_stage <= MVFIT_MAX_STAGES ? " the stages without the SDF term" : "");
     return MVFIT_OK;
 }
 
@@ -2385,7 +2307,7 @@ extern "C" int mvfit_pass_profile(mvfit_ctx* c, int* tiles_per_wg, int* workgrou
                                   double* slowest_ms) {
     if (!c) return MVFIT_E_ARG;
     if (tiles_per_wg) *tiles_per_wg = c->resident_tpw;
-    if (workgroups) *workgroups = resident_grid(c, c->resident_tpw);
+    if (workgroups) *workgroups = plan_resident_grid(c->resident_tpw, c->M.ntiles);
     if (rounds) *rounds = c->res_rounds;
     if (span_ms) *span_ms = c->res_span_ms;
     if (busy_ms) *busy_ms = c->res_busy_ms;
@@ -2411,11 +2333,8 @@ extern "C" int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs,
                                double* x_inout, double* trace, int max_trace, int* n_closure, double* final_loss) {
     if (!o || !x_inout || D <= 1 || D > LB_D || nseg < 1 || nseg > 8 || !segs) return MVFIT_E_ARG;
     if (hipSetDevice(device) != hipSuccess) return MVFIT_E_HIP;
-    LbOpts O;
-    memset(&O, 0, sizeof(O));
-    O.lr = o->lr; O.tol_grad = o->tolerance_grad; O.tol_change = o->tolerance_change; O.ftol = o->ftol; O.gtol = o->gtol;
-    O.max_iter = o->max_iter; O.max_eval = o->max_iter * 5 / 4; O.history = o->history; O.maxiters = o->maxiters;
-    O.num_stages = 1; O.nseg = nseg;
+    LbOpts O = lb_opts(*o, 1);
+    O.nseg = nseg;
     for (int i = 0; i < nseg; ++i) { O.seg_lo[i] = segs[i]; O.seg_hi[i] = segs[i + 1]; }
     double *dx, *dtrace, *dfl, *ddirs, *dstps, *dro, *dgrow, *dgcol, *dcmat;
     int* dn;

@@ -1084,7 +1084,7 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, Ks...>, F&
 //     `round - nslots` (a few times per fit) - no atomics, no contention.
 // Per closure round the pass now moves 84,712 bytes per problem + the operands; the basis crosses the memory system once
 // per fit.  Grid = ceil(ntiles / TPW) workgroups that must all be resident next to the optimiser's (one CU each): the host
-// picks TPW from the CU count (mvfit_api.hip: fit_async).  Vertices bit-identical to the per-round kernels
+// picks TPW from the CU count (fit_plan.cpp: resident_form).  Vertices bit-identical to the per-round kernels
 // (tests/test_gpu_async.py).  mvfit_profile: every workgroup logs {operands seen, stores drained} per round (wall clock).
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void wg_barrier_lds() {           // workgroup barrier that orders LDS traffic only (see above)

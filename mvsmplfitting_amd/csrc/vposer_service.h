@@ -35,9 +35,7 @@
 
 namespace mvfit {
 
-// VPS_SLICES (helpers per set = slices of the 512 fc2 units): model_layout.h
-constexpr int VPS_PMAX = 24;            // problems per set (wave w polls the slots w, w + 8, w + 16)
-constexpr int VPS_MAX_SETS = 16;          // 16 for launches of <= 32 problems, else 8
+// VPS_SLICES (helpers per set = slices of the 512 fc2 units), VPS_PMAX (problems per set), VPS_MAX_SETS: model_layout.h
 constexpr int VPS_GRAN = 144;           // granules per request / per answer (138 used)
 constexpr unsigned VPS_FWD = 1u, VPS_BWD = 2u, VPS_BYE = 3u;
 

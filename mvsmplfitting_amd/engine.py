@@ -146,7 +146,8 @@ class MvFit:
 
     def set_options(self, **values):
         """Change run-time selectors between calls (round_mode, resident_pass, sdf_two_phase, sdf_face_lists, vposer_helpers,
-        vposer_sets, closure_vposer_helpers, pass_kernel, sdf_service); returns the previous values of the ones changed."""
+        vposer_sets, closure_vposer_helpers, pass_kernel, sdf_service, work_queue); returns the previous values of the ones
+        changed."""
         cur = _lib.Options()
         self._check(self._lib.mvfit_get_options(self._ctx, C.byref(cur)))
         old = {k: int(getattr(cur, k)) for k in values}
