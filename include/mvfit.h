@@ -57,6 +57,7 @@ extern "C" {
 #define MVFIT_E_HIP (-2)
 #define MVFIT_E_STATE (-3)
 #define MVFIT_E_UNSUPPORTED (-4)
+#define MVFIT_SCENE_BODIES_MAX 256   /* bodies per scene (mvfit_render_scene images, mvfit_scene_sdf_loss scenes) */
 
 /* flags (mvfit_weights.flags) */
 #define MVFIT_F_VPOSER 1u      /* use_vposer: code/utils/fitting.py:166-168,327-329 */
@@ -336,6 +337,27 @@ int mvfit_set_sdf(mvfit_ctx* ctx, const int32_t* faces, int num_faces, int grid_
  *   samples[B,num_verts,4] dev out = (phi_v, d phi_v / d local x, y, z) per vertex (may be NULL),
  *   sums[B] dev out = S = sum_v phi_v (may be NULL). */
 int mvfit_sdf_term_read(mvfit_ctx* ctx, float* samples, float* sums);
+
+/* Scene collision loss: SDFLoss.forward (reference sdf/sdf/sdf_loss.py:51-99) for num_scenes scenes in one call.
+ *   vertices[N,num_vertices,3] dev: translation already added; bodies scene_first[s] .. scene_first[s+1]-1 form scene s
+ *   faces[num_faces,3] int32 dev, shared by all bodies; scene_first[num_scenes+1] host, scene_first[0]=0, non-decreasing,
+ *   1 .. MVFIT_SCENE_BODIES_MAX bodies per scene; 2 <= grid_size <= 128; robustifier <= 0: none.
+ *   loss[num_scenes] dev out; g_vertices[N,num_vertices,3] dev out or NULL = d loss[s] / d vertices (cotangent 1 per scene);
+ *   phi_out[N,G,G,G] dev out or NULL (diagnostics: the fields the samples were taken from).
+ * Per scene of P bodies: box of body i = (centre c_i, scale s_i = float32((1 + scale_factor) / 2) * largest extent), no
+ * gradient; phi_i = the voxel function of the SDF op above on (v_i - c_i) / s_i over ALL num_faces faces; for i != j and
+ * every vertex v of body j, p = grid_sample(phi_i, (v - c_i) / s_i) (trilinear, zeros padding, align_corners = False),
+ * with a robustifier r: p <- (p/r)^2 / ((p/r)^2 + 1); loss = sum p / P^2.  A scene of one body gives 0.
+ * The reference's isolation filter is reproduced as it EXECUTES: its mask is the bitwise complement of a uint8 tensor,
+ * never zero, so every body is kept and the divisor is P^2 even when a body is far from the others.
+ * Deterministic: fixed-order sums, no atomics; a scene's loss and gradient do not depend on the other scenes of the call.
+ * Needs no set_problems call.  The face indices are checked on the host in every call (one stream synchronisation);
+ * the op's path (face lists from 512 faces on) is reported by the info call of the SDF op.
+ * MVFIT_E_ARG: a null vertices / faces / scene_first / loss, scene_first[0] != 0 or decreasing, an empty scene, a scene
+ * of more than MVFIT_SCENE_BODIES_MAX bodies, grid_size out of range, a face index outside [0, num_vertices). */
+int mvfit_scene_sdf_loss(mvfit_ctx* ctx, const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
+                         const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor, float robustifier,
+                         float* loss, float* g_vertices, float* phi_out);
 
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear
  * triangulation of the 17 keypoints from V calibrated views, batched over B frames.

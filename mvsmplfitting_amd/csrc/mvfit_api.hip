@@ -70,6 +70,12 @@ hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int*
                                int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,
                                hipStream_t stream);
 size_t scene_ws_bytes(int n, int m, int Nv, int Nf, int H, int W);
+int scene_sdf_blocks(int nv);
+hipError_t launch_scene_boxes(const float* verts, int nv, int b0, int n, float factor, float4* box, float* local,
+                              hipStream_t stream);
+hipError_t launch_scene_pairs(const float* verts, int nv, int b0, int n, int s0, int ns, const void* tab, const int32_t* first,
+                              const float4* box, const float* phi, int G, float rob, float* g_verts, float* part, float* loss,
+                              hipStream_t stream);
 hipError_t launch_scene_group(const DevProblems& Q, const int32_t* tab, int num_images, int i0, int n, int j0, int m,
                               const float* verts, const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points,
                               int num_points, int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, int32_t* body_id,
@@ -790,6 +796,12 @@ struct mvfit_ctx {
     size_t vjp_part_size = 0;
     SdfAdj* d_vjp_rec = nullptr;
     int vjp_rec_n = 0;
+    // mvfit_scene_sdf_loss (scene_sdf.hip): tables, boxes, local vertices, fields, face lists and partials of one group of
+    // scenes in one allocation that grows to the largest call seen; the pinned staging of the call's tables
+    void* d_scn_ws = nullptr;
+    size_t scn_ws_size = 0;
+    int32_t* h_scn_tab = nullptr;
+    size_t h_scn_tab_bytes = 0;
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -1055,6 +1067,8 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     }
     if (c->d_vjp_part) hipFree(c->d_vjp_part);
     if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
+    if (c->d_scn_ws) hipFree(c->d_scn_ws);
+    if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
     for (void* p : c->allocs) if (p) hipFree(p);
     if (c->h_done) hipHostFree(c->h_done);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
@@ -2012,6 +2026,122 @@ extern "C" int mvfit_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, cons
     }
     hipError_t e = launch_sdf_voxelize(faces, num_faces, vertices, B, num_vertices, G, phi, c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "sdf launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+// SDFLoss.forward for num_scenes scenes (scene_sdf.hip).  Groups of consecutive whole scenes whose fields and local vertices
+// stay under the 256 MB cap the renderer uses (one scene's, when that alone needs more); inside a group the bodies are
+// voxelised in runs whose face lists stay under 2 GB.
+extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
+                                    const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor,
+                                    float robustifier, float* loss, float* g_vertices, float* phi_out) {
+    if (!c) return MVFIT_E_ARG;
+    if (!vertices || !faces || !scene_first || !loss)
+        return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: null %s", !vertices ? "vertices" : !faces ? "faces" : !scene_first ? "scene_first" : "loss");
+    if (num_vertices <= 0 || num_faces <= 0 || num_scenes <= 0)
+        return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: bad argument (num_vertices=%d num_faces=%d num_scenes=%d)", num_vertices,
+                    num_faces, num_scenes);
+    if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: grid_size %d outside [2, 128]", grid_size);
+    if (scene_first[0] != 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene_first[0] = %d, not 0", scene_first[0]);
+    for (int s = 0; s < num_scenes; ++s) {
+        const long long cnt = (long long)scene_first[s + 1] - scene_first[s];
+        if (cnt < 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene_first decreases at scene %d", s);
+        if (cnt == 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene %d is empty", s);
+        if (cnt > MVFIT_SCENE_BODIES_MAX)
+            return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene %d has %lld bodies (at most %d)", s, cnt, MVFIT_SCENE_BODIES_MAX);
+    }
+    const int N = scene_first[num_scenes];
+    HIP_OK(c, hipSetDevice(c->device));
+    // the voxelisation reads vertices through the face indices: checked on the host, as mvfit_set_sdf does (this also
+    // orders the call behind the earlier ones: the staging below is free again)
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    {
+        std::vector<int32_t> h((size_t)num_faces * 3);
+        HIP_OK(c, hipMemcpy(h.data(), faces, h.size() * 4, hipMemcpyDefault));
+        for (int32_t vi : h)
+            if (vi < 0 || vi >= num_vertices)
+                return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: face vertex index %d outside [0, %d)", (int)vi, num_vertices);
+    }
+    const int G = grid_size, nblk = scene_sdf_blocks(num_vertices);
+    const size_t nvox = (size_t)G * G * G, cap = (size_t)256 << 20;
+    const bool lists = sdf_op_uses_lists(num_faces) && c->opt.sdf_face_lists;
+    const size_t per_body = (phi_out ? 0 : nvox * 4) + (size_t)num_vertices * 12;
+    std::vector<int> group_end;                  // scene index one past each group
+    int nb_max = 0;
+    for (int s0 = 0; s0 < num_scenes;) {
+        int s1 = s0 + 1;
+        while (s1 < num_scenes && (size_t)(scene_first[s1 + 1] - scene_first[s0]) * per_body <= cap &&
+               scene_first[s1 + 1] - scene_first[s0] <= 4096)
+            ++s1;
+        group_end.push_back(s1);
+        nb_max = std::max(nb_max, scene_first[s1] - scene_first[s0]);
+        s0 = s1;
+    }
+    // bodies voxelised per run of the face-list kernels: as many as the group has while the lists stay under 2 GB (11.6 MB per
+    // body at 13,776 faces; one run of 128 bodies takes half the time of six runs of 22 - every run ends in a tail of few busy
+    // workgroups) and, when the workspace has to grow, under half of the free memory, as mvfit_sdf decides it
+    int run = lists ? (int)std::min<size_t>((size_t)nb_max, std::max<size_t>(1, ((size_t)2 << 30) / sdf_op_ws_bytes(1, num_faces))) : 0;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_tab = 0, o_first = o_tab + al((size_t)N * 16), o_box = o_first + al((size_t)(num_scenes + 1) * 4);
+    const size_t o_part = o_box + al((size_t)N * 16), o_local = o_part + al((size_t)nb_max * nblk * 4);
+    const size_t o_phi = o_local + al((size_t)nb_max * num_vertices * 12), o_cull = o_phi + (phi_out ? 0 : al((size_t)nb_max * nvox * 4));
+    size_t need = o_cull + (lists ? sdf_op_ws_bytes(run, num_faces) : 0);
+    if (need > c->scn_ws_size) {
+        if (c->d_scn_ws) hipFree(c->d_scn_ws);
+        c->d_scn_ws = nullptr; c->scn_ws_size = 0;
+        size_t free_b = 0, total_b = 0;
+        HIP_OK(c, hipMemGetInfo(&free_b, &total_b));
+        while (run > 1 && need > free_b / 2) {
+            run = (run + 1) / 2;
+            need = o_cull + sdf_op_ws_bytes(run, num_faces);
+        }
+        HIP_OK(c, hipMalloc(&c->d_scn_ws, need));
+        c->scn_ws_size = need;
+    }
+    const size_t tb = o_box;                     // tables: a row per body, then scene_first
+    if (tb > c->h_scn_tab_bytes) {
+        if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
+        c->h_scn_tab = nullptr; c->h_scn_tab_bytes = 0;
+        HIP_OK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_scn_tab), tb));
+        c->h_scn_tab_bytes = tb;
+    }
+    for (int s = 0; s < num_scenes; ++s)
+        for (int b = scene_first[s]; b < scene_first[s + 1]; ++b) {
+            int32_t* r = c->h_scn_tab + (size_t)b * 4;
+            r[0] = scene_first[s]; r[1] = scene_first[s + 1] - scene_first[s]; r[2] = 0; r[3] = 0;
+        }
+    memcpy(reinterpret_cast<unsigned char*>(c->h_scn_tab) + o_first, scene_first, (size_t)(num_scenes + 1) * 4);
+    unsigned char* ws = reinterpret_cast<unsigned char*>(c->d_scn_ws);
+    HIP_OK(c, hipMemcpyAsync(ws, c->h_scn_tab, tb, hipMemcpyHostToDevice, c->stream));
+    float4* box = reinterpret_cast<float4*>(ws + o_box);
+    float* part = reinterpret_cast<float*>(ws + o_part);
+    float* local = reinterpret_cast<float*>(ws + o_local);
+    const float factor = (float)((1.0 + (double)scale_factor) * 0.5);
+    c->sdf_op_path = lists ? 1 : 0;
+    int s0 = 0;
+    for (int s1 : group_end) {
+        const int b0 = scene_first[s0], n = scene_first[s1] - b0;
+        float* phi = phi_out ? phi_out + (size_t)b0 * nvox : reinterpret_cast<float*>(ws + o_phi);
+        hipError_t e = launch_scene_boxes(vertices, num_vertices, b0, n, factor, box, local, c->stream);
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: box launch: %s", hipGetErrorString(e));
+        if (lists) {
+            for (int r0 = 0; r0 < n; r0 += run) {
+                const int rn = std::min(run, n - r0);
+                // the lists' count area must be zero where this run's layout puts it
+                HIP_OK(c, hipMemsetAsync(ws + o_cull + sdf_cull_zero_offset(rn, num_faces), 0, sdf_cull_zero_bytes(rn), c->stream));
+                e = launch_sdf_voxelize_culled(faces, num_faces, local + (size_t)r0 * num_vertices * 3, rn, num_vertices, G,
+                                               phi + (size_t)r0 * nvox, ws + o_cull, c->stream);
+                if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: sdf launch: %s", hipGetErrorString(e));
+            }
+        } else {
+            e = launch_sdf_voxelize(faces, num_faces, local, n, num_vertices, G, phi, c->stream);
+            if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: sdf launch: %s", hipGetErrorString(e));
+        }
+        e = launch_scene_pairs(vertices, num_vertices, b0, n, s0, s1 - s0, ws + o_tab, reinterpret_cast<const int32_t*>(ws + o_first),
+                               box, phi, G, robustifier, g_vertices, part, loss, c->stream);
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: pair launch: %s", hipGetErrorString(e));
+        s0 = s1;
+    }
     return MVFIT_OK;
 }
 

@@ -359,6 +359,34 @@ class MvFit:
             warnings.warn(_SDF_WALK_WARNING % 'this mvfit_sdf call', RuntimeWarning)
         return phi
 
+    def scene_sdf_loss(self, vertices, faces, scene_sizes=None, grid_size=32, scale_factor=0.2, robustifier=None,
+                       need_grad=True, return_phi=False):
+        """The scene collision loss between bodies (include/mvfit.h:mvfit_scene_sdf_loss; the reference's SDFLoss.forward).
+        vertices[N,Nv,3] with the translation added; faces[F,3]; scene_sizes: bodies per scene, in order (None: all N bodies
+        are one scene).  Returns (loss[S], g_vertices[N,Nv,3] or None, phi[N,G,G,G] or None): g_vertices is
+        d loss[scene of the body] / d vertices."""
+        f = faces if isinstance(faces, torch.Tensor) else torch.as_tensor(np.asarray(faces).astype(np.int64))
+        f = f.to(device=self.device, dtype=torch.int32).contiguous()
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[2] != 3:
+            raise MvFitError('vertices must be [N, Nv, 3]')
+        if f.dim() != 2 or f.shape[1] != 3:
+            raise MvFitError('faces must be [F, 3]')
+        N = int(v.shape[0])
+        sizes = [N] if scene_sizes is None else [int(n) for n in scene_sizes]
+        if sum(sizes) != N:
+            raise MvFitError('scene_sizes %r do not add up to the %d bodies' % (sizes, N))
+        first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        G = int(grid_size)
+        loss = torch.zeros(len(sizes), device=self.device)
+        g = torch.zeros_like(v) if need_grad else None
+        phi = torch.zeros(N, G, G, G, device=self.device) if return_phi else None
+        self._check(self._lib.mvfit_scene_sdf_loss(
+            self._ctx, v.data_ptr(), int(v.shape[1]), f.data_ptr(), int(f.shape[0]), first.ctypes.data_as(_lib._ip), len(sizes), G,
+            float(scale_factor), float(robustifier) if robustifier else 0.0, loss.data_ptr(),
+            g.data_ptr() if need_grad else None, phi.data_ptr() if return_phi else None))
+        return loss, g, phi
+
     def set_sdf(self, faces, num_faces=1, grid_size=128):
         """Configure the interpenetration term (include/mvfit.h:mvfit_set_sdf).  ``faces`` [F,3]; ``num_faces``
         = how many leading triangles the op sees: 1 reproduces the reference's call site
