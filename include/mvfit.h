@@ -359,6 +359,32 @@ int mvfit_scene_sdf_loss(mvfit_ctx* ctx, const float* vertices, int num_vertices
                          const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor, float robustifier,
                          float* loss, float* g_vertices, float* phi_out);
 
+/* The collision term of a fit against the other bodies of a scene, with their fields FROZEN: the B problems of the ctx are
+ * partitioned into num_scenes scenes, contiguous in problem order (scene_first as above, and scene_first[num_scenes] = B).
+ *   vertices[B,num_verts,3] dev, world: where the obstacles are frozen.  For every body i the call stores its box
+ *   (c_i, s_i) and its field phi_i exactly as mvfit_scene_sdf_loss computes them over the model's own faces (the same
+ *   kernels: bit-identical to that op's phi_out).  vertices = NULL removes the obstacles.
+ * While they are set, a weight set with coll_loss_weight > 0 adds to problem j
+ *   pen_j = (coll_loss_weight * S_j)^2,  S_j = sum_{i != j in j's scene} sum_{v of j} rho(grid_sample(phi_i, (v - c_i) / s_i))
+ * (sampling and robustifier rho as in mvfit_scene_sdf_loss; no 1/P^2 - the weight absorbs it).  The fields and boxes carry no
+ * gradient, as in the reference's SDFLoss: the gradient flows through the sampled positions of body j only.  At the freeze
+ * point sum_j S_j / P^2 is the scene's loss of mvfit_scene_sdf_loss and d S_j / d v_j is P^2 times its g_vertices[j].  A
+ * scene of one body, or a body out of reach of every field, pays nothing.  A problem's numbers do not depend on B, on its
+ * position in the batch or on the other scenes.
+ * mvfit_fit runs the stages that carry this term as chained rounds (pass -> scene entries -> pull-back -> step kernel);
+ * stages without it in front keep their single-launch phase.  mvfit_sdf_term_read returns S_j in sums; samples:
+ * MVFIT_E_UNSUPPORTED.  Call again to re-freeze: for an unchanged (B, grid_size) the buffers keep their addresses and the
+ * captured round graph stays valid.  mvfit_set_problems with another B removes the obstacles.
+ * One interpenetration term per ctx: MVFIT_E_STATE while mvfit_set_sdf's term is configured (and mvfit_set_sdf returns it
+ * while obstacles are set).  MVFIT_E_STATE also without mvfit_set_problems or for a model without faces; MVFIT_E_ARG for a
+ * scene_first that mvfit_scene_sdf_loss would refuse or that does not end at B, or a grid_size outside [2, 128]. */
+int mvfit_set_scene_obstacles(mvfit_ctx* ctx, const float* vertices, const int32_t* scene_first, int num_scenes,
+                              int grid_size, float scale_factor, float robustifier);
+
+/* Diagnostics: the frozen obstacles.  phi[B,G,G,G] dev out (may be NULL), boxes[B,4] dev out = (c_i, s_i) (may be NULL).
+ * MVFIT_E_STATE when no obstacles are set. */
+int mvfit_scene_obstacles_read(mvfit_ctx* ctx, float* phi, float* boxes);
+
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear
  * triangulation of the 17 keypoints from V calibrated views, batched over B frames.
  *   keypoints[B,V,17,3] float32 dev (u, v, confidence) ; intris[V,3,3], extris[V,4,4] float64 dev (the reference

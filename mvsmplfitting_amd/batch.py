@@ -37,6 +37,7 @@ from . import _lib
 from . import io_formats as iof
 from .engine import MvFit, SCENE_PALETTE, stage_weights
 from .init_guess import init_guess_batch, initial_params
+from .scene_fit import refine_scenes
 from .sequence import fit_sequences
 
 
@@ -210,7 +211,7 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scen
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
-               save_images=False, image_root=None, image_folder=None, persons=0):
+               save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -230,7 +231,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     ``persons`` (the sorted ids fitted).  With is_seq the persons are the sequences of fit_sequences: a person's chain
     skips the frames they are absent from and starts cold at their first one.  save_images draws all fitted persons of a
     frame into every view that had a keypoint file, depth-tested, person p in palette colour p mod 7.  fix_scale /
-    fix_shape: one value for everybody or a dict {id: value} holding every requested id."""
+    fix_shape: one value for everybody or a dict {id: value} holding every requested id.
+    scene_collision: None, or dict(weight=..., sweeps=3, grid_size=32, robustifier=0.05, scale_factor=0.2) - after the
+    batched fit the persons of every frame are refined together (scene_fit.refine_scenes: a frame is a scene) with the last
+    stage's weights plus coll_loss_weight = weight, and the refined parameters are what is written; ``final_loss`` is then
+    the refined objective, collision term included, the serial's result gains ``scene_report`` and ``timing`` a 'refine'
+    entry.  It needs the multi-person path without is_seq (ValueError for persons=0, is_seq=True or a dict without
+    ``weight``).  Problems fitted in two groups (with and without 3-D targets) are refined with the 2-D objective only."""
     import time as _time
 
     def _tick(key, t0):
@@ -251,6 +258,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         if isinstance(persons, (str, bool)):
             raise ValueError("persons: an id, a list of ids or 'all', not %r" % (persons,))
         want = sorted({int(p) for p in (persons if isinstance(persons, (list, tuple, set, np.ndarray)) else [persons])})
+    if scene_collision is not None:
+        if not multi:
+            raise ValueError('scene_collision refines the persons of a frame together: it needs persons= a list of ids or \'all\'')
+        if is_seq:
+            raise ValueError('scene_collision is not available with is_seq=True')
+        if not isinstance(scene_collision, dict) or 'weight' not in scene_collision:
+            raise ValueError("scene_collision: a dict with at least 'weight' (the collision term's coll_loss_weight)")
+        unknown = set(scene_collision) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
+        if unknown:
+            raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
     for name, val in (('fix_scale', fix_scale), ('fix_shape', fix_shape)):
         if isinstance(val, dict) and want is not None and not set(want) <= set(val):
             raise ValueError('%s holds no value for persons %s' % (name, sorted(set(want) - set(val))))
@@ -406,6 +423,17 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 eng.set_problems(rig, gt_xy, conf)
             restarted = np.ones(N, bool)
         _t = _tick('fit', _t)
+        scene_report = None
+        if scene_collision is not None:
+            # a frame is a scene (the problems are frame-major); all N problems are set again, with their 3-D targets only
+            # when every problem carries them (they were then fitted as one group and the targets are still in place)
+            sc = dict(scene_collision)
+            st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(sc.pop('weight')))
+            sizes = [int((pf == f).sum()) for f in sorted(set(pf.tolist()))]
+            xr, scene_report = refine_scenes(eng, xf, sizes, st_, **sc)
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(scene_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('refine', _t)
         full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
         xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
         res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
@@ -424,6 +452,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         out = dict(frames=[fr[0] for fr in frames], params=xf_h, final_loss=final_h, n_closure=ncl.cpu().numpy(), files=files,
                    init=x0.cpu().numpy(), restarted=restarted, used_3d=has.copy(), views_per_frame=vmask.sum(1),
                    problem_frame=pf, problem_person=pp, persons=sorted(set(pp.tolist())))
+        if scene_report is not None:
+            out['scene_report'] = scene_report
         _t = _tick('write', _t)
         if save_images:
             palette = np.asarray(SCENE_PALETTE, np.float32)

@@ -76,6 +76,10 @@ hipError_t launch_scene_boxes(const float* verts, int nv, int b0, int n, float f
 hipError_t launch_scene_pairs(const float* verts, int nv, int b0, int n, int s0, int ns, const void* tab, const int32_t* first,
                               const float4* box, const float* phi, int G, float rob, float* g_verts, float* part, float* loss,
                               hipStream_t stream);
+hipError_t launch_scene_null_boxes(SdfBox* box, int B, hipStream_t stream);
+hipError_t launch_scene_term(const DevModel& M, const DevPose& P, const float* verts, int B, const void* tab, const float4* box,
+                             const float* phi, int G, float rob, const int* gate, const SdfBox* null_box, void* entries,
+                             SdfAdj* adj, hipStream_t stream);
 hipError_t launch_scene_group(const DevProblems& Q, const int32_t* tab, int num_images, int i0, int n, int j0, int m,
                               const float* verts, const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points,
                               int num_points, int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, int32_t* body_id,
@@ -802,6 +806,14 @@ struct mvfit_ctx {
     size_t scn_ws_size = 0;
     int32_t* h_scn_tab = nullptr;
     size_t h_scn_tab_bytes = 0;
+    // frozen obstacles of the scene term (mvfit_set_scene_obstacles): per problem its scene's row, its box and its field.
+    // The buffers keep their addresses while (B, grid) stay the same, so a re-freeze leaves the captured round graph valid.
+    bool obst_on = false;
+    int obst_grid = 0;
+    float obst_rob = 0.f;
+    int32_t* d_obst_tab = nullptr;     // [B] SceneBody rows
+    float4* d_obst_box = nullptr;      // [B] (centre, scale)
+    float* d_obst_phi = nullptr;       // [B][G^3]
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -1026,6 +1038,14 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
     return MVFIT_OK;
 }
 
+// the scene term's obstacles go with the batch they were frozen for
+static void free_obstacles(mvfit_ctx* c) {
+    void* ps[] = {c->d_obst_tab, c->d_obst_box, c->d_obst_phi};
+    for (void* p : ps) if (p) hipFree(p);
+    c->d_obst_tab = nullptr; c->d_obst_box = nullptr; c->d_obst_phi = nullptr;
+    c->obst_on = false; c->obst_grid = 0; c->obst_rob = 0.f;
+}
+
 static void free_problem_buffers(mvfit_ctx* c) {
     drop_graph(c);
     void* ps[] = {c->d_camR, c->d_camt, c->d_camf, c->d_camc, c->d_gt, c->d_wc, c->P.coefH, c->P.coefT, c->P.Amat, c->P.tau,
@@ -1048,6 +1068,7 @@ static void free_problem_buffers(mvfit_ctx* c) {
     c->d_sdf_box = nullptr; c->d_sdf_samp = nullptr; c->d_sdf_entries = nullptr; c->d_sdf_adj = nullptr; c->d_sdf_cull = nullptr;
     c->d_sdf_boxpart = nullptr;
     c->sdf_cull_refused = false;
+    free_obstacles(c);
 }
 
 extern "C" void mvfit_destroy(mvfit_ctx* c) {
@@ -1161,6 +1182,8 @@ extern "C" int mvfit_set_joints3d(mvfit_ctx* c, const float* gt3d, const float* 
 
 extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, int grid_size) {
     if (!c) return MVFIT_E_ARG;
+    if (c->obst_on && faces && num_faces != 0)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: scene obstacles are the interpenetration term (one per ctx): remove them first");
     HIP_OK(c, hipSetDevice(c->device));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     drop_graph(c);
@@ -1188,6 +1211,8 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
 extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
     if (!c) return MVFIT_E_ARG;
     if (!c->d_sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
+    if (samples && c->obst_on)
+        return fail(c, MVFIT_E_UNSUPPORTED, "mvfit_sdf_term_read: the scene term keeps no per-vertex samples (sums only)");
     HIP_OK(c, hipSetDevice(c->device));
     if (samples) HIP_OK(c, hipMemcpyAsync(samples, c->d_sdf_samp, (size_t)c->B * c->nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     if (sums) HIP_OK(c, hipMemcpy2DAsync(sums, sizeof(float), c->d_sdf_adj, sizeof(SdfAdj), sizeof(float), c->B, hipMemcpyDeviceToDevice, c->stream));
@@ -1234,10 +1259,25 @@ static int ensure_sdf_buffers(mvfit_ctx* c) {
 // DevPose::box_part is set) when the split-fp16 basis exists and the launch is one 32-problem chunk per workgroup
 static bool pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
     const int chunks = (b_hi + 31) / 32 - b_lo / 32;
-    return c->M.bs_h2 != nullptr && c->d_sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
+    return !c->obst_on && c->M.bs_h2 != nullptr && c->d_sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
+}
+
+// the interpenetration term of a chained round behind its vertex pass: against the frozen obstacles when they are set,
+// else the one-person term of mvfit_set_sdf
+static hipError_t launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
+    if (c->obst_on)
+        return launch_scene_term(c->M, c->P, verts, c->B, c->d_obst_tab, c->d_obst_box, c->d_obst_phi, c->obst_grid, c->obst_rob, gate,
+                                 c->d_sdf_box, c->d_sdf_entries, c->d_sdf_adj, st);
+    return launch_sdf_term(c->M, c->P, verts, c->B, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, gate, c->d_sdf_box, c->d_sdf_samp,
+                           c->d_sdf_entries, c->d_sdf_adj, st, c->d_sdf_cull, nullptr, 0u, box_part);
 }
 
 static int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st) {
+    if (c->obst_on) {
+        const hipError_t e = launch_term(c, verts, gate, st, nullptr);
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "scene term launch: %s", hipGetErrorString(e));
+        return MVFIT_OK;
+    }
     hipError_t e = launch_sdf_term(c->M, c->P, verts, c->B, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, gate, c->d_sdf_box,
                                    c->d_sdf_samp, c->d_sdf_entries, c->d_sdf_adj, st, c->d_sdf_cull);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "sdf term launch: %s", hipGetErrorString(e));
@@ -1376,7 +1416,7 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
     int rc = check_flags(c, w->flags);
     if (rc) return rc;
     const bool sdf = w->coll_loss_weight > 0.f;
-    if (sdf && !c->sdf_num_faces)
+    if (sdf && !c->sdf_num_faces && !c->obst_on)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
     HIP_OK(c, hipSetDevice(c->device));
     if (c->opt.closure_vposer_helpers && (w->flags & MVFIT_F_VPOSER) && c->vps_mem && !sdf)
@@ -1443,14 +1483,18 @@ static int make_opts(mvfit_ctx* c, const mvfit_lbfgs_opts* o, uint32_t flags, Lb
 static const int kGraphRounds = 24;
 
 static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O) {
-    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int));
+    // (the scene term's obstacles: buffers and scalars baked into its kernel node; a re-freeze changes none of them)
+    struct { const void *tab, *box, *phi; int grid; float rob; } obst = {nullptr, nullptr, nullptr, 0, 0.f};
+    if (c->obst_on) { obst.tab = c->d_obst_tab; obst.box = c->d_obst_box; obst.phi = c->d_obst_phi; obst.grid = c->obst_grid; obst.rob = c->obst_rob; }
+    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
     memcpy(k, &O, sizeof(O)); k += sizeof(O);
     memcpy(k, &c->P, sizeof(DevPose)); k += sizeof(DevPose);
     memcpy(k, &c->F, sizeof(FitBuffers)); k += sizeof(FitBuffers);
     memcpy(k, &c->Q, sizeof(DevProblems)); k += sizeof(DevProblems);
-    memcpy(k, &c->opt.pass_kernel, sizeof(int));
+    memcpy(k, &c->opt.pass_kernel, sizeof(int)); k += sizeof(int);
+    memcpy(k, &obst, sizeof(obst));
     if (c->round_graph && key == c->graph_key) return MVFIT_OK;
     drop_graph(c);
     hipStream_t cs;
@@ -1465,8 +1509,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         for (int r = 0; r < kGraphRounds && e == hipSuccess; ++r) {
             e = launch_vertex_pass(c->M, Pg, c->B, c->d_verts, c->opt.pass_kernel, cs);
             if (e == hipSuccess && c->F.sdf_adj)
-                e = launch_sdf_term(c->M, c->P, c->d_verts, c->B, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, c->F.sdf_gate,
-                                    c->d_sdf_box, c->d_sdf_samp, c->d_sdf_entries, c->d_sdf_adj, cs, c->d_sdf_cull, nullptr, 0u, Pg.box_part);
+                e = launch_term(c, c->d_verts, c->F.sdf_gate, cs, Pg.box_part);
             hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), cs, c->M, (const ObsBlock*)c->d_obs, c->V, SW, O,
                                c->P, c->F);
         }
@@ -1871,8 +1914,9 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
         SW.w[s] = to_dev(sw[s]);
     }
     const bool any_sdf = in.sdf_stages != 0;
-    if (any_sdf && !c->sdf_num_faces)
+    if (any_sdf && !c->sdf_num_faces && !c->obst_on)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
+    if (c->obst_on) in.sdf_service = 0;          // the scene term runs in chained rounds only (no service path for it)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;
@@ -2032,35 +2076,44 @@ extern "C" int mvfit_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, cons
 // SDFLoss.forward for num_scenes scenes (scene_sdf.hip).  Groups of consecutive whole scenes whose fields and local vertices
 // stay under the 256 MB cap the renderer uses (one scene's, when that alone needs more); inside a group the bodies are
 // voxelised in runs whose face lists stay under 2 GB.
-extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
-                                    const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor,
-                                    float robustifier, float* loss, float* g_vertices, float* phi_out) {
-    if (!c) return MVFIT_E_ARG;
-    if (!vertices || !faces || !scene_first || !loss)
-        return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: null %s", !vertices ? "vertices" : !faces ? "faces" : !scene_first ? "scene_first" : "loss");
-    if (num_vertices <= 0 || num_faces <= 0 || num_scenes <= 0)
-        return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: bad argument (num_vertices=%d num_faces=%d num_scenes=%d)", num_vertices,
-                    num_faces, num_scenes);
-    if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: grid_size %d outside [2, 128]", grid_size);
-    if (scene_first[0] != 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene_first[0] = %d, not 0", scene_first[0]);
+// scene_first[num_scenes + 1]: starts at 0, 1 .. MVFIT_SCENE_BODIES_MAX bodies per scene
+static int check_scene_first(mvfit_ctx* c, const char* who, const int32_t* scene_first, int num_scenes) {
+    if (scene_first[0] != 0) return fail(c, MVFIT_E_ARG, "%s: scene_first[0] = %d, not 0", who, scene_first[0]);
     for (int s = 0; s < num_scenes; ++s) {
         const long long cnt = (long long)scene_first[s + 1] - scene_first[s];
-        if (cnt < 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene_first decreases at scene %d", s);
-        if (cnt == 0) return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene %d is empty", s);
+        if (cnt < 0) return fail(c, MVFIT_E_ARG, "%s: scene_first decreases at scene %d", who, s);
+        if (cnt == 0) return fail(c, MVFIT_E_ARG, "%s: scene %d is empty", who, s);
         if (cnt > MVFIT_SCENE_BODIES_MAX)
-            return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: scene %d has %lld bodies (at most %d)", s, cnt, MVFIT_SCENE_BODIES_MAX);
+            return fail(c, MVFIT_E_ARG, "%s: scene %d has %lld bodies (at most %d)", who, s, cnt, MVFIT_SCENE_BODIES_MAX);
     }
+    return MVFIT_OK;
+}
+
+// keep_box / keep_tab (both or neither; then phi_out is set too): the freeze of mvfit_set_scene_obstacles - boxes and table
+// rows go to the caller's buffers as well, the faces are the model's own (checked at mvfit_create) and the pair kernels do
+// not run (no loss).  Boxes and fields are what the loss call computes: the same kernels on the same inputs.
+static int scene_sdf_run(mvfit_ctx* c, const char* who, const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
+                         const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor, float robustifier,
+                         float* loss, float* g_vertices, float* phi_out, float4* keep_box, int32_t* keep_tab) {
+    const bool freeze = keep_box != nullptr;
+    if (!vertices || !faces || !scene_first || (!loss && !freeze))
+        return fail(c, MVFIT_E_ARG, "%s: null %s", who, !vertices ? "vertices" : !faces ? "faces" : !scene_first ? "scene_first" : "loss");
+    if (num_vertices <= 0 || num_faces <= 0 || num_scenes <= 0)
+        return fail(c, MVFIT_E_ARG, "%s: bad argument (num_vertices=%d num_faces=%d num_scenes=%d)", who, num_vertices,
+                    num_faces, num_scenes);
+    if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "%s: grid_size %d outside [2, 128]", who, grid_size);
+    if (const int rc = check_scene_first(c, who, scene_first, num_scenes)) return rc;
     const int N = scene_first[num_scenes];
     HIP_OK(c, hipSetDevice(c->device));
     // the voxelisation reads vertices through the face indices: checked on the host, as mvfit_set_sdf does (this also
     // orders the call behind the earlier ones: the staging below is free again)
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    {
+    if (!freeze) {
         std::vector<int32_t> h((size_t)num_faces * 3);
         HIP_OK(c, hipMemcpy(h.data(), faces, h.size() * 4, hipMemcpyDefault));
         for (int32_t vi : h)
             if (vi < 0 || vi >= num_vertices)
-                return fail(c, MVFIT_E_ARG, "mvfit_scene_sdf_loss: face vertex index %d outside [0, %d)", (int)vi, num_vertices);
+                return fail(c, MVFIT_E_ARG, "%s: face vertex index %d outside [0, %d)", who, (int)vi, num_vertices);
     }
     const int G = grid_size, nblk = scene_sdf_blocks(num_vertices);
     const size_t nvox = (size_t)G * G * G, cap = (size_t)256 << 20;
@@ -2113,7 +2166,8 @@ extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num
     memcpy(reinterpret_cast<unsigned char*>(c->h_scn_tab) + o_first, scene_first, (size_t)(num_scenes + 1) * 4);
     unsigned char* ws = reinterpret_cast<unsigned char*>(c->d_scn_ws);
     HIP_OK(c, hipMemcpyAsync(ws, c->h_scn_tab, tb, hipMemcpyHostToDevice, c->stream));
-    float4* box = reinterpret_cast<float4*>(ws + o_box);
+    if (freeze) HIP_OK(c, hipMemcpyAsync(keep_tab, c->h_scn_tab, (size_t)N * 16, hipMemcpyHostToDevice, c->stream));
+    float4* box = freeze ? keep_box : reinterpret_cast<float4*>(ws + o_box);
     float* part = reinterpret_cast<float*>(ws + o_part);
     float* local = reinterpret_cast<float*>(ws + o_local);
     const float factor = (float)((1.0 + (double)scale_factor) * 0.5);
@@ -2123,7 +2177,7 @@ extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num
         const int b0 = scene_first[s0], n = scene_first[s1] - b0;
         float* phi = phi_out ? phi_out + (size_t)b0 * nvox : reinterpret_cast<float*>(ws + o_phi);
         hipError_t e = launch_scene_boxes(vertices, num_vertices, b0, n, factor, box, local, c->stream);
-        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: box launch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s: box launch: %s", who, hipGetErrorString(e));
         if (lists) {
             for (int r0 = 0; r0 < n; r0 += run) {
                 const int rn = std::min(run, n - r0);
@@ -2131,17 +2185,78 @@ extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num
                 HIP_OK(c, hipMemsetAsync(ws + o_cull + sdf_cull_zero_offset(rn, num_faces), 0, sdf_cull_zero_bytes(rn), c->stream));
                 e = launch_sdf_voxelize_culled(faces, num_faces, local + (size_t)r0 * num_vertices * 3, rn, num_vertices, G,
                                                phi + (size_t)r0 * nvox, ws + o_cull, c->stream);
-                if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: sdf launch: %s", hipGetErrorString(e));
+                if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s: sdf launch: %s", who, hipGetErrorString(e));
             }
         } else {
             e = launch_sdf_voxelize(faces, num_faces, local, n, num_vertices, G, phi, c->stream);
-            if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: sdf launch: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s: sdf launch: %s", who, hipGetErrorString(e));
         }
+        if (freeze) { s0 = s1; continue; }
         e = launch_scene_pairs(vertices, num_vertices, b0, n, s0, s1 - s0, ws + o_tab, reinterpret_cast<const int32_t*>(ws + o_first),
                                box, phi, G, robustifier, g_vertices, part, loss, c->stream);
-        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_scene_sdf_loss: pair launch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s: pair launch: %s", who, hipGetErrorString(e));
         s0 = s1;
     }
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_scene_sdf_loss(mvfit_ctx* c, const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
+                                    const int32_t* scene_first, int num_scenes, int grid_size, float scale_factor,
+                                    float robustifier, float* loss, float* g_vertices, float* phi_out) {
+    if (!c) return MVFIT_E_ARG;
+    return scene_sdf_run(c, "mvfit_scene_sdf_loss", vertices, num_vertices, faces, num_faces, scene_first, num_scenes, grid_size,
+                         scale_factor, robustifier, loss, g_vertices, phi_out, nullptr, nullptr);
+}
+
+// Freeze the obstacles of the scene term at `vertices` (scene_sdf.hip: scene_entries_kernel reads them in every chained round).
+extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, const int32_t* scene_first, int num_scenes,
+                                         int grid_size, float scale_factor, float robustifier) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (!vertices) {                                         // remove: the buffers stay for the next freeze of this batch
+        c->obst_on = false;
+        return MVFIT_OK;
+    }
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the model was created without (valid) faces");
+    if (c->sdf_num_faces)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: mvfit_set_sdf's term is the interpenetration term (one per ctx): remove it first");
+    if (c->nv > 8192) return fail(c, MVFIT_E_UNSUPPORTED, "the scene term supports up to 8192 vertices (model has %d)", c->nv);
+    if (!scene_first || num_scenes <= 0) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: bad argument (num_scenes=%d)", num_scenes);
+    if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: grid_size %d outside [2, 128]", grid_size);
+    int rc = check_scene_first(c, "mvfit_set_scene_obstacles", scene_first, num_scenes);
+    if (rc) return rc;
+    if (scene_first[num_scenes] != c->B)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: the scenes hold %d bodies, the ctx %d problems", scene_first[num_scenes], c->B);
+    const size_t nvox = (size_t)grid_size * grid_size * grid_size;
+    if (c->obst_grid != grid_size || !c->d_obst_phi) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        free_obstacles(c);
+        HIP_OK(c, hipMalloc(&c->d_obst_tab, (size_t)c->B * 16));
+        HIP_OK(c, hipMalloc(&c->d_obst_box, (size_t)c->B * sizeof(float4)));
+        HIP_OK(c, hipMalloc(&c->d_obst_phi, (size_t)c->B * nvox * 4));
+        c->obst_grid = grid_size;
+    }
+    c->obst_on = false;                                      // a failed freeze leaves no term behind
+    rc = ensure_sdf_buffers(c);
+    if (rc) return rc;
+    hipError_t e = launch_scene_null_boxes(c->d_sdf_box, c->B, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_set_scene_obstacles: box launch: %s", hipGetErrorString(e));
+    rc = scene_sdf_run(c, "mvfit_set_scene_obstacles", vertices, c->nv, c->d_faces, c->num_faces, scene_first, num_scenes, grid_size,
+                       scale_factor, robustifier, nullptr, nullptr, c->d_obst_phi, c->d_obst_box, c->d_obst_tab);
+    if (rc) return rc;
+    c->obst_rob = robustifier;
+    c->obst_on = true;
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_scene_obstacles_read(mvfit_ctx* c, float* phi, float* boxes) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->obst_on) return fail(c, MVFIT_E_STATE, "mvfit_scene_obstacles_read: no obstacles are set");
+    HIP_OK(c, hipSetDevice(c->device));
+    const size_t nvox = (size_t)c->obst_grid * c->obst_grid * c->obst_grid;
+    if (phi) HIP_OK(c, hipMemcpyAsync(phi, c->d_obst_phi, (size_t)c->B * nvox * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (boxes) HIP_OK(c, hipMemcpyAsync(boxes, c->d_obst_box, (size_t)c->B * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 

@@ -23,6 +23,9 @@
 // workgroup in order, one partial per (body, workgroup), then one pass per scene over its partials in ascending order - no
 // float atomics, and nothing a scene computes depends on the other scenes of the call or on where it stands in it.
 #include "sdf_device.h"
+#include "mvfit_device.h"
+#include "wave_ops.h"
+#include "sdf_entries.h"
 
 namespace mvfit {
 
@@ -70,6 +73,57 @@ __global__ __launch_bounds__(SCN_NT) void scene_box_kernel(const float* __restri
     }
 }
 
+// One target vertex (p0, p1, p2) against the field f of a source body with box bx: the sampled value is added to acc and
+// its gradient with respect to the vertex to g.  Shared by scene_pair_kernel and scene_entries_kernel: the same
+// expressions in the same order (contraction is off in this file), hence the same bits in both.
+__device__ __forceinline__ void scene_sample_add(const float4 bx, const float* __restrict__ f, int G, float rob, float p0,
+                                                 float p1, float p2, float& acc, float (&g)[3]) {
+    const float fG = (float)G;
+    // grid_sample's source index, align_corners = False: ((x + 1) * G - 1) / 2
+    const float ix = (((p0 - bx.x) / bx.w + 1.f) * fG - 1.f) / 2.f;
+    const float iy = (((p1 - bx.y) / bx.w + 1.f) * fG - 1.f) / 2.f;
+    const float iz = (((p2 - bx.z) / bx.w + 1.f) * fG - 1.f) / 2.f;
+    // outside the field and its border band of zeros padding: value and gradient 0, no memory access (also a NaN)
+    if (!(ix > -1.f && ix < fG && iy > -1.f && iy < fG && iz > -1.f && iz < fG)) return;
+    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
+    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
+    const float tx = ix - fx, ty = iy - fy, tz = iz - fz;
+    float c[2][2][2];
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
+                const bool in = xx >= 0 && xx < G && yy >= 0 && yy < G && zz >= 0 && zz < G;
+                c[dz][dy][dx] = in ? f[((size_t)zz * G + yy) * G + xx] : 0.f;
+            }
+    const float wx[2] = {1.f - tx, tx}, wy[2] = {1.f - ty, ty}, wz[2] = {1.f - tz, tz};
+    float p = 0.f, dpx = 0.f, dpy = 0.f, dpz = 0.f;
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const float cv = c[dz][dy][dx];
+                p += cv * (wx[dx] * wy[dy] * wz[dz]);
+                dpx += cv * ((dx ? 1.f : -1.f) * wy[dy] * wz[dz]);
+                dpy += cv * ((dy ? 1.f : -1.f) * wx[dx] * wz[dz]);
+                dpz += cv * ((dz ? 1.f : -1.f) * wx[dx] * wy[dy]);
+            }
+    // d index / d vertex = G / 2 / s_i
+    float k = fG / 2.f / bx.w;
+    if (rob > 0.f) {
+        const float q = p / rob, fr = q * q, den = fr + 1.f;
+        k *= 2.f * q / rob / (den * den);
+        p = fr / den;
+    }
+    acc += p;
+    g[0] += dpx * k; g[1] += dpy * k; g[2] += dpz * k;
+}
+
 // grid (ceil(nv / SCN_NT), bodies of the group): thread = target vertex (j, v).  phi holds the fields of bodies b0 .. .
 // part[(j - b0) * gridDim.x + blockIdx.x] = the workgroup's sum of sampled values (before the division by P^2).
 __global__ __launch_bounds__(SCN_NT) void scene_pair_kernel(const float* __restrict__ verts, int nv, int b0,
@@ -85,54 +139,9 @@ __global__ __launch_bounds__(SCN_NT) void scene_pair_kernel(const float* __restr
         const float* pv = verts + ((size_t)j * nv + v) * 3;
         const float p0 = pv[0], p1 = pv[1], p2 = pv[2];
         const size_t nvox = (size_t)G * G * G;
-        const float fG = (float)G;
         for (int i = sb.first; i < sb.first + sb.count; ++i) {
             if (i == j) continue;
-            const float4 bx = box[i];
-            // grid_sample's source index, align_corners = False: ((x + 1) * G - 1) / 2
-            const float ix = (((p0 - bx.x) / bx.w + 1.f) * fG - 1.f) / 2.f;
-            const float iy = (((p1 - bx.y) / bx.w + 1.f) * fG - 1.f) / 2.f;
-            const float iz = (((p2 - bx.z) / bx.w + 1.f) * fG - 1.f) / 2.f;
-            // outside the field and its border band of zeros padding: value and gradient 0, no memory access (also a NaN)
-            if (!(ix > -1.f && ix < fG && iy > -1.f && iy < fG && iz > -1.f && iz < fG)) continue;
-            const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-            const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-            const float tx = ix - fx, ty = iy - fy, tz = iz - fz;
-            const float* f = phi + (size_t)(i - b0) * nvox;
-            float c[2][2][2];
-#pragma unroll
-            for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-                for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx) {
-                        const int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
-                        const bool in = xx >= 0 && xx < G && yy >= 0 && yy < G && zz >= 0 && zz < G;
-                        c[dz][dy][dx] = in ? f[((size_t)zz * G + yy) * G + xx] : 0.f;
-                    }
-            const float wx[2] = {1.f - tx, tx}, wy[2] = {1.f - ty, ty}, wz[2] = {1.f - tz, tz};
-            float p = 0.f, dpx = 0.f, dpy = 0.f, dpz = 0.f;
-#pragma unroll
-            for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-                for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx) {
-                        const float cv = c[dz][dy][dx];
-                        p += cv * (wx[dx] * wy[dy] * wz[dz]);
-                        dpx += cv * ((dx ? 1.f : -1.f) * wy[dy] * wz[dz]);
-                        dpy += cv * ((dy ? 1.f : -1.f) * wx[dx] * wz[dz]);
-                        dpz += cv * ((dz ? 1.f : -1.f) * wx[dx] * wy[dy]);
-                    }
-            // d index / d vertex = G / 2 / s_i
-            float k = fG / 2.f / bx.w;
-            if (rob > 0.f) {
-                const float q = p / rob, fr = q * q, den = fr + 1.f;
-                k *= 2.f * q / rob / (den * den);
-                p = fr / den;
-            }
-            acc += p;
-            g[0] += dpx * k; g[1] += dpy * k; g[2] += dpz * k;
+            scene_sample_add(box[i], phi + (size_t)(i - b0) * nvox, G, rob, p0, p1, p2, acc, g);
         }
         if (g_verts) {
             const float pp = (float)(sb.count * sb.count);
@@ -147,6 +156,61 @@ __global__ __launch_bounds__(SCN_NT) void scene_pair_kernel(const float* __restr
         float s = sh[0];
         for (int w = 1; w < SCN_NT / 64; ++w) s += sh[w];
         part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// The collision term of a fit against FROZEN obstacles (mvfit_set_scene_obstacles): the scene counterpart of
+// sdf_entries_kernel<false>.  Grid (SDF_NC, B): a workgroup owns one vertex chunk of problem j, every wave an ascending
+// run of it, a thread one trial vertex of the vertex pass's output.  The thread walks the other bodies of j's scene in
+// ascending i against their frozen boxes and fields (scene_sample_add: the box test comes before any field access; most
+// vertices fail it for every source) and keeps value and gradient in registers.  The workgroup writes the chunk's
+// record - S in float64, wave tree then the waves in order; the frozen boxes carry no gradient, so the box-adjoint sums
+// are 0 - and its entries, the vertices with a non-zero gradient in ascending order at the chunk's own offset: what
+// sdf_pullback_kernel reads.  S_j = sum_{i != j} sum_v rho(sample(phi_i, v)) carries no 1 / P^2 (the stage weight absorbs
+// it).  No atomics, and nothing depends on B, on j's position in the call or on the other scenes.
+__global__ __launch_bounds__(SDF_ADJ_NT) void scene_entries_kernel(int nv, const float* __restrict__ verts,
+                                                                   const SceneBody* __restrict__ tab,
+                                                                   const float4* __restrict__ box, const float* __restrict__ phi,
+                                                                   int G, float rob, const int* __restrict__ gate,
+                                                                   SdfEntry* __restrict__ entries, SdfChunk* __restrict__ chunks) {
+    static_assert(SDF_NIT == 1, "one 64-vertex row per wave");
+    __shared__ double sh_d[SDF_ADJ_NT / 64];
+    __shared__ int sh_cnt[SDF_ADJ_NT / 64];
+    const int j = blockIdx.y, y = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (gate && !gate[j]) return;
+    const SceneBody sb = tab[j];
+    const int csz = (nv + SDF_NC - 1) / SDF_NC, k0 = y * csz, k1 = min(nv, k0 + csz);
+    const int wsz = (csz + 7) / 8, c0 = k0 + wave * wsz, c1 = min(k1, c0 + wsz);
+    const int v = c0 + lane;
+    const bool in = v < c1;
+    float acc = 0.f, g[3] = {0.f, 0.f, 0.f};
+    if (in) {
+        const float* pv = verts + ((size_t)j * nv + v) * 3;
+        const float p0 = pv[0], p1 = pv[1], p2 = pv[2];
+        const size_t nvox = (size_t)G * G * G;
+        for (int i = sb.first; i < sb.first + sb.count; ++i) {
+            if (i == j) continue;
+            scene_sample_add(box[i], phi + (size_t)i * nvox, G, rob, p0, p1, p2, acc, g);
+        }
+    }
+    const bool act = in && ((g[0] != 0.f) | (g[1] != 0.f) | (g[2] != 0.f));
+    const unsigned long long bal = __ballot(act);
+    const double S = wave64_sum((double)acc);
+    if (lane == 0) { sh_d[wave] = S; sh_cnt[wave] = __popcll(bal); }
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += sh_cnt[w];
+    if (act) {
+        SdfEntry* eb = entries + (size_t)j * nv + k0;
+        const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+        *reinterpret_cast<float4*>(&eb[pos]) = make_float4(__builtin_bit_cast(float, v), g[0], g[1], g[2]);
+    }
+    if (tid == 0) {
+        SdfChunk c;
+        c.S = 0.0; c.cnt = 0;
+        for (int w = 0; w < SDF_ADJ_NT / 64; ++w) { c.S += sh_d[w]; c.cnt += sh_cnt[w]; }
+        c.gc0 = 0.0; c.gc1 = 0.0; c.gc2 = 0.0; c.gs = 0.0; c.pad = 0;
+        chunks[(size_t)j * SDF_NC + y] = c;
     }
 }
 
@@ -181,6 +245,36 @@ hipError_t launch_scene_pairs(const float* verts, int nv, int b0, int n, int s0,
                        reinterpret_cast<const SceneBody*>(tab), box, phi, G, rob, g_verts, part);
     hipLaunchKernelGGL(scene_loss_kernel, dim3(ns), dim3(64), 0, stream, (const float*)part, nblk, first, s0, b0, loss);
     return hipGetLastError();
+}
+
+// one box per problem for the pull-back of the scene term: no vertex matches its box-adjoint branch
+__global__ void scene_null_box_kernel(SdfBox* __restrict__ box, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    SdfBox x;
+    for (int a = 0; a < 3; ++a) { x.c[a] = 0.f; x.imin[a] = -1; x.imax[a] = -1; }
+    x.s = 1.f; x.amax = 0; x.pad = 0;
+    box[b] = x;
+}
+
+hipError_t launch_scene_null_boxes(SdfBox* box, int B, hipStream_t stream) {
+    hipLaunchKernelGGL(scene_null_box_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, box, B);
+    return hipGetLastError();
+}
+
+// The scene term of one closure round for all B problems of the ctx: entries against the frozen obstacles (tab, box, phi:
+// [B] rows / [B] boxes / [B] fields by problem index), then the pull-back of sdf_term.hip into adj.  null_box: [B] boxes
+// of launch_scene_null_boxes; entries: the work area of sdf_work_bytes(B, nv) bytes.
+hipError_t launch_scene_term(const DevModel& M, const DevPose& P, const float* verts, int B, const void* tab, const float4* box,
+                             const float* phi, int G, float rob, const int* gate, const SdfBox* null_box, void* entries,
+                             SdfAdj* adj, hipStream_t stream) {
+    if (M.nv > SDF_NC * 8 * SDF_NIT * 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scene_entries_kernel, dim3(SDF_NC, B), dim3(SDF_ADJ_NT), 0, stream, M.nv, verts,
+                       reinterpret_cast<const SceneBody*>(tab), box, phi, G, rob, gate, reinterpret_cast<SdfEntry*>(entries),
+                       sdf_work_chunks(entries, B, M.nv));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_sdf_pullback(M, P, B, gate, null_box, entries, adj, stream);
 }
 
 }  // namespace mvfit

@@ -25,12 +25,12 @@
 #include "sdf_device.h"
 #include "mvfit_device.h"
 #include "wave_ops.h"
+#include "sdf_entries.h"
 
 namespace mvfit {
 
 #pragma clang fp contract(off)
 
-constexpr int SDF_ADJ_NT = 512;
 constexpr int SDF_EB = 256;          // entries staged per batch in phase 2
 
 // (ord_bits / ord_float / dpp_u64 / row16_key: wave_ops.h - shared with the vertex pass, which reduces its tile's keys itself)
@@ -729,16 +729,7 @@ hipError_t launch_sdf_voxelize_culled(const int32_t* faces, int num_faces, const
     return hipGetLastError();
 }
 
-// entry list of one problem: the vertices that carry gradient, in ascending vertex order
-struct SdfEntry { int v; float g[3]; };                                  // vertex, dS/dvertex
-static_assert(sizeof(SdfEntry) == 16, "entry layout");
-
-constexpr int SDF_NC = 16;           // vertex chunks per problem in the entry kernel (one workgroup each)
-constexpr int SDF_NIT = 1;           // 64-vertex rows per wave of a chunk: nv <= SDF_NC * 8 waves * SDF_NIT * 64 = 8192
-
-// per (problem, vertex chunk): partial sums of S and of the box adjoint, entries written (at the chunk's own offset)
-struct SdfChunk { double S, gc0, gc1, gc2, gs; int cnt, pad; };
-static_assert(sizeof(SdfChunk) == 48, "chunk record");
+// (SdfEntry, SdfChunk, SDF_NC, SDF_NIT: sdf_entries.h - the scene term of scene_sdf.hip writes the same records)
 #ifndef SDF_NS_
 #define SDF_NS_ 8                   // (-DSDF_NS_=1 reproduces the single-chain summation order bit for bit: the control experiment)
 #endif
@@ -1085,6 +1076,22 @@ hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* ver
     }
     hipLaunchKernelGGL(sdf_pullback_kernel, dim3(SDF_NS, B), dim3(SDF_ADJ_NT), 0, stream, M, P, gate, (const SdfBox*)box,
                        reinterpret_cast<const SdfEntry*>(entries), (const SdfChunk*)chunks, part, tickets, adj, answer_tag, answer);
+    return hipGetLastError();
+}
+
+SdfChunk* sdf_work_chunks(void* entries, int B, int nv) {
+    return reinterpret_cast<SdfChunk*>(reinterpret_cast<unsigned char*>(entries) + sdf_chunk_offset(B, nv));
+}
+
+// the pull-back alone, for a producer of entries and chunk records other than sdf_entries_kernel (chained rounds: no answer tag)
+hipError_t launch_sdf_pullback(const DevModel& M, const DevPose& P, int B, const int* gate, const SdfBox* box, void* entries,
+                               SdfAdj* adj, hipStream_t stream) {
+    unsigned char* wk = reinterpret_cast<unsigned char*>(entries);
+    SdfAdj* part = reinterpret_cast<SdfAdj*>(wk + sdf_part_offset(B, M.nv));
+    int* tickets = reinterpret_cast<int*>(wk + sdf_ticket_offset(B, M.nv));
+    hipLaunchKernelGGL(sdf_pullback_kernel, dim3(SDF_NS, B), dim3(SDF_ADJ_NT), 0, stream, M, P, gate, box,
+                       reinterpret_cast<const SdfEntry*>(entries), (const SdfChunk*)sdf_work_chunks(entries, B, M.nv), part, tickets, adj,
+                       (unsigned*)nullptr, 0u);
     return hipGetLastError();
 }
 

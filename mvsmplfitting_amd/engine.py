@@ -113,6 +113,7 @@ class MvFit:
             m.gmm_means = fp(means); m.gmm_precisions = fp(prec); m.gmm_nll_weights = fp(nllw)
         self.has_vposer = vposer is not None
         self.has_gmm = gmm is not None
+        self.faces = _i32(model['faces']) if model.get('faces') is not None else None     # (what the scene term voxelises)
         ctx = C.c_void_p()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -122,6 +123,7 @@ class MvFit:
         self._check(rc)
         self.B = 0
         self.V = 0
+        self._obstacles = False
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -219,6 +221,8 @@ class MvFit:
         self._check(self._lib.mvfit_set_problems(
             self._ctx, B, V, batched, R.data_ptr(), t.data_ptr(), f.data_ptr(), c.data_ptr(),
             gt.data_ptr(), wc.data_ptr()))
+        if B != self.B or V != self.V:
+            self._obstacles = False              # (the C side drops them with the batch they were frozen for)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -386,6 +390,35 @@ class MvFit:
             float(scale_factor), float(robustifier) if robustifier else 0.0, loss.data_ptr(),
             g.data_ptr() if need_grad else None, phi.data_ptr() if return_phi else None))
         return loss, g, phi
+
+    def set_scene_obstacles(self, vertices, scene_sizes, grid_size=32, scale_factor=0.2, robustifier=None):
+        """Freeze the other bodies of every scene as obstacles of the fit (include/mvfit.h:mvfit_set_scene_obstacles).
+        vertices[B,Nv,3] (world) of the B problems of set_problems; scene_sizes: problems per scene, in order (they add up to
+        B).  While set, a stage with coll_loss_weight w > 0 adds (w * S_j)^2 to problem j in closure() and fit(), S_j = the
+        samples of j's vertices in the frozen fields of the other bodies of its scene (the model's own faces)."""
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[0] != self.B or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [B, %d, 3] with B = %d' % (self.nv, self.B))
+        first = np.concatenate([[0], np.cumsum([int(n) for n in scene_sizes])]).astype(np.int32)
+        self._check(self._lib.mvfit_set_scene_obstacles(
+            self._ctx, v.data_ptr(), first.ctypes.data_as(_lib._ip), len(first) - 1, int(grid_size), float(scale_factor),
+            float(robustifier) if robustifier else 0.0))
+        self._obstacles = True
+        self._obstacle_grid = int(grid_size)
+
+    def scene_obstacles(self):
+        """Diagnostics: (phi [B,G,G,G], boxes [B,4] = centre and scale) of the frozen obstacles."""
+        box = torch.empty(self.B, 4, device=self.device)
+        self._check(self._lib.mvfit_scene_obstacles_read(self._ctx, None, box.data_ptr()))
+        G = self._obstacle_grid
+        phi = torch.empty(self.B, G, G, G, device=self.device)
+        self._check(self._lib.mvfit_scene_obstacles_read(self._ctx, phi.data_ptr(), None))
+        return phi, box
+
+    def clear_scene_obstacles(self):
+        """Remove the obstacles of set_scene_obstacles."""
+        self._check(self._lib.mvfit_set_scene_obstacles(self._ctx, None, None, 0, 0, 0.0, 0.0))
+        self._obstacles = False
 
     def set_sdf(self, faces, num_faces=1, grid_size=128):
         """Configure the interpenetration term (include/mvfit.h:mvfit_set_sdf).  ``faces`` [F,3]; ``num_faces``
@@ -576,10 +609,11 @@ class MvFit:
         return recv
 
     def sdf_term_read(self):
-        """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term."""
-        smp = torch.empty(self.B, self.nv, 4, device=self.device)
+        """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
+        (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set."""
+        smp = None if self._obstacles else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
-        self._check(self._lib.mvfit_sdf_term_read(self._ctx, smp.data_ptr(), S.data_ptr()))
+        self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S
 
     # ------------------------------------------------------------------ profiling
