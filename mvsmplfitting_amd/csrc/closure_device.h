@@ -850,7 +850,8 @@ __device__ __forceinline__ void sparse_forward(const DevModel& M, ClosureLds& L,
 // SDFW (service launches of the single-launch fit only): S is the answer of the term's kernels to THIS round's request - the
 // combining wave waits for the answer tag here, i.e. the keypoint phase (E4) and E5 run under the term's kernels; a wait that
 // times out (200 ms) makes the loss NaN and is counted: the host fails the fit
-template <bool SDFW = false>
+// SDFT = false: an instantiation that can never see the term (its prologue got no SdfAdj): the term's branch is not compiled
+template <bool SDFW = false, bool SDFT = true>
 __device__ __forceinline__ double loss_combine(const DevModel& M, ClosureLds& L, int V, const DevWeights& W, bool writer) {
     const bool use_vp = (W.flags & MVFIT_F_VPOSER) != 0;
     const bool use_gmm = !use_vp && (W.flags & MVFIT_F_PRIOR_GMM);
@@ -889,7 +890,7 @@ __device__ __forceinline__ double loss_combine(const DevModel& M, ClosureLds& L,
     // interpenetration term (fitting.py:352-393): pen = (w S / valid_people)^2 with S from sdf_term.hip
     double l_coll = 0.0;
     float sdf_fac = 0.f;
-    if (L.sdf_adj && W.coll_w > 0.f) {
+    if (SDFT && L.sdf_adj && W.coll_w > 0.f) {
         bool answered = true;
         if constexpr (SDFW) {
             if (L.sdf_wait_tag) {
@@ -1188,7 +1189,9 @@ __device__ __forceinline__ void contraction_backward(const DevModel& M, ClosureL
 // ---------------------------------------------------------------------------------------------
 // DEFER: the loss's scalar terms were left uncombined by loss_and_keypoint_grad<true>; the last wave - idle in E5 - combines
 // them here, under E5 (400 cycles that every thread used to spend between the loss's barrier and this function's first one)
-template <bool REMOTE = false, bool DEFER = false, bool SDFW = false>
+// SDFT = false: the kernel can never see the SDF term (no SdfAdj reaches its prologue, L.sdf_fac stays 0): the factor is a
+// compile-time zero and the term's branches of E6, E8 and E9 are not in the code
+template <bool REMOTE = false, bool DEFER = false, bool SDFW = false, bool SDFT = true>
 __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& L, int V, const DevWeights& W, int tid) {
     const bool use_vp = (W.flags & MVFIT_F_VPOSER) != 0;
     const int ns = L.M.ns, nc = L.M.nc, nc_pad = L.M.nc_pad;
@@ -1196,7 +1199,7 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
     // ---- E5: g_x = Ksel^T g_kp ; g_vposed = Tr^T g_x ----
     if constexpr (DEFER) {
         static_assert(NC_MAX + NJ * 3 <= STEP_NT - 64, "E5's threads leave the last wave free");
-        if (tid >= STEP_NT - 64) loss_combine<SDFW>(M, L, V, W, tid == STEP_NT - 64);
+        if (tid >= STEP_NT - 64) loss_combine<SDFW, SDFT>(M, L, V, W, tid == STEP_NT - 64);
     }
     if (tid < nc_pad) {
         float v = 0.f;
@@ -1234,7 +1237,7 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
     }
     __syncthreads();
     PH_T(4);
-    const float sdf_fac = L.sdf_fac;       // (side results of the loss's combine: complete behind this barrier in either mode)
+    const float sdf_fac = SDFT ? L.sdf_fac : 0.f;       // (side results of the loss's combine: complete behind this barrier in either mode)
     // ---- E6: g_A = sum_s W[s][j] [g_x v_posed^T | g_x]: 16-lane row per joint, lanes stride s ----
     if (tid < NJ * 16) {
         const int j = tid >> 4, g = tid & 15;
@@ -1402,59 +1405,64 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
         else if (i < DV) g = use_vp ? 2.f * L.opt.x[i] * wp2 : 0.f;
         L.grad[i] = g;
     } else if (tid < NJ) {
+        // Every product and sum of this block is stated: fmaf where the compiler fused a product into a sum, separately
+        // rounded products (contraction off) where it paired them into packed multiplies and added afterwards - the form
+        // the block had in every kernel when its bits were recorded (tests/test_gpu_closure_bits.py), read off the gfx950
+        // code.  Said explicitly it no longer depends on the code around it.  Products with the zero entries
+        // of K are left out: they add an exact zero.
+#pragma clang fp contract(off)
         const float rx = L.pose.theta[3 * tid], ry = L.pose.theta[3 * tid + 1], rz = L.pose.theta[3 * tid + 2];
         const float ex = rx + 1e-8f, ey = ry + 1e-8f, ez = rz + 1e-8f;
         const float a = L.pose.rod[tid][0], sn = L.pose.rod[tid][1], cs = L.pose.rod[tid][2];
         const float ia = 1.0f / a;
-        const float kx = rx * ia, ky = ry * ia, kz = rz * ia;
+        const float kx = rx * ia, ky = ry * ia, kz = rz * ia;      // K = [0 -kz ky ; kz 0 -kx ; -ky kx 0]
         const float oc = 1.f - cs;
-        const float K[9] = {0.f, -kz, ky, kz, 0.f, -kx, -ky, kx, 0.f};
-        float KK[9];
-        mat3_mul(K, K, KK);
         float g[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) g[e] = L.gR[tid][e];
-        float gK_dot = 0.f, gKK_dot = 0.f;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) { gK_dot += g[e] * K[e]; gKK_dot += g[e] * KK[e]; }
-        float ga = cs * gK_dot + sn * gKK_dot;
-        // gK = sn g + oc (g K^T + K^T g)
-        float gKt[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int jq = 0; jq < 3; ++jq) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int m = 0; m < 3; ++m) { s1 += g[i * 3 + m] * K[jq * 3 + m]; s2 += K[m * 3 + i] * g[m * 3 + jq]; }
-                gKt[i * 3 + jq] = sn * g[i * 3 + jq] + oc * (s1 + s2);
-            }
-        const float gkx = gKt[7] - gKt[5], gky = gKt[2] - gKt[6], gkz = gKt[3] - gKt[1];
-        ga -= (gkx * rx + gky * ry + gkz * rz) * (ia * ia);
-        float gth[3] = {(gkx + ga * ex) * ia, (gky + ga * ey) * ia, (gkz + ga * ez) * ia};
+        // K K (symmetric): the off-diagonal entries are single products, the diagonal ones -(ky^2 + kz^2), -(kx^2 + kz^2),
+        // -(ky^2 + kx^2) with the roundings below
+        const float kxx = kx * kx, kzz = kz * kz, kxy = kx * ky, kxz = kx * kz, kyz = ky * kz;
+        const float KK0 = -fmaf(ky, ky, kzz), KK4 = -(kxx + kzz), KK8 = -fmaf(ky, ky, kxx);
+        // g . K: six rounded products added in the order of the entries
+        const float gK_dot = ((((ky * g[2] - kz * g[1]) + kz * g[3]) - kx * g[5]) - ky * g[6]) + kx * g[7];
+        // g . KK: the first three terms fused, the other six rounded and added in order
+        float gKK_dot = fmaf(kxz, g[2], fmaf(kxy, g[1], KK0 * g[0]));
+        gKK_dot += kxy * g[3]; gKK_dot += KK4 * g[4]; gKK_dot += kyz * g[5];
+        gKK_dot += kxz * g[6]; gKK_dot += kyz * g[7]; gKK_dot += KK8 * g[8];
+        float ga = fmaf(cs, gK_dot, sn * gKK_dot);
+        // gK = sn g + oc (g K^T + K^T g), off-diagonal entries only: entry e = fma(sn, g[e], oc * (s1 + s2)), s1 and s2 the
+        // two 3-term sums with their zero term gone - first product rounded, second fused (one sum of entry 7: both rounded)
+        const float gKt1 = fmaf(sn, g[1], oc * (fmaf(g[2], -kx, g[0] * kz) + fmaf(g[7], -ky, kz * g[4])));
+        const float gKt3 = fmaf(sn, g[3], oc * (fmaf(ky, g[5], -(kz * g[4])) + fmaf(kx, g[6], -(kz * g[0]))));
+        const float gKt2 = fmaf(sn, g[2], oc * (fmaf(kx, g[1], -(ky * g[0])) + fmaf(g[8], -ky, kz * g[5])));
+        const float gKt6 = fmaf(sn, g[6], oc * (fmaf(g[8], ky, -(kz * g[7])) + fmaf(g[3], -kx, ky * g[0])));
+        const float gKt5 = fmaf(sn, g[5], oc * (fmaf(kx, g[4], -(ky * g[3])) + fmaf(kx, g[8], -(kz * g[2]))));
+        const float gKt7 = fmaf(sn, g[7], oc * (fmaf(g[8], -kx, kz * g[6]) + (ky * g[1] - kx * g[4])));
+        const float gkx = gKt7 - gKt5, gky = gKt2 - gKt6, gkz = gKt3 - gKt1;
+        ga = fmaf(-fmaf(gkz, rz, fmaf(gky, ry, gkx * rx)), ia * ia, ga);
+        float gth[3] = {ia * fmaf(ex, ga, gkx), ia * fmaf(ey, ga, gky), ia * fmaf(ez, ga, gkz)};
         if (tid > 0 && !use_vp) {
-            // priors on body_pose (fitting.py:330-337)
+            // priors on body_pose (fitting.py:330-337); body_pose[3 (tid - 1) + q] is this joint's own angle component
+            const float bp[3] = {rx, ry, rz};
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
-                const int i = 3 * (tid - 1) + q;               // body_pose index
-                const float bp = L.pose.theta[3 + i];
                 float gq = gth[q];
-                if (W.flags & MVFIT_F_PRIOR_GMM) { if (!(L.flags_dropped & 1)) gq += L.gmm_d[i] * wp2; }
-                else if (!(L.flags_dropped & 1)) gq += 2.f * bp * wp2;
-                gq += 2.f * bp * 16.f * wp2;
+                if (W.flags & MVFIT_F_PRIOR_GMM) { if (!(L.flags_dropped & 1)) gq = fmaf(L.gmm_d[3 * (tid - 1) + q], wp2, gq); }
+                else if (!(L.flags_dropped & 1)) gq = fmaf(2.f * bp[q], wp2, gq);
+                gq = fmaf(2.f * bp[q] * 16.f, wp2, gq);
                 gth[q] = gq;
             }
         }
-        if (tid > 0 && !(L.flags_dropped & 2)) {
-            // angle prior gradient on full_pose[3:66] idx 52,55,9,12
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int i = 3 * (tid - 1) + q;
-                if (i == 52 || i == 55 || i == 9 || i == 12) {
-                    const float sg = (i == 52) ? 1.f : -1.f;
-                    gth[q] += 2.f * expf(2.f * L.pose.theta[3 + i] * sg) * sg * W.bend_w;
-                }
-            }
+        // angle prior gradient on body_pose 9, 12 (component 0 of joints 4, 5), 52, 55 (component 1 of joints 18, 19); sign +
+        // for 52 (fitting.py:345-350): one evaluation for the four lanes that carry one
+        static_assert(NJ == 24, "the bending prior's joints are those of the 24-joint skeleton");
+        const int aq = (tid == 4 || tid == 5) ? 0 : ((tid == 18 || tid == 19) ? 1 : -1);
+        if (aq >= 0 && !(L.flags_dropped & 2)) {
+            const float sg = tid == 18 ? 1.f : -1.f;
+            const float add = 2.f * expf(2.f * (aq == 0 ? rx : ry) * sg) * sg;
+            const float gq = fmaf(add, W.bend_w, aq == 0 ? gth[0] : gth[1]);
+            if (aq == 0) gth[0] = gq; else gth[1] = gq;
         }
         L.gtheta[3 * tid] = gth[0]; L.gtheta[3 * tid + 1] = gth[1]; L.gtheta[3 * tid + 2] = gth[2];
         // the flat gradient is written where its parts are made (global_orient | body_pose are contiguous; with VPoser the

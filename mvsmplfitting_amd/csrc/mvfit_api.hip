@@ -278,8 +278,11 @@ __global__ __launch_bounds__(STEP_NT) void fit_init_kernel(DevModel M, const Obs
 // cache every round (86 -> 73 KB), 1.2-1.6 % per fit (speed only: the result does not depend on it)
 // SDFS: the launch serves stages with the SDF term by asking for it (closure_device.h: publish_sdf_request, loss_combine<true>);
 // sv = {pass operands of the chained layout (coefT), gate words, answer tags, global problem index, round offset of the launch}
+// SDFT = false: no SdfAdj ever reaches the kernel's prologue (fit_persistent_kernel without SDFS): the adjoint is compiled without
+// the term's branches (the chained step kernel gets the term through its prologue and keeps them)
 struct SdfService { const DevPose* P; int* gate; const unsigned* tag; int b; int round0; };
-template <bool REMOTE = false, bool REUSE = false, bool LEAN = false, bool COMPACT = false, bool SDFS = false, bool ROFF = SDFS>
+template <bool REMOTE = false, bool REUSE = false, bool LEAN = false, bool COMPACT = false, bool SDFS = false, bool ROFF = SDFS,
+          bool SDFT = true>
 __device__ __forceinline__ bool fit_round(const DevModel& M, ClosureLds& L, int nviews, const LbHist<float>& H,
                           bool from_pass, bool have_pose, double* stage_final, int tid,
                           LbGramLds GL = LbGramLds{nullptr, 0, 0}, float* trace = nullptr, int trace_cap = 0,
@@ -328,7 +331,7 @@ __device__ __forceinline__ bool fit_round(const DevModel& M, ClosureLds& L, int 
     }
     loss_and_keypoint_grad<true>(M, L, nviews, W, true, tid);          // (scalar terms combined under the adjoint's first phase)
     PH_T(3);
-    closure_backward<REMOTE, true, SDFS>(M, L, nviews, W, tid);
+    closure_backward<REMOTE, true, SDFS, SDFT>(M, L, nviews, W, tid);
     const double total = L.total;
     if (trace) {                                           // (x_trial, loss) of this closure call (mvfit_fit_trace)
         const int k = L.opt.lbS.n_closure;                 // closures consumed so far = index of this one
@@ -527,7 +530,7 @@ __global__ __launch_bounds__(STEP_NT) void fit_persistent_kernel(DevModel M, con
         // of the closure out of the round loop (which costs >256 live VGPRs and spills)
         int t = tid;
         asm volatile("" : "+v"(t));
-        done = fit_round<REMOTE, REUSE, LEAN, true, SDFS, SDFS || QUEUE>(M, L, nviews, H, false, false, F.stage_final + (size_t)b * MVFIT_MAX_STAGES, t, LbGramLds{nullptr, 0, 0},
+        done = fit_round<REMOTE, REUSE, LEAN, true, SDFS, SDFS || QUEUE, SDFS>(M, L, nviews, H, false, false, F.stage_final + (size_t)b * MVFIT_MAX_STAGES, t, LbGramLds{nullptr, 0, 0},
                          F.trace ? F.trace + (size_t)b * F.trace_cap * (DV + 1) : nullptr, F.trace_cap,
                          ring, ring.tag != nullptr, (int)blockIdx.x,        // ring slots: sub-batch-relative problem index
                          SdfService{SDFS ? &P : nullptr, SDFS ? F.sdf_gate : nullptr, SDFS ? F.sdf_tag : nullptr, b, round0});
