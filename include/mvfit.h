@@ -57,6 +57,7 @@ extern "C" {
 #define MVFIT_E_HIP (-2)
 #define MVFIT_E_STATE (-3)
 #define MVFIT_E_UNSUPPORTED (-4)
+#define MVFIT_ASSOC_MAX_DET 16      /* detections per view of a frame (the association op) */
 #define MVFIT_SCENE_BODIES_MAX 256   /* bodies per scene (mvfit_render_scene images, mvfit_scene_sdf_loss scenes) */
 
 /* flags (mvfit_weights.flags) */
@@ -392,6 +393,47 @@ int mvfit_scene_obstacles_read(mvfit_ctx* ctx, float* phi, float* boxes);
  * Same arithmetic as the reference: float64 accumulation, AtA rounded to float32 before the float64 solve (:54). */
 int mvfit_triangulate(mvfit_ctx* ctx, int B, int V, const float* keypoints, const double* intris, const double* extris,
                       double* joints3d);
+
+/* Association of 2-D detections across the views of a frame: which detections show the same person.  A detector run per
+ * view lists its people in its own order; this op scores every cross-view pair of a frame's detections geometrically and
+ * clusters them into persons.  Batched over F frames, asynchronous on the ctx stream, no set_problems call needed.
+ *   keypoints[F,V,Nmax,17,3] float32 dev (u, v, confidence) ; count[F,V] int32 dev: detections of view v in frame f (slots
+ *   k < count are read; a value above Nmax counts as Nmax, below 0 as 0) ; intris[V,3,3], extris[V,4,4] float64 dev as the
+ *   triangulation takes them.  D = V * Nmax, detection (view v, slot k) has the flat index a = v * Nmax + k.
+ *   cost_out[F,D,D] float64 dev out or NULL ; labels[F,V,Nmax] int32 dev out ; num_clusters[F] int32 dev out or NULL.
+ * Limits: F >= 1, 2 <= min_views <= V <= MVFIT_MAX_VIEWS, 1 <= Nmax <= MVFIT_ASSOC_MAX_DET, 1 <= min_joints <= 17, max_cost
+ * finite and >= 0 ; MVFIT_E_ARG otherwise and for a NULL keypoints / count / intris / extris / labels.
+ *
+ * Cost (float64, every product and sum rounded on its own - no fused multiply-add -, operands in the order written, sums
+ * left to right unless bracketed; sqrt and / correctly rounded):
+ *   view v:  Ki = inverse of intris[v] by cofactors, as the triangulation forms it: with K = (a b c; d e f; g h i),
+ *            A = e*i - f*h, B = -(d*i - f*g), C = d*h - e*g, id = 1 / (a*A + b*B + c*C),
+ *            Ki = (A*id, -(b*i - c*h)*id, (b*f - c*e)*id ; B*id, (a*i - c*g)*id, -(a*f - c*d)*id ;
+ *                  C*id, -(a*h - b*g)*id, (a*e - b*d)*id) ;
+ *            R, t = rotation and translation of extris[v] ; origin o_i = -((R0i*t0 + R1i*t1) + R2i*t2).
+ *   detection a, joint j with pixel (x, y) and confidence cf, all converted to float64:
+ *            n_r = Ki_r0*x + Ki_r1*y + Ki_r2, nn = sqrt(n0*n0 + n1*n1 + n2*n2), n_r = n_r / nn,
+ *            direction d_i = (R0i*n0 + R1i*n1) + R2i*n2.
+ *   pair a < b of different views, both slots below their count, joint j with both confidences > 0:
+ *            b_ = o_b - o_a, c = d_a x d_b (c0 = da1*db2 - da2*db1, c1 = da2*db0 - da0*db2, c2 = da0*db1 - da1*db0),
+ *            s2 = (c0*c0 + c1*c1) + c2*c2 ;
+ *            s2 > 1e-18:  dist_j = |(b_0*c0 + b_1*c1) + b_2*c2| / sqrt(s2)      (distance of the two lines, world units)
+ *            otherwise:   x = b_ x d_a (same component pattern), dist_j = sqrt((x0*x0 + x1*x1) + x2*x2)
+ *            w_j = sqrt(cf_a * cf_b) ; num = num + w_j*dist_j, den = den + w_j in ascending j from 0.
+ *   cost(a, b) = cost(b, a) = num / den when at least min_joints joints took part, +inf otherwise, and +inf for a == b, for
+ *   two detections of one view and for a slot at or above its count.
+ * Clustering, per frame (complete linkage, cannot-link within a view): every valid detection starts as its own cluster.
+ * While a pair of clusters {A, B} has L(A, B) = max over a in A, b in B of cost(a, b) <= max_cost - two clusters that share a
+ * view have L = +inf by the rule above -, the pair with the smallest L is merged; ties go to the lexicographically smallest
+ * (smallest member of A, smallest member of B), A the cluster with the smaller smallest member.  Then clusters of fewer than
+ * min_views members get label -1, as do slots at or above their count; the others are numbered 0, 1, ... in ascending order
+ * of their smallest member, and num_clusters[f] is their number.  A cluster never holds two detections of one view.
+ * A frame's costs and labels do not depend on F, on the frame's position in the call or on the groups of frames the op
+ * works in (each group's rays and D x D linkage matrices, D * (17 * 32 + D * 8) bytes per frame behind a 512-byte head,
+ * stay under 256 MB of a workspace the ctx keeps and grows to the largest call). */
+int mvfit_associate_views(mvfit_ctx* ctx, int F, int V, int Nmax, const float* keypoints, const int32_t* count,
+                          const double* intris, const double* extris, double max_cost, int min_joints, int min_views,
+                          double* cost_out, int32_t* labels, int32_t* num_clusters);
 
 /* Per-frame initial guess, stage 1 for single-view input (code/utils/init_guess.py:54-74): the depth guess that replaces
  * the triangulation when a frame has ONE view - the model's rest-pose keypoints pushed along the camera's z axis by

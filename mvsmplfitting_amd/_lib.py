@@ -16,6 +16,7 @@ D_MODEL = 86
 NUM_KP = 17
 MAX_VIEWS = 16
 MAX_STAGES = 8
+ASSOC_MAX_DET = 16
 
 F_VPOSER = 1
 F_PRIOR_GMM = 2
@@ -68,7 +69,8 @@ class Options(C.Structure):
 EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'mvfit_set_problems', 'mvfit_set_joints3d',
            'mvfit_closure', 'mvfit_vertices', 'mvfit_vertices_backward', 'mvfit_full_pose', 'mvfit_fit', 'mvfit_fit_trace', 'mvfit_fit_stats', 'mvfit_decoder_stats', 'mvfit_debug_capture_pass', 'mvfit_sdf', 'mvfit_set_sdf', 'mvfit_sdf_term_read', 'mvfit_triangulate', 'mvfit_depth_guess', 'mvfit_umeyama', 'mvfit_project_points', 'mvfit_gather', 'mvfit_profile', 'mvfit_profile_read', 'mvfit_profile_vertex_pass', 'mvfit_profile_vertex_pass_ex', 'mvfit_pass_profile',
            'mvfit_options_default', 'mvfit_create_ex', 'mvfit_set_options', 'mvfit_get_options', 'mvfit_sdf_info',
-           'mvfit_lbfgs_kat', 'mvfit_render_overlay', 'mvfit_render_scene', 'mvfit_scene_sdf_loss', 'mvfit_set_scene_obstacles', 'mvfit_scene_obstacles_read']
+           'mvfit_lbfgs_kat', 'mvfit_render_overlay', 'mvfit_render_scene', 'mvfit_scene_sdf_loss', 'mvfit_set_scene_obstacles', 'mvfit_scene_obstacles_read',
+           'mvfit_associate_views']
 
 
 def load(path=None):
@@ -128,6 +130,8 @@ def load(path=None):
     lib.mvfit_sdf_term_read.restype = C.c_int
     lib.mvfit_triangulate.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.mvfit_triangulate.restype = C.c_int
+    lib.mvfit_associate_views.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp]
+    lib.mvfit_associate_views.restype = C.c_int
     lib.mvfit_depth_guess.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.mvfit_depth_guess.restype = C.c_int
     lib.mvfit_umeyama.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]

@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import associate as assoc
 from . import io_formats as iof
 from .engine import MvFit, SCENE_PALETTE, stage_weights
 from .init_guess import init_guess_batch, initial_params
@@ -211,7 +212,7 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scen
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
-               save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None):
+               save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -237,7 +238,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     stage's weights plus coll_loss_weight = weight, and the refined parameters are what is written; ``final_loss`` is then
     the refined objective, collision term included, the serial's result gains ``scene_report`` and ``timing`` a 'refine'
     entry.  It needs the multi-person path without is_seq (ValueError for persons=0, is_seq=True or a dict without
-    ``weight``).  Problems fitted in two groups (with and without 3-D targets) are refined with the 2-D objective only."""
+    ``weight``).  Problems fitted in two groups (with and without 3-D targets) are refined with the 2-D objective only.
+    associate: None, True or a dict of max_cost=0.05, min_joints=6, min_views=2, max_move=0.5, max_gap=5 (distances in
+    metres; associate.DEFAULTS) - the files' ``people`` lists are in detector order, view by view: the persons are found by
+    associate.associate_serial (cross-view association on the device, tracks over the frames) instead of being read off
+    the list index or ``person_id``, and ``persons`` ('all' or a list) then names track ids, which count from 0 in order
+    of first appearance.  Everything after the keypoints is the multi-person path unchanged.  The serial's result gains
+    ``association`` (the report of associate_serial) and ``timing`` an 'associate' entry (reading the detections
+    included).  ValueError with persons=0 (one
+    identity needs no association), for an unknown key, and with use_3d: the files' 3-D annotations are keyed by
+    ``person_id`` and matching them to tracks is not built."""
     import time as _time
 
     def _tick(key, t0):
@@ -268,6 +278,14 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         unknown = set(scene_collision) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
         if unknown:
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
+    if associate is not None and associate is not False:
+        if not multi:
+            raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
+        if use_3d:
+            raise ValueError('associate with use_3d is not available: 3-D annotations are keyed by person_id, not by track')
+        associate = assoc.check_params(associate)
+    else:
+        associate = None
     for name, val in (('fix_scale', fix_scale), ('fix_shape', fix_shape)):
         if isinstance(val, dict) and want is not None and not set(want) <= set(val):
             raise ValueError('%s holds no value for persons %s' % (name, sorted(set(want) - set(val))))
@@ -315,7 +333,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         """The multi-person path of one serial -> its result dict, or None when no requested person occurs."""
         nonlocal _t
         F = len(frames)
-        ids_all, kpp, pmask = load_serial_people(frames, V)
+        association = None
+        if associate is not None:
+            _t = _tick('read', _t)
+            ids_all, kpp, pmask, association = assoc.associate_serial(eng, frames, extris, intris, **associate)
+            _t = _tick('associate', _t)
+        else:
+            ids_all, kpp, pmask = load_serial_people(frames, V)
         col = {p: i for i, p in enumerate(ids_all)}
         ids = [p for p in (ids_all if want is None else want) if p in col]
         prob = [(f, p) for f in range(F) for p in ids if pmask[f, col[p]].any()]
@@ -454,6 +478,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                    problem_frame=pf, problem_person=pp, persons=sorted(set(pp.tolist())))
         if scene_report is not None:
             out['scene_report'] = scene_report
+        if association is not None:
+            out['association'] = association
         _t = _tick('write', _t)
         if save_images:
             palette = np.asarray(SCENE_PALETTE, np.float32)

@@ -70,6 +70,11 @@ hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int*
                                int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,
                                hipStream_t stream);
 size_t scene_ws_bytes(int n, int m, int Nv, int Nf, int H, int W);
+size_t assoc_frame_bytes(int D);
+size_t assoc_head_bytes();
+hipError_t launch_associate_group(const float* kps, const int32_t* count, const double* intris, const double* extris, int f0,
+                                  int nf, int V, int Nmax, double max_cost, int min_joints, int min_views, void* ws,
+                                  double* cost_out, int32_t* labels, int32_t* num_clusters, hipStream_t stream);
 int scene_sdf_blocks(int nv);
 hipError_t launch_scene_boxes(const float* verts, int nv, int b0, int n, float factor, float4* box, float* local,
                               hipStream_t stream);
@@ -809,6 +814,10 @@ struct mvfit_ctx {
     size_t scn_ws_size = 0;
     int32_t* h_scn_tab = nullptr;
     size_t h_scn_tab_bytes = 0;
+    // mvfit_associate_views (associate.hip): ray origins, then rays and linkage matrices of one group of frames; grown to
+    // the largest call
+    void* d_assoc_ws = nullptr;
+    size_t assoc_ws_size = 0;
     // frozen obstacles of the scene term (mvfit_set_scene_obstacles): per problem its scene's row, its box and its field.
     // The buffers keep their addresses while (B, grid) stay the same, so a re-freeze leaves the captured round graph valid.
     bool obst_on = false;
@@ -1093,6 +1102,7 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
     if (c->d_scn_ws) hipFree(c->d_scn_ws);
     if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
+    if (c->d_assoc_ws) hipFree(c->d_assoc_ws);
     for (void* p : c->allocs) if (p) hipFree(p);
     if (c->h_done) hipHostFree(c->h_done);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
@@ -2271,6 +2281,44 @@ extern "C" int mvfit_triangulate(mvfit_ctx* c, int B, int V, const float* keypoi
     HIP_OK(c, hipSetDevice(c->device));
     hipError_t e = launch_triangulate(keypoints, intris, extris, B, V, NKP, joints3d, c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "triangulate launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+// Cross-view association of a frame's detections (associate.hip).  Frames go through in groups whose rays and linkage
+// matrices stay under the 256 MB cap of the renderer's and the scene op's workspaces; a frame's result does not depend on
+// its group.
+extern "C" int mvfit_associate_views(mvfit_ctx* c, int F, int V, int Nmax, const float* keypoints, const int32_t* count,
+                                     const double* intris, const double* extris, double max_cost, int min_joints, int min_views,
+                                     double* cost_out, int32_t* labels, int32_t* num_clusters) {
+    if (!c) return MVFIT_E_ARG;
+    if (!keypoints || !count || !intris || !extris || !labels)
+        return fail(c, MVFIT_E_ARG, "mvfit_associate_views: null %s",
+                    !keypoints ? "keypoints" : !count ? "count" : !intris ? "intris" : !extris ? "extris" : "labels");
+    if (F <= 0 || V > MVFIT_MAX_VIEWS || Nmax < 1 || Nmax > MVFIT_ASSOC_MAX_DET || min_views < 2 || min_views > V)
+        return fail(c, MVFIT_E_ARG, "mvfit_associate_views: bad argument (F=%d V=%d Nmax=%d min_views=%d): 2 <= min_views <= V <= %d, "
+                    "1 <= Nmax <= %d", F, V, Nmax, min_views, MVFIT_MAX_VIEWS, MVFIT_ASSOC_MAX_DET);
+    if (min_joints < 1 || min_joints > NKP)
+        return fail(c, MVFIT_E_ARG, "mvfit_associate_views: min_joints %d outside [1, %d]", min_joints, NKP);
+    if (!(max_cost >= 0.0) || std::isinf(max_cost))
+        return fail(c, MVFIT_E_ARG, "mvfit_associate_views: max_cost %g is not a finite value >= 0", max_cost);
+    if (max_cost == 0.0) max_cost = 0.0;                     // -0.0: the kernels compare bit patterns
+    HIP_OK(c, hipSetDevice(c->device));
+    const int D = V * Nmax;
+    const size_t cap = (size_t)256 << 20, per = assoc_frame_bytes(D);
+    const int group = (int)std::min<size_t>({(size_t)F, std::max<size_t>(1, (cap - assoc_head_bytes()) / per), (size_t)32768});
+    const size_t need = assoc_head_bytes() + (size_t)group * per;
+    if (need > c->assoc_ws_size) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));          // an earlier call may still run on the old one
+        if (c->d_assoc_ws) hipFree(c->d_assoc_ws);
+        c->d_assoc_ws = nullptr; c->assoc_ws_size = 0;
+        HIP_OK(c, hipMalloc(&c->d_assoc_ws, need));
+        c->assoc_ws_size = need;
+    }
+    for (int f0 = 0; f0 < F; f0 += group) {
+        const hipError_t e = launch_associate_group(keypoints, count, intris, extris, f0, std::min(group, F - f0), V, Nmax, max_cost,
+                                                    min_joints, min_views, c->d_assoc_ws, cost_out, labels, num_clusters, c->stream);
+        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_associate_views: launch: %s", hipGetErrorString(e));
+    }
     return MVFIT_OK;
 }
 

@@ -451,6 +451,30 @@ class MvFit:
         self._check(self._lib.mvfit_triangulate(self._ctx, B, V, kp.data_ptr(), K.data_ptr(), E.data_ptr(), out.data_ptr()))
         return out
 
+    def associate_views(self, keypoints, count, intris, extris, max_cost=0.05, min_joints=6, min_views=2, return_cost=False):
+        """Which detections of a frame's views show the same person (include/mvfit.h:mvfit_associate_views).
+        keypoints [F,V,Nmax,17,3] (u, v, confidence) in each view's own order, count [F,V] detections per view, the float64
+        camera matrices intris [V,3,3], extris [V,4,4].  max_cost: the largest mean distance between the rays of two
+        detections of one person, in world units (metres); min_joints: joints both detections must carry; min_views:
+        detections a person needs.  Returns (labels [F,V,Nmax] int32: cluster number or -1, num_clusters [F] int32) and,
+        with return_cost, the cost matrix [F,D,D] float64, D = V * Nmax."""
+        kp = self._dev(keypoints)
+        if kp.dim() != 5 or kp.shape[3] != 17 or kp.shape[4] != 3:
+            raise MvFitError('keypoints must be [F, V, Nmax, 17, 3]')
+        F, V, N = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+        cnt = count if isinstance(count, torch.Tensor) else torch.as_tensor(np.asarray(count))
+        cnt = cnt.to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(cnt.shape) != (F, V):
+            raise MvFitError('count must be [F, V] = [%d, %d]' % (F, V))
+        K, E = self._f64(intris, (V, 3, 3)), self._f64(extris, (V, 4, 4))
+        labels = torch.empty(F, V, N, dtype=torch.int32, device=self.device)
+        num = torch.empty(F, dtype=torch.int32, device=self.device)
+        cost = torch.empty(F, V * N, V * N, dtype=torch.float64, device=self.device) if return_cost else None
+        self._check(self._lib.mvfit_associate_views(
+            self._ctx, F, V, N, kp.data_ptr(), cnt.data_ptr(), K.data_ptr(), E.data_ptr(), float(max_cost), int(min_joints),
+            int(min_views), cost.data_ptr() if return_cost else None, labels.data_ptr(), num.data_ptr()))
+        return (labels, num, cost) if return_cost else (labels, num)
+
     def depth_guess(self, rest_joints, extri, intri, keypoints):
         """joints3d [B,17,3] float64 for frames seen by ONE camera (include/mvfit.h:mvfit_depth_guess; reference
         init_guess.py:54-74): rest_joints [17,3] float64, extri [4,4], intri [3,3] float64, keypoints [B,17,3]

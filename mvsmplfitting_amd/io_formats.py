@@ -79,6 +79,8 @@ def read_people(path):
     """{person id: [17, 3] float32 (x, y, confidence)} of one keypoint file.  The id of a ``people`` entry is its integer
     ``person_id`` field when EVERY entry of the file carries one, else its index in the list.  An entry whose confidences
     are all zero counts as absent - how an index-identified file says "person 1 is not in this view but person 2 is".
+    Files whose lists are in detector order carry no identity this rule could read: those go through
+    associate.associate_serial (batch.fit_folder(associate=...)), which finds the persons across views and frames.
     Two entries with one id: ValueError naming the file."""
     return _read_people(path, 'pose_keypoints_2d', 3)
 
