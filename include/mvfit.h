@@ -386,6 +386,68 @@ int mvfit_set_scene_obstacles(mvfit_ctx* ctx, const float* vertices, const int32
  * MVFIT_E_STATE when no obstacles are set. */
 int mvfit_scene_obstacles_read(mvfit_ctx* ctx, float* phi, float* boxes);
 
+/* ---- Silhouette loss against per-view person masks, with its gradient on the vertices (csrc/silhouette.hip).  The reference
+ * has no term on the body's outline: this contract is the project's own.
+ *
+ * Images.  M mask images, all H x W (2 <= H, W <= 8192, M <= 65535).  Image i shows body image_body[i] through its own
+ * pinhole camera (R_i, t_i, f_i, c_i) - given per image, not taken from mvfit_set_problems.  A body may have any number of
+ * images, none included.  A mask pixel is "on" when its byte is non-zero.
+ *
+ * mvfit_set_silhouettes prepares, once per mask set:
+ *   Field D_i[H,W] float32: d2 = the exact integer squared Euclidean distance, in pixels, from the pixel to the nearest on
+ *     pixel (0 on the mask), computed in integer arithmetic; D = float32(sqrt(float64(d2))) - what
+ *     scipy.ndimage.distance_transform_edt(mask == 0) gives, cast to float32.  An image with no on pixel is ignored by both
+ *     terms, its field reads back as zeros and it has no contour points; an all-on image has field 0 and no contour.
+ *   Contour of image i: the on pixels with at least one 4-neighbour that lies inside the image and is off (a mask running
+ *     into the image border is a person cut by the frame, not an outline), in raster order; the k-th of them is kept iff
+ *     k % contour_stride == 0.  Stored as CSR contour_first[M+1] over the kept points and contour_xy[C,2] int32 (x, y).
+ *   The call waits for the stream (the contour sizes come back to the host); every other entry is asynchronous.
+ *
+ * mvfit_silhouette_loss evaluates at vertices[N,Nv,3] float32 (translation included, as mvfit_vertices returns them; Nv is
+ * the model's):
+ *   Projection, the rasteriser's fp32 sequence without contraction: p = ((R0 X + R1 Y) + R2 Z) + t, u = f (px / pz) + cx,
+ *     v = f (py / pz) + cy.  A vertex is valid in image i iff pz > 0.05; an invalid one contributes to neither term.
+ *   Term A (body inside mask).  Pixel-index coordinates x = u - 0.5, y = v - 0.5 (pixel (x, y) has its centre at
+ *     (x + .5, y + .5), as the rasteriser); xc = min(max(x, 0), W-1), x0 = min(int(floorf(xc)), W-2), a = xc - x0 in fp32,
+ *     likewise yc, y0, b.  In float64 from the fp32 a, b and the four field values:
+ *     d = (1-b)((1-a) D00 + a D01) + b((1-a) D10 + a D11); dd/dx = (1-b)(D01-D00) + b(D11-D10) if x == xc, else 0, likewise
+ *     dd/dy.  rho_A = d^2 when sigma <= 0, else sigma^2 d^2 / (sigma^2 + d^2) (the data term's GMoF form).
+ *     A_i = sum_j rho_A.
+ *   Term B (mask covered by body).  For a kept contour point with centre c = (x + .5, y + .5) and a valid vertex j:
+ *     dx = u_j - cx, dy = v_j - cy, m_j = dx*dx + dy*dy, products and sum each rounded to fp32.  The winner is the valid j
+ *     with the smallest m_j, ties to the lowest j; with no valid vertex the winner is -1 and the point contributes 0.
+ *     rho_B = m when sigma <= 0, else sigma^2 m / (sigma^2 + m), in float64 from the fp32 m.
+ *     B_i = contour_stride * sum_k rho_B; the gradient goes to the winner only: contour_stride * rho_B'(m) * 2 (dx, dy) in
+ *     pixel space.  Term B measures the distance to the nearest projected vertex, not to the outline polygon.
+ *   loss[n] = sum over the images of body n, in ascending image index, of (w_in A_i + w_out B_i), accumulated in float64,
+ *     output float32.  g_vertices[n,j,:] = the pull-back of both terms through the projection (du/dp = (f/pz) [1, 0, -px/pz],
+ *     dv/dp likewise, then R^T), summed in float64 over the body's images in ascending order and rounded to float32 once.
+ *     The gradient flows through the vertex positions only: field, contour and winners are constants.
+ *   Determinism: no float atomics; a body's loss and gradient are bit-identical alone, in any batch, at any position and from
+ *     run to run; a body with no images gets loss 0 and an exactly zero gradient.  Term B's many-points-to-one-vertex sum is
+ *     a 64-bit integer accumulation in units of 2^-28 pixel (each point's contribution is rounded to that unit; the sum of
+ *     one vertex in one image must stay below 2^35 pixels in magnitude).
+ *
+ * masks[M,H,W] uint8 dev or host; image_body[M], cam_R[M,3,3], cam_t[M,3], cam_f[M], cam_c[M,2] host.  num_images = 0 clears
+ * the mask set (the other arguments are ignored).  loss[N] dev out; g_vertices[N,Nv,3] dev out or NULL; winner[C] int32 dev
+ * out or NULL (diagnostics: the winner of every kept contour point).
+ * Workspace, kept in the ctx and reused by a second set of the same sizes:
+ *     M H W * 5 + M H * 4 + M * (16 Nv + 8 ceil(Nv / 256) + 92) + 8   bytes   (field 4 H W and a copy of the mask H W per
+ *     image, row offsets, the fixed-point accumulators, term A's partials, tables), each part rounded up to 256 bytes, plus
+ *     C * 8 + ceil-sum(C_i / 512) * 24 bytes for the contour list, the search's chunk table and term B's partials (grows to
+ *     the largest set seen).
+ * MVFIT_E_ARG: sizes out of range, contour_stride < 1, a NULL required pointer, num_bodies outside [1, 65535], an
+ * image_body[i] outside [0, num_bodies) (checked at loss time).  MVFIT_E_STATE: no mask set is present.
+ * MVFIT_E_UNSUPPORTED: more than 2^31 - 1 kept contour points. */
+int mvfit_set_silhouettes(mvfit_ctx* ctx, int num_images, int height, int width, const uint8_t* masks,
+                          const int32_t* image_body, const float* cam_R, const float* cam_t, const float* cam_f,
+                          const float* cam_c, int contour_stride);
+/* field[M,H,W] dev out or NULL, contour_first[M+1] dev out or NULL, contour_xy[C,2] dev out or NULL, num_points host out (C;
+ * known when the set returns, so a caller reads it first and sizes contour_xy). */
+int mvfit_silhouettes_read(mvfit_ctx* ctx, float* field, int32_t* contour_first, int32_t* contour_xy, int32_t* num_points);
+int mvfit_silhouette_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float w_in, float w_out, float sigma,
+                          float* loss, float* g_vertices, int32_t* winner);
+
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear
  * triangulation of the 17 keypoints from V calibrated views, batched over B frames.
  *   keypoints[B,V,17,3] float32 dev (u, v, confidence) ; intris[V,3,3], extris[V,4,4] float64 dev (the reference

@@ -27,6 +27,7 @@
 #include "closure_device.h"
 #include "fit_plan.h"
 #include "model_prep.h"
+#include "silhouette.h"
 
 namespace mvfit {
 
@@ -826,6 +827,8 @@ struct mvfit_ctx {
     int32_t* d_obst_tab = nullptr;     // [B] SceneBody rows
     float4* d_obst_box = nullptr;      // [B] (centre, scale)
     float* d_obst_phi = nullptr;       // [B][G^3]
+    // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
+    SilState sil;
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -1103,6 +1106,7 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     if (c->d_scn_ws) hipFree(c->d_scn_ws);
     if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
     if (c->d_assoc_ws) hipFree(c->d_assoc_ws);
+    sil_free(c->sil);
     for (void* p : c->allocs) if (p) hipFree(p);
     if (c->h_done) hipHostFree(c->h_done);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
@@ -2271,6 +2275,49 @@ extern "C" int mvfit_scene_obstacles_read(mvfit_ctx* c, float* phi, float* boxes
     if (phi) HIP_OK(c, hipMemcpyAsync(phi, c->d_obst_phi, (size_t)c->B * nvox * 4, hipMemcpyDeviceToDevice, c->stream));
     if (boxes) HIP_OK(c, hipMemcpyAsync(boxes, c->d_obst_box, (size_t)c->B * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
+}
+
+// The silhouette term (silhouette.hip): the mask set is prepared once, the loss calls sample it.
+extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, int width, const uint8_t* masks,
+                                     const int32_t* image_body, const float* cam_R, const float* cam_t, const float* cam_f,
+                                     const float* cam_c, int contour_stride) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (num_images == 0) {                                   // clear: the work areas stay for a next set of the same size
+        c->sil.on = false;
+        return MVFIT_OK;
+    }
+    if (num_images < 0 || num_images > 65535 || height < 2 || height > 8192 || width < 2 || width > 8192)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: sizes out of range (num_images=%d in [0, 65535], height=%d and "
+                    "width=%d in [2, 8192])", num_images, height, width);
+    if (contour_stride < 1) return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: contour_stride %d < 1", contour_stride);
+    if (!masks || !image_body || !cam_R || !cam_t || !cam_f || !cam_c)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: null %s", !masks ? "masks" : !image_body ? "image_body" : !cam_R ? "cam_R" :
+                    !cam_t ? "cam_t" : !cam_f ? "cam_f" : "cam_c");
+    return sil_set(c->sil, c->nv, num_images, height, width, masks, image_body, cam_R, cam_t, cam_f, cam_c, contour_stride,
+                   c->stream, c->err);
+}
+
+extern "C" int mvfit_silhouettes_read(mvfit_ctx* c, float* field, int32_t* contour_first, int32_t* contour_xy, int32_t* num_points) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_silhouettes_read: no mask set is present");
+    HIP_OK(c, hipSetDevice(c->device));
+    if (num_points) *num_points = c->sil.C;
+    return sil_read(c->sil, field, contour_first, contour_xy, c->stream, c->err);
+}
+
+extern "C" int mvfit_silhouette_loss(mvfit_ctx* c, const float* vertices, int num_bodies, float w_in, float w_out, float sigma,
+                                     float* loss, float* g_vertices, int32_t* winner) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_silhouette_loss: no mask set is present (mvfit_set_silhouettes)");
+    if (!vertices || !loss) return fail(c, MVFIT_E_ARG, "mvfit_silhouette_loss: null %s", !vertices ? "vertices" : "loss");
+    if (num_bodies < 1 || num_bodies > 65535)
+        return fail(c, MVFIT_E_ARG, "mvfit_silhouette_loss: num_bodies %d outside [1, 65535]", num_bodies);
+    if (c->sil.body_min < 0 || c->sil.body_max >= num_bodies)
+        return fail(c, MVFIT_E_ARG, "mvfit_silhouette_loss: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min,
+                    c->sil.body_max, num_bodies);
+    HIP_OK(c, hipSetDevice(c->device));
+    return sil_loss(c->sil, vertices, num_bodies, w_in, w_out, sigma, loss, g_vertices, winner, c->stream, c->err);
 }
 
 extern "C" int mvfit_triangulate(mvfit_ctx* c, int B, int V, const float* keypoints, const double* intris, const double* extris,

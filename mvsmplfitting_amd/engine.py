@@ -420,6 +420,69 @@ class MvFit:
         self._check(self._lib.mvfit_set_scene_obstacles(self._ctx, None, None, 0, 0, 0.0, 0.0))
         self._obstacles = False
 
+    # ------------------------------------------------------------------ silhouette term (include/mvfit.h:mvfit_set_silhouettes)
+    def set_silhouettes(self, masks, image_body, cams, contour_stride=1):
+        """Prepare a mask set (include/mvfit.h:mvfit_set_silhouettes): masks uint8 [M,H,W] (tensor or array, non-zero = on),
+        image_body[M] = the body every image shows, cams = (R[M,3,3], t[M,3], f[M], c[M,2]) per image.  Distance fields and
+        contour lists stay in the engine until clear_silhouettes() or the next set."""
+        if isinstance(masks, torch.Tensor):
+            m = masks.to(device=self.device, dtype=torch.uint8).contiguous()
+        else:
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(masks), dtype=np.uint8)).to(self.device)
+        if m.dim() != 3:
+            raise MvFitError('masks must be [M, H, W], got %r' % (tuple(m.shape),))
+        M, H, W = (int(n) for n in m.shape)
+        body = _i32(np.asarray(image_body).reshape(-1))
+        R, t, f, c = (_f32(a) for a in cams)
+        if body.size != M or R.shape != (M, 3, 3) or t.shape != (M, 3) or f.reshape(-1).shape != (M,) or c.shape != (M, 2):
+            raise MvFitError('image_body and cams need one entry per image (%d)' % M)
+        if M == 0:
+            return self.clear_silhouettes()
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.mvfit_set_silhouettes(
+            self._ctx, M, H, W, m.data_ptr(), body.ctypes.data_as(_lib._ip), R.ctypes.data_as(fp), t.ctypes.data_as(fp),
+            f.ctypes.data_as(fp), c.ctypes.data_as(fp), int(contour_stride)))
+        self._sil_shape = (M, H, W)
+
+    def clear_silhouettes(self):
+        """Remove the mask set of set_silhouettes."""
+        self._check(self._lib.mvfit_set_silhouettes(self._ctx, 0, 0, 0, None, None, None, None, None, None, 1))
+
+    def silhouettes(self):
+        """Diagnostics: (field [M,H,W] float32, contour_first [M+1] int32, contour_xy [C,2] int32) of the mask set."""
+        n = C.c_int32(0)
+        self._check(self._lib.mvfit_silhouettes_read(self._ctx, None, None, None, C.byref(n)))
+        M, H, W = self._sil_shape
+        field = torch.empty(M, H, W, device=self.device)
+        first = torch.empty(M + 1, dtype=torch.int32, device=self.device)
+        xy = torch.empty(int(n.value), 2, dtype=torch.int32, device=self.device)
+        self._check(self._lib.mvfit_silhouettes_read(self._ctx, field.data_ptr(), first.data_ptr(),
+                                                     xy.data_ptr() if n.value else None, C.byref(n)))
+        return field, first, xy
+
+    def silhouette_loss(self, vertices, w_in=1.0, w_out=1.0, sigma=0.0, need_grad=True, return_winner=False):
+        """The silhouette loss of the mask set at vertices[N,Nv,3], translation included (include/mvfit.h:
+        mvfit_silhouette_loss): w_in weighs the body-inside-mask term, w_out the mask-covered-by-body term, sigma > 0 makes
+        both robust.  Returns (loss[N], g_vertices[N,Nv,3] or None) and, with return_winner, the int32 [C] nearest projected
+        vertex of every kept contour point (-1: none)."""
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [N, %d, 3], got %r' % (self.nv, tuple(v.shape)))
+        N = int(v.shape[0])
+        loss = torch.empty(N, device=self.device)
+        g = torch.empty_like(v) if need_grad else None
+        win = None
+        if return_winner:
+            n = C.c_int32(0)
+            self._check(self._lib.mvfit_silhouettes_read(self._ctx, None, None, None, C.byref(n)))
+            win = torch.empty(max(int(n.value), 1), dtype=torch.int32, device=self.device)
+        self._check(self._lib.mvfit_silhouette_loss(self._ctx, v.data_ptr(), N, float(w_in), float(w_out), float(sigma),
+                                                    loss.data_ptr(), g.data_ptr() if need_grad else None,
+                                                    win.data_ptr() if return_winner else None))
+        if return_winner:
+            return loss, g, win[:int(n.value)]
+        return loss, g
+
     def set_sdf(self, faces, num_faces=1, grid_size=128):
         """Configure the interpenetration term (include/mvfit.h:mvfit_set_sdf).  ``faces`` [F,3]; ``num_faces``
         = how many leading triangles the op sees: 1 reproduces the reference's call site

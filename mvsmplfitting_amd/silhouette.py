@@ -1,0 +1,201 @@
+"""The silhouette loss against per-view person masks as a differentiable PyTorch module, and a small driver that refines
+shape and scale with it (include/mvfit.h:mvfit_set_silhouettes / mvfit_silhouette_loss; csrc/silhouette.hip).
+
+Keypoints fix bone lengths and pose and say almost nothing about girth; masks do.  The loss has two terms per image: the
+projected vertices must lie inside the mask (a bilinear sample of the mask's exact distance field) and the mask's contour
+must be covered by the body (squared distance of every contour pixel to the nearest projected vertex).  It composes with the
+differentiable body model:
+
+    layer = BodyLayer(model_arrays)
+    sil = SilhouetteLoss(engine=layer.engine, masks=masks, image_body=image_body, cams=(R, t, f, c))
+    out = layer(betas, global_orient, body_pose, transl=transl, scale=scale)
+    loss = sil(out.vertices)              # [N], one value per body
+    loss.sum().backward()                 # -> betas.grad, ..., scale.grad
+
+One autograd node maps the vertices to the loss; the forward call already computes the gradient and the node keeps it,
+backward scales it by each body's incoming gradient.  Once differentiable: there is no double backward.
+
+Not built here: reading mask files, fit_folder(silhouettes=...), the term inside the fit's own rounds, multi-person instance
+masks, visibility or occlusion between bodies, point-to-edge distances (the contour term measures the distance to the
+nearest projected *vertex*; its floor is about half the projected vertex spacing).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from .layer import _WIDTHS
+
+
+class SilhouetteFunction(torch.autograd.Function):
+    """v[N,Nv,3] float32 (translation included) -> loss[N] on module's engine; backward = grad_out[body] * g_vertices."""
+
+    @staticmethod
+    def forward(ctx, v, module):
+        loss, g = module.engine.silhouette_loss(v.detach(), w_in=module.w_in, w_out=module.w_out, sigma=module.sigma,
+                                                need_grad=True)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        g, = ctx.saved_tensors
+        return grad_out.to(g.dtype)[:, None, None] * g, None
+
+
+class SilhouetteLoss(torch.nn.Module):
+    """masks uint8 [M,H,W] (non-zero = person), image_body[M] = which body of the batch every image shows, cams =
+    (R[M,3,3], t[M,3], f[M], c[M,2]) per image.  engine: an object with MvFit's set_silhouettes / silhouette_loss and
+    device (a BodyLayer's engine, or a stand-in in tests); without one the module builds an MvFit of its own on ``model``.
+    The mask set lives in the engine: one SilhouetteLoss per engine at a time (``rebind()`` sets this module's masks again
+    after another one used the engine).
+
+    Pass cropped or downscaled masks, with f and c scaled to match, when full-resolution fields (5 bytes per pixel and
+    image) do not fit."""
+
+    def __init__(self, engine=None, masks=None, image_body=None, cams=None, contour_stride=1, w_in=1.0, w_out=1.0, sigma=0.0,
+                 model: dict | None = None, device: int = 0):
+        super().__init__()
+        if engine is None:
+            if model is None:
+                raise ValueError('SilhouetteLoss needs engine= (an MvFit, e.g. BodyLayer(...).engine) or model=')
+            from .engine import MvFit
+            engine = MvFit(model, device=device)
+        if masks is None or image_body is None or cams is None:
+            raise ValueError('SilhouetteLoss needs masks=, image_body= and cams=')
+        self.engine = engine
+        self.w_in, self.w_out, self.sigma = float(w_in), float(w_out), float(sigma)
+        self.contour_stride = int(contour_stride)
+        self._set = (masks, np.asarray(image_body).reshape(-1).copy(), tuple(cams))
+        self.rebind()
+
+    def rebind(self):
+        masks, body, cams = self._set
+        self.engine.set_silhouettes(masks, body, cams, contour_stride=self.contour_stride)
+
+    def forward(self, vertices):
+        """vertices[N,Nv,3] with the translation included (what BodyLayer returns with transl=) -> loss[N]."""
+        vertices = torch.as_tensor(vertices)
+        if vertices.dim() != 3 or vertices.shape[2] != 3:
+            raise ValueError('vertices must be [N, Nv, 3], got %r' % (tuple(vertices.shape),))
+        v = vertices.to(device=self.engine.device, dtype=torch.float32)
+        return SilhouetteFunction.apply(v, self)
+
+
+def keypoint_term(joints, cams_fit, gt_xy, w_conf, data_weight, rho):
+    """The closure's 2-D data term on joints[B,17,3], in torch: data_weight^2 * sum conf^2 * rho^2 r^2 / (r^2 + rho^2) per
+    residual coordinate r over views, keypoints and (u, v) -> [B].  cams_fit = (R[V,3,3] | [B,V,3,3], t, f, c)."""
+    dev, dt = joints.device, joints.dtype
+    R, t, f, c = (torch.as_tensor(np.asarray(a, np.float32) if not isinstance(a, torch.Tensor) else a).to(device=dev, dtype=dt)
+                  for a in cams_fit)
+    if R.dim() == 3:
+        R, t, f, c = R[None], t[None], f[None], c[None]
+    gt = torch.as_tensor(gt_xy).to(device=dev, dtype=dt)
+    w2 = torch.as_tensor(w_conf).to(device=dev, dtype=dt)[..., None] ** 2
+    p = torch.einsum('bvac,bkc->bvka', R.expand(joints.shape[0], -1, -1, -1), joints) + t[:, :, None, :]
+    uv = f[:, :, None, None] * p[..., :2] / p[..., 2:3] + c[:, :, None, :]
+    r2 = (gt - uv) ** 2
+    rho2 = float(rho) ** 2
+    return (w2 * (rho2 * r2 / (r2 + rho2))).sum(dim=(1, 2, 3)) * float(data_weight) ** 2
+
+
+def refine_shape(layer, params, masks, image_body, cams, *, free=('betas', 'scale'), share=None, weight, sigma, shape_weight,
+                 keypoints=None, max_iter=30, contour_stride=1, w_in=1.0, w_out=1.0):
+    """Refine the result of a keypoint fit against masks.
+
+    params[B,118] (flat parameter rows, include/mvfit.h); masks / image_body / cams as SilhouetteLoss takes them (image_body
+    indexes the rows of params).  free: the blocks that move ('betas', 'global_orient', 'body_pose', 'transl', 'scale').
+    share: an integer group id per problem (None: every problem its own group); the problems of a group optimise ONE betas
+    and ONE scale - one shape per person over all their frames - starting from the group's first row; the other free blocks
+    stay per problem.  Per group the objective is
+
+        weight * sum_b silhouette_b + shape_weight^2 |betas|^2 [+ sum_b keypoint_term_b]
+
+    (the shape prior in the reference's form, once per group; keypoints = (cams_fit, gt_xy, w_conf, data_weight, rho) adds the
+    closure's 2-D data term on the layer's joints).  All groups are minimised together by one
+    torch.optim.LBFGS(line_search_fn='strong_wolfe') on the sum; a group keeps its result only if its own objective
+    dropped, otherwise its rows come back exactly as they were given.
+
+    Returns (params_out[B,118], report) with report = dict(groups, before, after, accepted, silhouette_before,
+    silhouette_after: one entry per group in ascending group id; iterations: the optimiser's)."""
+    names = [n for n, _ in _WIDTHS]
+    free = tuple(free)
+    for n in free:
+        if n not in names or n == 'pose_embedding':
+            raise ValueError('free block %r: one of betas, global_orient, body_pose, transl, scale' % (n,))
+    dev = layer.engine.device
+    x0 = torch.as_tensor(params).detach().to(device=dev, dtype=torch.float32).clone()
+    B = int(x0.shape[0])
+    if x0.dim() != 2 or x0.shape[1] != sum(w for _, w in _WIDTHS):
+        raise ValueError('params must be [B, 118], got %r' % (tuple(x0.shape),))
+    ids = np.arange(B) if share is None else np.asarray(share).reshape(-1)
+    if ids.size != B:
+        raise ValueError('share needs one group id per problem (%d)' % B)
+    groups, inverse = np.unique(ids, return_inverse=True)
+    G = len(groups)
+    gi = torch.as_tensor(inverse.reshape(-1), device=dev, dtype=torch.long)
+    first_row = torch.as_tensor(np.array([int(np.flatnonzero(inverse == g)[0]) for g in range(G)]), device=dev, dtype=torch.long)
+    offs, o = {}, 0
+    for n, w in _WIDTHS:
+        offs[n] = (o, o + w)
+        o += w
+    shared = ('betas', 'scale')
+    var = {}
+    for n in free:
+        a, b = offs[n]
+        init = x0[first_row, a:b] if n in shared else x0[:, a:b]
+        var[n] = init.clone().requires_grad_(True)
+
+    def rows(values):
+        """x[B,118] with the free blocks taken from values (shared ones expanded over their group)."""
+        parts = []
+        for n, _ in _WIDTHS:
+            a, b = offs[n]
+            if n in values:
+                parts.append(values[n][gi] if n in shared else values[n])
+            else:
+                parts.append(x0[:, a:b])
+        return parts
+
+    sil = SilhouetteLoss(engine=layer.engine, masks=masks, image_body=image_body, cams=cams, contour_stride=contour_stride,
+                         w_in=w_in, w_out=w_out, sigma=sigma)
+    sw2 = float(shape_weight) ** 2
+
+    def objective(parts):
+        p = dict(zip(names, parts))
+        out = layer(p['betas'], p['global_orient'], p['body_pose'], transl=p['transl'], scale=p['scale'])
+        s = sil(out.vertices)
+        per_body = float(weight) * s
+        if keypoints is not None:
+            cams_fit, gt_xy, w_conf, data_weight, rho = keypoints
+            per_body = per_body + keypoint_term(out.joints, cams_fit, gt_xy, w_conf, data_weight, rho)
+        zero = torch.zeros(G, device=dev, dtype=per_body.dtype)
+        J = zero.index_add(0, gi, per_body) + sw2 * (p['betas'][first_row] ** 2).sum(dim=1)
+        return J, zero.index_add(0, gi, s.detach())
+
+    try:
+        with torch.no_grad():
+            before, sil_before = objective([x0[:, a:b] for a, b in (offs[n] for n in names)])
+        opt = torch.optim.LBFGS(list(var.values()), max_iter=int(max_iter), line_search_fn='strong_wolfe')
+
+        def closure():
+            opt.zero_grad()
+            J, _ = objective(rows(var))
+            total = J.sum()
+            total.backward()
+            return total
+        if var:
+            opt.step(closure)
+        with torch.no_grad():
+            x1 = torch.cat(rows({n: v.detach() for n, v in var.items()}), dim=1)
+            after, sil_after = objective([x1[:, a:b] for a, b in (offs[n] for n in names)])
+    finally:
+        layer.engine.clear_silhouettes()
+    accepted = after < before
+    out = torch.where(accepted[gi][:, None], x1, x0)
+    n_iter = int(opt.state[opt._params[0]].get('n_iter', 0)) if var else 0
+    report = dict(groups=groups.tolist(), before=before.tolist(), after=after.tolist(), accepted=accepted.tolist(),
+                  silhouette_before=sil_before.tolist(), silhouette_after=sil_after.tolist(), iterations=n_iter)
+    return out, report
