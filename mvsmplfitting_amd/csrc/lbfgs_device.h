@@ -105,7 +105,10 @@ struct LbHist {
     //   rinv    = R^-1, R_ij = s_i . y_j for pair i not newer than pair j (upper triangular in age order), stored by SLOT in
     //             packed symmetric form: the entry of the unordered slot pair {r, c} lives at tri(max) + min and holds
     //             (R^-1)_(older, newer).  Exactly one of the two orders is live for any two live pairs, whatever the ring
-    //             head: neither accepting a pair (its column overwrites the evicted pair's star) nor evicting one moves data.
+    //             head: neither accepting a pair nor evicting one moves data.  The new pair's column goes to the entries
+    //             {live slot, new slot}: at history == LB_HIST the new slot is the evicted pair's and the column overwrites
+    //             its star; at a smaller history it is a slot that has been dead for LB_HIST - history pairs, and the evicted
+    //             pair's entries stay behind unread (every product masks by age) until the ring comes round to that slot.
     T* ys = nullptr;
     T* rinv = nullptr;
     int ld = LB_D;  // row stride of dirs / stps
@@ -448,8 +451,9 @@ __device__ __forceinline__ void lb_cmp_rowdots(const LbHist<T>& Hh, LbWork<T>& W
 // waves and met in LDS: the same bits.)  The lane with q = 0 finishes the row:
 //   FWD  w = sum_{a <= b < nE} Rinv(a, b) p_b and, when a pair has just been accepted (slot t, age n - 1), the new column of
 //        R^-1: Rinv(a, t) = -ro_t sum_b Rinv(a, b) u_b (u = S y_new), w += Rinv(a, t) p_t; row t itself is (ro_t p_t, ro_t).
-//        Nobody reads column t or row t in this phase (its age is outside nE), and the packed entry {slot(a), t} is the one
-//        the evicted pair's star occupied: written here, read from the next phase on.  Ages n .. 99 are the dead slots: 0.
+//        Nobody reads column t or row t in this phase (its age is outside nE), and the packed entry {slot(a), t} belongs to a
+//        dead slot (the evicted pair's at history == LB_HIST): written here, read from the next phase on.  Ages n .. 99 are
+//        the dead slots: 0.
 //   BWD  c = sum_{b <= a} Rinv(b, a) z_b.
 // Loads are issued four columns at a time before their first use.
 template <typename T, int NT, bool FWD>

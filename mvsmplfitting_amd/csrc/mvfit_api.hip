@@ -1472,9 +1472,16 @@ static LbOpts lb_opts(const mvfit_lbfgs_opts& o, int num_stages) {
     return O;
 }
 
+// What every entry that runs the optimiser requires of them.  The ring has LB_HIST slots and a new pair goes to slot
+// (hist_head + hist_len - 1) % LB_HIST: history <= 0 makes that slot negative (hist_len stays 0), history > LB_HIST lets
+// hist_len grow past the ring.
+static_assert(MVFIT_HISTORY == LB_HIST, "mvfit_lbfgs_opts::history is checked against the size of the device ring");
+static bool lb_opts_ok(const mvfit_lbfgs_opts& o) {
+    return o.max_iter > 0 && o.history > 0 && o.history <= MVFIT_HISTORY && o.maxiters > 0;
+}
+
 static int make_opts(mvfit_ctx* c, const mvfit_lbfgs_opts* o, uint32_t flags, LbOpts& O) {
-    if (o->max_iter <= 0 || o->history <= 0 || o->history > MVFIT_HISTORY || o->maxiters <= 0 || o->num_stages <= 0 ||
-        o->num_stages > MVFIT_MAX_STAGES)
+    if (!lb_opts_ok(*o) || o->num_stages <= 0 || o->num_stages > MVFIT_MAX_STAGES)
         return fail(c, MVFIT_E_ARG, "bad lbfgs options");
     O = lb_opts(*o, o->num_stages);
     O.reuse_outer = (flags & MVFIT_F_REUSE_OUTER_VALUE) ? 1 : 0;
@@ -2675,6 +2682,7 @@ extern "C" int mvfit_profile_read(mvfit_ctx* c, double* vp_ms, int* launches, do
 extern "C" int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs, int nseg, const mvfit_lbfgs_opts* o,
                                double* x_inout, double* trace, int max_trace, int* n_closure, double* final_loss) {
     if (!o || !x_inout || D <= 1 || D > LB_D || nseg < 1 || nseg > 8 || !segs) return MVFIT_E_ARG;
+    if (!lb_opts_ok(*o)) return MVFIT_E_ARG;
     if (hipSetDevice(device) != hipSuccess) return MVFIT_E_HIP;
     LbOpts O = lb_opts(*o, 1);
     O.nseg = nseg;

@@ -51,6 +51,7 @@ class LbfgsOracle:
         self.func_evals = 0
         self.d = self.t = self.H = self.prev_g = self.prev_loss = None
         self.dirs, self.stps, self.ro = [], [], []
+        self.n_pairs = 0               # accepted (s, y) pairs so far, evicted ones included
         self.last_grad = None          # .grad left by the last closure call (gtol test reads it)
         self.trace = []                # (x_trial, loss) of every closure call
         self.exits = []                # why each step() ended: 'grad0', 'gtd' (:379-380, with n_iter), 'ls' (:419-434)
@@ -62,6 +63,10 @@ class LbfgsOracle:
         self.func_evals += 1
         self.trace.append((x.copy(), f))
         return f, self.last_grad.copy()
+
+    def _evict(self):
+        """Drop the oldest pair (lbfgs_ls.py:325-329)."""
+        self.dirs.pop(0); self.stps.pop(0); self.ro.pop(0)
 
     def _strong_wolfe(self, t, d, f, g, gtd, c1=1e-4, c2=0.9, max_ls=25):
         """lbfgs_ls.py:39-167; obj_func(x,t,d) evaluates at x + t d (lbfgs_ls.py:249-254)."""
@@ -157,8 +162,9 @@ class LbfgsOracle:
                 ys = float(y @ s)
                 if ys > 1e-10:
                     if len(self.dirs) == self.history:
-                        self.dirs.pop(0); self.stps.pop(0); self.ro.pop(0)
+                        self._evict()
                     self.dirs.append(y); self.stps.append(s); self.ro.append(1.0 / ys)
+                    self.n_pairs += 1
                     H = ys / float(y @ y)
                 k = len(self.dirs)
                 al = [0.0] * k
@@ -245,7 +251,7 @@ def kat_objective(kind: str, D: int, seed: int = 0):
             a = x[1:] - x[:-1] ** 2
             b = 1.0 - x[:-1]
             f = float((100.0 * a * a + b * b).sum())
-            g = np.zeros(D)
+            g = np.zeros_like(x)
             g[:-1] += -400.0 * a * x[:-1] - 2.0 * b
             g[1:] += 200.0 * a
             return f, g
