@@ -58,8 +58,19 @@ struct LbOpts {
     // (lbfgs_ls.py:279-283) at the point the previous step() of the same stage ended on, whose loss and gradient the
     // optimiser still holds - the accepted line-search point (:393-399).  With the flag the device feeds those back
     // instead of evaluating again: same iterates, same eval accounting, 8-10 % fewer closure evaluations.
-    int reuse_outer, pad_;
+    int reuse_outer;
+    int dir_general;     // -DMVFIT_DEBUG_HOOKS builds only: every compact direction takes the general (ring) form of its
+                         // triangular products.  Always 0 otherwise, and no other build reads it.
 };
+
+// hooks build: the environment switch the host read (uniform); every other build: false at compile time
+__device__ __forceinline__ bool lb_dir_general(const LbOpts& O) {
+#ifdef MVFIT_DEBUG_HOOKS
+    return __builtin_amdgcn_readfirstlane(O.dir_general) != 0;
+#else
+    return false;
+#endif
+}
 
 // Per-problem scalar state (lives in global memory between launches).
 struct LbState {
@@ -525,6 +536,117 @@ __device__ __forceinline__ void lb_cmp_tri(const LbHist<T>& Hh, LbWork<T>& W, in
     }
 }
 
+// The same two products for a window that does not wrap round the ring (head + n <= LB_HIST: always while a stage has accepted
+// fewer than LB_HIST pairs, head stays 0 until the first eviction).  Then slot = head + age is monotone and everything
+// lb_cmp_tri recomputes per column is linear or quadratic in the column index:
+//   BWD  (b <= a)  packed index = tri(sa) + head + b                     : a running base plus constant offsets
+//   FWD  (b >= a)  packed index = tri(head + b) + sa, and with S the slot of a batch's first column
+//                  tri(S + 4 j) + sa = (tri(S) + sa) + j (4 S) + (8 j^2 + 2 j): one add per column and a constant offset;
+//                  the next batch (LB_TRI_B columns on, d = 4 LB_TRI_B slots) starts at + d S + d (d + 1) / 2
+//   the vector elements x / u at head + b: base plus constant offsets
+// - no multiply, no ring arithmetic and no max / min of slots in the column loop.  Same items, same lanes, same FMAs in the
+// same order as the general form: lane q of row a takes the live columns b = q (mod 4) in ascending order, starting at its
+// own first one, LB_TRI_B columns per batch with every load of a batch ahead of its first use - and 4 in the last batch
+// where that covers the rest of the wave's longest lane (the typical 42-pair window: 11 columns per lane = 8 + 4 column
+// steps instead of 16; measured, profiles/tri_forms_ab.md); the row total and what the finishing lane writes are the
+// general form's, word for word.
+// Masked columns: a column of the general form's uniform range that is not this lane's (b < a in front, b >= nE behind) is
+// fma(0, 0, s) there.  The sums start at +0 and a sum is -0 only if both addends are: s is never -0, fma(0, 0, s) == s
+// bit for bit, and such a column is NOT EXECUTED here where a whole batch of a lane is masked (a lane that has run out of
+// columns sits the wave's remaining batches out); the masked columns of a lane's last batch still are fma(0, 0, s), both
+// operands zeroed.  Rows a >= n
+// (dead: their sums are discarded by the finishing lane in both forms) run as aliases of the last live row, so that every
+// address stays inside the arrays: a lane reads at most LB_TRI_B - 1 columns past its last live one - x / u below slot
+// LB_HIST + 4 (LB_TRI_B - 1) <= 128, the packed index clamped to the array.
+constexpr int LB_TRI_B = 8;        // 64-pair window: 2 batches for the longest row (the general form needs 3 at 48 pairs)
+static_assert(LB_HIST + 4 * (LB_TRI_B - 1) <= 128, "masked columns of a last batch stay inside the work vectors");
+
+template <typename T, int NT, bool FWD>
+__device__ __forceinline__ void lb_cmp_tri_nowrap(const LbHist<T>& Hh, LbWork<T>& W, int tid) {
+    constexpr int B = LB_TRI_B;
+    const int n = W.n, head = W.head;
+    const int t = FWD ? W.ins_slot : -1;
+    const int nE = (FWD && t >= 0) ? n - 1 : n;            // live columns of this product (the inserted pair is the newest)
+    const T* xv = FWD ? W.bvec : W.zv;
+    // the finishing lane's own operands of the new column: they depend on nothing below
+    T rot = (T)0, pt = (T)0;
+    if (FWD) { const int tc = max(t, 0); rot = Hh.ro[tc]; pt = W.bvec[tc]; }
+    for (int r = LB_HIST + tid; r < 128; r += NT) (FWD ? W.alpha : W.cvec)[r] = (T)0;      // padding slots
+    for (int item = tid; item < 4 * 128; item += NT) {
+        const int a = item >> 2, q = item & 3;
+        const int a0 = __builtin_amdgcn_readfirstlane(a);                   // the wave's first row
+        if (a0 >= LB_HIST) break;                                           // uniform: nothing but padding from here on
+        const bool live = a < n;
+        int sa = head + min(a, LB_HIST - 1);                                // (dead ages are the slots behind the window, round the ring)
+        sa = sa >= LB_HIST ? sa - LB_HIST : sa;
+        T s0 = (T)0, s1 = (T)0;
+        if (a0 < n) {                                                       // uniform
+            const int ar = min(a, n - 1);                                   // dead rows: alias of the last live row
+            const int b0 = FWD ? ar + ((q - ar) & 3) : q;                   // this lane's first column: the smallest b >= a, resp. 0, with b = q (mod 4)
+            const int cnt = FWD ? (nE - b0 + 3) >> 2 : (ar - q + 4) >> 2;   // its live columns b0, b0 + 4, ... (<= 0: none)
+            const T* xp = xv + head + b0;
+            const T* up = W.gnew + head + b0;
+            const int S = head + b0;
+            int R = FWD ? ((S * (S + 1)) >> 1) + head + ar : lb_tri(head + ar, head + q);      // packed index of the first column
+            int S4 = 4 * S;
+            // the wave's longest lane: the last batch is a short one (4 columns) where that covers it
+            const int armax = min(a0 + 15, n - 1);
+            const int trips = __builtin_amdgcn_readfirstlane(FWD ? (nE - a0 + 3) >> 2 : (armax + 4) >> 2);
+            auto batch = [&](auto bn, int rem) {
+                constexpr int BN = decltype(bn)::value;
+                T m[BN], x[BN], u[BN];
+                int A = R;
+#pragma unroll
+                for (int j = 0; j < BN; ++j) {
+                    const int cj = FWD ? 8 * j * j + 2 * j : 4 * j;
+                    const T* mp = Hh.rinv + min(A, LB_RPACK - 1 - cj);
+                    m[j] = mp[cj];
+                    x[j] = xp[4 * j];
+                    if (FWD) { u[j] = up[4 * j]; A += S4; }
+                }
+#pragma unroll
+                for (int j = 0; j < BN; ++j) {
+                    const bool use = j < rem;
+                    const T mk = use ? m[j] : (T)0;
+                    s0 = fma(mk, use ? x[j] : (T)0, s0);
+                    if (FWD) s1 = fma(mk, use ? u[j] : (T)0, s1);
+                }
+                xp += 4 * BN; up += 4 * BN;
+                if (FWD) { R += BN * S4 + (4 * BN) * (4 * BN + 1) / 2; S4 += 16 * BN; }
+                else R += 4 * BN;
+            };
+            for (int k0 = 0; k0 < trips;) {
+                const int rem = cnt - k0;
+                if (trips - k0 > 4) { if (rem > 0) batch(std::integral_constant<int, B>{}, rem); k0 += B; }
+                else { if (rem > 0) batch(std::integral_constant<int, 4>{}, rem); k0 += 4; }
+            }
+            s0 = ((dpp_mov<0x00>(s0) + dpp_mov<0x55>(s0)) + dpp_mov<0xAA>(s0)) + dpp_mov<0xFF>(s0);
+            if (FWD) s1 = ((dpp_mov<0x00>(s1) + dpp_mov<0x55>(s1)) + dpp_mov<0xAA>(s1)) + dpp_mov<0xFF>(s1);
+        }
+        if (q == 0 && a < LB_HIST) {
+            if (FWD) {
+                T wr = (T)0;
+                if (live) {
+                    if (sa == t) {
+                        wr = rot * pt;
+                        Hh.rinv[lb_tri(t, t)] = rot;
+                    } else {
+                        wr = s0;
+                        if (t >= 0) {
+                            const T cr = -s1 * rot;
+                            Hh.rinv[lb_tri(sa, t)] = cr;
+                            wr = fma(cr, pt, wr);
+                        }
+                    }
+                }
+                W.alpha[sa] = wr;
+            } else {
+                W.cvec[sa] = live ? s0 : (T)0;
+            }
+        }
+    }
+}
+
 // sum_j coef[j] rows_j (a D-vector): 32 lanes per row (4-element chunks), NT / 32 rows per pass, halves of a wave
 // combined by v_permlane32_swap, per-wave partials in W.part (the caller sums them after a barrier)
 template <typename T, int NT>
@@ -560,15 +682,19 @@ __device__ __forceinline__ void lb_cmp_matvec(const T* rows, int ld, const T* co
 }
 
 // In: W.qv = -g, W.n / head / ins_slot / Hdiag, history rows, ys, ro incl. the freshly inserted pair.  Out: W.dv.
+// general: take the general form of the triangular products whatever the window (a switch of the hooks build).
 template <typename T, int NT>
-__device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork<T>& W, int tid) {
-    const int t = W.ins_slot, head = W.head, n = W.n;
+__device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork<T>& W, int tid, bool general = false) {
+    // the window does not wrap round the ring: the triangular products take their no-wrap form (workgroup-uniform; a fit may
+    // change form from one call to the next - both read and write the same packed R^-1 and the same work vectors)
+    const bool nowrap = !general && __builtin_amdgcn_readfirstlane(W.head + W.n) <= LB_HIST;
     // ---- p = S^T q (+ u = S^T y_new) ----
     lb_cmp_rowdots<T, NT, true>(Hh, W, tid);
     __syncthreads();
     PH_T(16);
     // ---- w = R^-1 p ; new column of R^-1 ----
-    lb_cmp_tri<T, NT, true>(Hh, W, tid);
+    if (nowrap) lb_cmp_tri_nowrap<T, NT, true>(Hh, W, tid);
+    else lb_cmp_tri<T, NT, true>(Hh, W, tid);
     __syncthreads();
     PH_T(17);
     // ---- t = Y w - q ----
@@ -587,7 +713,8 @@ __device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork
     __syncthreads();
     PH_T(19);
     // ---- a = R^-T z ----
-    lb_cmp_tri<T, NT, false>(Hh, W, tid);
+    if (nowrap) lb_cmp_tri_nowrap<T, NT, false>(Hh, W, tid);
+    else lb_cmp_tri<T, NT, false>(Hh, W, tid);
     __syncthreads();
     PH_T(20);
     // ---- d = S a - gamma t ----

@@ -364,7 +364,7 @@ __device__ __forceinline__ bool fit_round(const DevModel& M, ClosureLds& L, int 
         PH_T(10);
         // the single-launch fit takes the direction in compact form (history and R^-1 in LDS, every phase on all waves);
         // the chained step kernel keeps the two-loop form over its Gram matrices in global memory
-        if constexpr (COMPACT) lb_direction_compact<float, STEP_NT>(H, L.lbW, tid);
+        if constexpr (COMPACT) lb_direction_compact<float, STEP_NT>(H, L.lbW, tid, lb_dir_general(O));
         else lb_direction_block<float, STEP_NT>(H, L.lbW, tid, GL);
         PH_T(11); PH_ADD(15, 1);
     });
@@ -705,7 +705,7 @@ __global__ __launch_bounds__(64) void lbfgs_kat_kernel(int kind, int D, LbOpts O
         for (int e = 0; e < LB_EPL; ++e) gnew[e] = (LB_EPL * lane + e < D) ? gs[LB_EPL * lane + e] : 0.0;
         __syncthreads();
         lbfgs_round<double, 64, false>(&S, &Vm[0], H, W, O, f, gnew, xt, lane, final_loss, [&]() {   // the production round
-            if (compact) lb_direction_compact<double, 64>(H, W, lane);
+            if (compact) lb_direction_compact<double, 64>(H, W, lane, lb_dir_general(O));
             else lb_direction_block<double, 64>(H, W, lane);
         });
         __syncthreads();
@@ -1469,6 +1469,7 @@ static LbOpts lb_opts(const mvfit_lbfgs_opts& o, int num_stages) {
     O.lr = o.lr; O.tol_grad = o.tolerance_grad; O.tol_change = o.tolerance_change; O.ftol = o.ftol; O.gtol = o.gtol;
     O.max_iter = o.max_iter; O.max_eval = o.max_iter * 5 / 4; O.history = o.history; O.maxiters = o.maxiters;
     O.num_stages = num_stages;
+    O.dir_general = debug_hook("MVFIT_DIR_GENERAL") != 0;      // (hooks build only) the general form of the direction's triangular products
     return O;
 }
 

@@ -754,9 +754,10 @@ def pack_params(betas=None, global_orient=None, body_pose=None, transl=None, sca
     return x
 
 
-def lbfgs_kat(kind: int, D_: int, segs, x0, max_trace=80, device=0, **opts):
-    """Run the float64 device L-BFGS on an analytic objective (include/mvfit.h:mvfit_lbfgs_kat)."""
-    lib = _lib.load()
+def lbfgs_kat(kind: int, D_: int, segs, x0, max_trace=80, device=0, library=None, **opts):
+    """Run the float64 device L-BFGS on an analytic objective (include/mvfit.h:mvfit_lbfgs_kat); library: another build
+    of libmvfit."""
+    lib = _lib.load(library)
     o = _lib.LbfgsOpts(opts.get('lr', 1.0), opts.get('max_iter', 30), opts.get('history', 100),
                        opts.get('tolerance_grad', 1e-5), opts.get('tolerance_change', 1e-9),
                        opts.get('maxiters', 30), opts.get('ftol', 1e-9), opts.get('gtol', 1e-9), 1, 0)
