@@ -11,7 +11,7 @@
 //                      AsyncRing); optionally VPoser decoder helpers behind the problems' workgroups
 //   lbfgs_kat_kernel   float64 instantiation of the state machine on analytic objectives
 // Host side: the C ABI; the model's tables are built by model_prep.cpp and uploaded by mvfit_create_ex; how a fit runs is
-// decided by fit_plan.cpp and executed by mvfit_fit.
+// decided by fit_plan.cpp and executed by mvfit_fit; every allocation of a ctx has an owner of dev_mem.h, which does all the freeing.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -26,6 +26,7 @@
 
 #include "closure_device.h"
 #include "fit_plan.h"
+#include "dev_mem.h"
 #include "model_prep.h"
 #include "silhouette.h"
 
@@ -721,114 +722,109 @@ __global__ __launch_bounds__(64) void lbfgs_kat_kernel(int kind, int D, LbOpts O
 // ==================================================================================== host side
 using namespace mvfit;
 
+// device buffers sized by the batch, owned by mvfit_ctx::problem_mem (the SDF term's: ensure_sdf_buffers)
+struct ProblemBufs {
+    float *camR = nullptr, *camt = nullptr, *camf = nullptr, *camc = nullptr, *gt = nullptr, *wc = nullptr;
+    ObsBlock* obs = nullptr;           // [B] packed observations (LDS image block)
+    float* verts = nullptr;            // [B][nv][3] internal vertex buffer
+    float *gt3d = nullptr, *c3d = nullptr;       // staging of mvfit_set_joints3d ([B][17][3], [B][17])
+    SdfBox* sdf_box = nullptr;         // [B]
+    float4* sdf_samp = nullptr;        // [B][nv]
+    void* sdf_entries = nullptr;       // [B][nv] entry list
+    SdfAdj* sdf_adj = nullptr;         // [B]
+    unsigned long long* sdf_boxpart = nullptr;   // [B][ntiles][6] the vertex pass's own per-tile keys of the term's bounding box (single-chunk split kernel)
+};
+
+// frozen obstacles of the scene term (mvfit_set_scene_obstacles): per problem its scene's row, its box and its field, owned
+// by mvfit_ctx::obst_mem.  The buffers keep their addresses while (B, grid) stay the same, so a re-freeze leaves the
+// captured round graph valid.
+struct Obstacles {
+    bool on = false;
+    int grid = 0;
+    float rob = 0.f;
+    int32_t* tab = nullptr;            // [B] SceneBody rows
+    float4* box = nullptr;             // [B] (centre, scale)
+    float* phi = nullptr;              // [B][G^3]
+};
+
 struct mvfit_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
+    // ---- memory: every allocation belongs to one of these owners (dev_mem.h), grouped by lifetime; the structs handed to
+    // ---- kernels (M, Q, P, F, ring) and pb / obst are plain views of it, reset by assignment.  A new buffer is added here only.
+    // model lifetime (mvfit_create_ex .. mvfit_destroy): the model's tables, the renderer's faces, vps_mem
+    DevPool model_mem;
+    // problem lifetime (free_problem_buffers): what mvfit_set_problems and ensure_sdf_buffers allocate; the ring (its done_round
+    // is sized by Bpad) and the obstacles go whenever the problems go, and each may be replaced on its own before that
+    DevPool problem_mem, ring_mem, obst_mem;
+    // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
+    DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
+    DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
+    DevBuf sdf_op_ws;                  // face lists of the stand-alone op (mvfit_sdf), kept between calls of one shape
+    DevBuf vp_log;                     // mvfit_profile: per-round stamps of the resident pass [kVpLogRounds][grid][2]
+    DevBuf render_nrm, render_ws;      // overlay rendering: [B][nv][3] vertex normals of the call; workspace of the largest group seen
+    DevBuf scene_tab;                  // image / instance tables of the last mvfit_render_scene
+    PinnedBuf h_scene_tab[2];          // their staging, two slots used in turn: a slot is rewritten once the copy out of it (two calls back) is done
+    DevBuf vjp_part, vjp_rec;          // mvfit_vertices_backward (vertex_backward.hip): slice partials and one record per problem, grown with the batch
+    DevBuf scn_ws;                     // mvfit_scene_sdf_loss (scene_sdf.hip): tables, boxes, local vertices, fields, face lists and partials of one
+    PinnedBuf h_scn_tab;               // group of scenes, grown to the largest call seen; the pinned staging of the call's tables
+    DevBuf assoc_ws;                   // mvfit_associate_views (associate.hip): ray origins, then rays and linkage matrices of one group of frames
+    DevBuf queue;                      // work queue of a single-launch fit with more problems than rows: next problem to hand out
+    PinnedBuf h_done;                  // 2 slots
+    PinnedBuf h_async_done;            // host word the last finishing problem writes
+    // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
+    SilState sil;
+    // ---- model ----
     DevModel M{};
-    std::vector<void*> allocs;
-    bool upload_failed = false;
+    bool upload_failed = false, alloc_failed = false;
     int nv = 0;
-    // problems
-    DevProblems Q{};
-    int B = 0, Bpad = 0, V = 0;
-    float *d_camR = nullptr, *d_camt = nullptr, *d_camf = nullptr, *d_camc = nullptr, *d_gt = nullptr, *d_wc = nullptr;
-    ObsBlock* d_obs = nullptr;         // [B] packed observations (LDS image block)
-    // per-problem work buffers
-    DevPose P{};
-    float* d_verts = nullptr;          // [B][nv][3] internal vertex buffer
-    FitBuffers F{};
-    int* h_done = nullptr;             // pinned, 2 slots
-    hipEvent_t ev_done[2] = {nullptr, nullptr};
     bool has_vposer = false;
-    bool has_joints3d = false;
-    float *d_gt3d = nullptr, *d_c3d = nullptr;   // staging of mvfit_set_joints3d ([B][17][3], [B][17])
-    // asynchronous full-mode fit: ring of pose operands + the side stream the vertex passes are queued on
-    AsyncRing ring{};
-    hipStream_t pass_stream = nullptr;
-    hipEvent_t ev_batch[4] = {nullptr, nullptr, nullptr, nullptr}, ev_init = nullptr;
-    int* h_async_done = nullptr;       // pinned host word the last finishing problem writes
-    unsigned async_stats[4] = {0, 0, 0, 0};
-    mvfit_options opt{};               // precision / path selectors (include/mvfit.h); the library reads no environment variable
-    int n_cu = 0;                      // compute units of the device (residency of the resident vertex pass)
-    int resident_tpw = 0;              // tiles per workgroup of the resident pass in the last asynchronous fit (0: per-round launches)
-    int* d_queue = nullptr;            // work queue of a single-launch fit with more problems than rows: next problem to hand out
-    int h_queue0 = 0;
-    bool resident_auto_off = false;    // automatic resident_pass: a fit on this ctx timed out waiting - later fits use per-round launches
-    unsigned long long* d_vp_log = nullptr;     // mvfit_profile: per-round stamps of the resident pass [kVpLogRounds][grid][2]
-    size_t vp_log_words = 0;
-    double res_span_ms = 0.0, res_busy_ms = 0.0, res_slowest_ms = 0.0;   // per round: service span / mean workgroup busy time / slowest workgroup (last profiled fit)
-    int res_rounds = 0;
+    int gmm_M = 0;
+    int32_t *d_faces = nullptr, *d_vf_ptr = nullptr, *d_vf_idx = nullptr;    // the model's faces and the vertex -> face CSR (faces in ascending id), when it has faces
+    int num_faces = 0;
     // decoder helpers of the single-launch fit (vposer_service.h): granule memory [requests | answers | 2 counters]
     unsigned long long* vps_mem = nullptr;
     size_t vps_words = 0;
     unsigned vps_stats[3] = {0, 0, 0};     // launches with helpers in the last fit, answers timed out, helpers that gave up
+    // ---- problems and their work buffers ----
+    DevProblems Q{};
+    int B = 0, Bpad = 0, V = 0;
+    ProblemBufs pb;
+    DevPose P{};
+    FitBuffers F{};
+    bool has_joints3d = false;
+    hipEvent_t ev_done[2] = {nullptr, nullptr};
+    // asynchronous full-mode fit: ring of pose operands + the side stream the vertex passes are queued on
+    AsyncRing ring{};
+    hipStream_t pass_stream = nullptr;
+    hipEvent_t ev_batch[4] = {nullptr, nullptr, nullptr, nullptr}, ev_init = nullptr;
+    unsigned async_stats[4] = {0, 0, 0, 0};
+    mvfit_options opt{};               // precision / path selectors (include/mvfit.h); the library reads no environment variable
+    int n_cu = 0;                      // compute units of the device (residency of the resident vertex pass)
+    int resident_tpw = 0;              // tiles per workgroup of the resident pass in the last asynchronous fit (0: per-round launches)
+    int h_queue0 = 0;
+    bool resident_auto_off = false;    // automatic resident_pass: a fit on this ctx timed out waiting - later fits use per-round launches
+    double res_span_ms = 0.0, res_busy_ms = 0.0, res_slowest_ms = 0.0;   // per round: service span / mean workgroup busy time / slowest workgroup (last profiled fit)
+    int res_rounds = 0;
     float* capture_verts = nullptr;    // mvfit_debug_capture_pass: the pass of closure round capture_round writes here
     int capture_round = -1;
     float* trace = nullptr;            // caller's device buffer (mvfit_fit_trace), not owned
     int trace_cap = 0;
-    int gmm_M = 0;
     // full-mode round loop captured as a graph: key = everything baked into the kernel nodes
     hipGraphExec_t round_graph = nullptr;
     std::vector<unsigned char> graph_key;
     int graph_rounds = 0;
-    // SDF interpenetration term (mvfit_set_sdf): faces as the reference's caller hands them to the op
-    int32_t* d_sdf_faces = nullptr;
+    // SDF interpenetration term (mvfit_set_sdf)
     int sdf_num_faces = 0, sdf_grid = 0;
-    SdfBox* d_sdf_box = nullptr;       // [B]
-    float4* d_sdf_samp = nullptr;      // [B][nv]
-    void* d_sdf_entries = nullptr;     // [B][nv] entry list
-    SdfAdj* d_sdf_adj = nullptr;       // [B]
-    unsigned long long* d_sdf_boxpart = nullptr;   // [B][ntiles][6] the vertex pass's own per-tile keys of the term's bounding box (single-chunk split kernel)
-    void* d_sdf_cull = nullptr;        // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces)
-    void* d_sdf_op_ws = nullptr;       // face lists of the stand-alone op (mvfit_sdf), kept between calls of one shape
     int sdf_op_B = 0, sdf_op_F = 0;
     // which path served the last mvfit_sdf / the SDF term of the last fit (mvfit_sdf_info): 0 walk over every face (short
     // list or lists switched off), 1 face lists, 2 walk because the lists' workspace did not fit
     int sdf_op_path = 0, sdf_term_path = 0;
     bool sdf_cull_refused = false;      // the term's workspace did not fit for the current (batch, face list)
-    // overlay rendering (mvfit_render_overlay): the model's faces and the vertex -> face CSR (faces in ascending id), kept
-    // from mvfit_create when the model has faces; the workspace grows to the largest group seen
-    int32_t* d_faces = nullptr;
-    int32_t *d_vf_ptr = nullptr, *d_vf_idx = nullptr;
-    int num_faces = 0;
-    double* d_render_nrm = nullptr;    // [B][nv][3] vertex normals of the call
-    size_t render_nrm_bytes = 0;
-    void* d_render_ws = nullptr;
-    size_t render_ws_size = 0;
-    int32_t* d_scene_tab = nullptr;    // image / instance tables of the last mvfit_render_scene
-    size_t scene_tab_bytes = 0;
-    // their pinned host staging, two slots used in turn: a slot is rewritten once the copy out of it (two calls back) is done
-    int32_t* h_scene_tab[2] = {nullptr, nullptr};
-    size_t h_scene_tab_bytes[2] = {0, 0};
+    Obstacles obst;
     hipEvent_t scene_copied[2] = {nullptr, nullptr};
     int scene_slot = 0;
-    // mvfit_vertices_backward (vertex_backward.hip): slice partials and one record per problem, allocated by its first call,
-    // grown with the batch
-    float* d_vjp_part = nullptr;
-    size_t vjp_part_size = 0;
-    SdfAdj* d_vjp_rec = nullptr;
-    int vjp_rec_n = 0;
-    // mvfit_scene_sdf_loss (scene_sdf.hip): tables, boxes, local vertices, fields, face lists and partials of one group of
-    // scenes in one allocation that grows to the largest call seen; the pinned staging of the call's tables
-    void* d_scn_ws = nullptr;
-    size_t scn_ws_size = 0;
-    int32_t* h_scn_tab = nullptr;
-    size_t h_scn_tab_bytes = 0;
-    // mvfit_associate_views (associate.hip): ray origins, then rays and linkage matrices of one group of frames; grown to
-    // the largest call
-    void* d_assoc_ws = nullptr;
-    size_t assoc_ws_size = 0;
-    // frozen obstacles of the scene term (mvfit_set_scene_obstacles): per problem its scene's row, its box and its field.
-    // The buffers keep their addresses while (B, grid) stay the same, so a re-freeze leaves the captured round graph valid.
-    bool obst_on = false;
-    int obst_grid = 0;
-    float obst_rob = 0.f;
-    int32_t* d_obst_tab = nullptr;     // [B] SceneBody rows
-    float4* d_obst_box = nullptr;      // [B] (centre, scale)
-    float* d_obst_phi = nullptr;       // [B][G^3]
-    // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
-    SilState sil;
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_vp, ev_step;
@@ -854,9 +850,8 @@ template <typename T>
 static T* dev_upload(mvfit_ctx* c, const T* h, size_t n) {
     if (n == 0) return nullptr;
     T* d = nullptr;
-    if (hipMalloc(&d, n * sizeof(T)) != hipSuccess) d = nullptr;
-    c->allocs.push_back(d);                 // a null entry makes mvfit_create_ex fail (checked after all uploads)
-    if (d && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) c->upload_failed = true;
+    if (c->model_mem.alloc(&d, n * sizeof(T)) != hipSuccess) c->alloc_failed = true;      // (mvfit_create_ex checks after all uploads)
+    else if (hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) c->upload_failed = true;
     return d;
 }
 template <typename T>
@@ -1028,9 +1023,9 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
     }
     if (c->has_vposer) {    // request / answer granules of the decoder helpers (re-initialised before every launch that has them)
         c->vps_words = (size_t)VPS_MAX_SETS * VPS_PMAX * VPS_GRAN * (1 + VPS_SLICES);
-        c->vps_mem = dev_upload(c, std::vector<unsigned long long>(c->vps_words + 1, 0ull));
+        if (c->model_mem.alloc(&c->vps_mem, (c->vps_words + 1) * 8, true) != hipSuccess) c->alloc_failed = true;
     }
-    for (void* p : c->allocs) if (!p) return fail(c, MVFIT_E_HIP, "device allocation failed");
+    if (c->alloc_failed) return fail(c, MVFIT_E_HIP, "device allocation failed");
     if (c->upload_failed) return fail(c, MVFIT_E_HIP, "copying the model constants to the device failed");
     HIP_OK(c, vertex_pass_configure());
     HIP_OK(c, vertex_backward_configure());
@@ -1048,40 +1043,27 @@ extern "C" int mvfit_create_ex(mvfit_ctx** out, int device, void* hip_stream, co
                           reinterpret_cast<const void*>(fit_persistent_kernel<false, true, true>),
                           reinterpret_cast<const void*>(fit_persistent_kernel<true, true, false>)})
         HIP_OK(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(persistent_lds(false), persistent_lds(true))));
-    HIP_OK(c, hipHostMalloc(&c->h_done, 8));
+    HIP_OK(c, c->h_done.reserve(8));
     HIP_OK(c, hipDeviceSynchronize());
     return MVFIT_OK;
 }
 
 // the scene term's obstacles go with the batch they were frozen for
 static void free_obstacles(mvfit_ctx* c) {
-    void* ps[] = {c->d_obst_tab, c->d_obst_box, c->d_obst_phi};
-    for (void* p : ps) if (p) hipFree(p);
-    c->d_obst_tab = nullptr; c->d_obst_box = nullptr; c->d_obst_phi = nullptr;
-    c->obst_on = false; c->obst_grid = 0; c->obst_rob = 0.f;
+    c->obst_mem.release();
+    c->obst = Obstacles{};
 }
 
 static void free_problem_buffers(mvfit_ctx* c) {
     drop_graph(c);
-    void* ps[] = {c->d_camR, c->d_camt, c->d_camf, c->d_camc, c->d_gt, c->d_wc, c->P.coefH, c->P.coefT, c->P.Amat, c->P.tau,
-                  c->P.vposed_sel, c->P.xs_sel, c->d_verts, c->d_obs, c->F.opt, c->F.pose, c->F.dirs, c->F.stps,
-                  c->F.grow, c->F.gcol, c->F.rinv, c->F.stage_final, c->F.n_done, c->d_sdf_box, c->d_sdf_samp, c->d_sdf_entries,
-                  c->d_sdf_adj, c->d_sdf_cull, c->d_sdf_boxpart, c->F.sdf_gate, c->F.sdf_tag, c->F.vp, c->d_gt3d, c->d_c3d};
-    for (void* p : ps) if (p) hipFree(p);
-    {
-        void* rp[] = {c->ring.coefH, c->ring.Amat, c->ring.tau, c->ring.tag, c->ring.done_round, c->ring.stats, c->ring.pass_done};
-        for (void* q : rp) if (q) hipFree(q);
-        c->ring = AsyncRing{};
-    }
+    c->problem_mem.release();
+    c->ring_mem.release();
+    c->sdf_cull.reset();
     c->B = c->V = c->Bpad = 0;          // nothing is allocated: a failed re-allocation cannot leave a stale shape behind
-    c->d_gt3d = c->d_c3d = nullptr;
-    c->d_camR = c->d_camt = c->d_camf = c->d_camc = c->d_gt = c->d_wc = nullptr;
-    c->d_obs = nullptr;
+    c->pb = ProblemBufs{};
     c->P = DevPose{};
-    c->d_verts = nullptr;
     c->F = FitBuffers{};
-    c->d_sdf_box = nullptr; c->d_sdf_samp = nullptr; c->d_sdf_entries = nullptr; c->d_sdf_adj = nullptr; c->d_sdf_cull = nullptr;
-    c->d_sdf_boxpart = nullptr;
+    c->ring = AsyncRing{};
     c->sdf_cull_refused = false;
     free_obstacles(c);
 }
@@ -1091,33 +1073,14 @@ extern "C" void mvfit_destroy(mvfit_ctx* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     free_problem_buffers(c);
-    if (c->d_sdf_faces) hipFree(c->d_sdf_faces);
-    if (c->d_sdf_op_ws) hipFree(c->d_sdf_op_ws);
-    if (c->d_vp_log) hipFree(c->d_vp_log);
-    if (c->d_render_nrm) hipFree(c->d_render_nrm);
-    if (c->d_render_ws) hipFree(c->d_render_ws);
-    if (c->d_scene_tab) hipFree(c->d_scene_tab);
-    for (int k = 0; k < 2; ++k) {
-        if (c->h_scene_tab[k]) hipHostFree(c->h_scene_tab[k]);
-        if (c->scene_copied[k]) hipEventDestroy(c->scene_copied[k]);
-    }
-    if (c->d_vjp_part) hipFree(c->d_vjp_part);
-    if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
-    if (c->d_scn_ws) hipFree(c->d_scn_ws);
-    if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
-    if (c->d_assoc_ws) hipFree(c->d_assoc_ws);
-    sil_free(c->sil);
-    for (void* p : c->allocs) if (p) hipFree(p);
-    if (c->h_done) hipHostFree(c->h_done);
+    for (hipEvent_t e : c->scene_copied) if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_done) if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_batch) if (e) hipEventDestroy(e);
     if (c->ev_init) hipEventDestroy(c->ev_init);
     if (c->pass_stream) hipStreamDestroy(c->pass_stream);
-    if (c->h_async_done) hipHostFree(c->h_async_done);
-    if (c->d_queue) hipFree(c->d_queue);
     for (auto& e : c->ev_vp) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto& e : c->ev_step) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    delete c;
+    delete c;                           // the owners free the rest
 }
 
 extern "C" int mvfit_sync(mvfit_ctx* c) {
@@ -1140,45 +1103,43 @@ extern "C" int mvfit_set_problems(mvfit_ctx* c, int B, int V, int cam_batched, c
         c->capture_verts = nullptr; c->capture_round = -1;
         const size_t nc = cam_batched ? (size_t)B * V : (size_t)V;
         const int Bpad = (B + 31) / 32 * 32;
-        HIP_OK(c, hipMalloc(&c->d_camR, nc * 9 * 4)); HIP_OK(c, hipMalloc(&c->d_camt, nc * 3 * 4));
-        HIP_OK(c, hipMalloc(&c->d_camf, nc * 4)); HIP_OK(c, hipMalloc(&c->d_camc, nc * 2 * 4));
-        HIP_OK(c, hipMalloc(&c->d_gt, (size_t)B * V * NKP * 2 * 4)); HIP_OK(c, hipMalloc(&c->d_wc, (size_t)B * V * NKP * 4));
-        HIP_OK(c, hipMalloc(&c->P.coefT, (size_t)Bpad * KROWS * 4)); HIP_OK(c, hipMalloc(&c->P.Amat, (size_t)Bpad * 288 * 4));
-        HIP_OK(c, hipMalloc(&c->P.tau, (size_t)Bpad * 4 * 4));
-        HIP_OK(c, hipMalloc(&c->P.vposed_sel, (size_t)Bpad * NC_MAX * 4));
-        HIP_OK(c, hipMalloc(&c->P.xs_sel, (size_t)Bpad * NC_MAX * 4));
-        HIP_OK(c, hipMemset(c->P.coefT, 0, (size_t)Bpad * KROWS * 4));
-        HIP_OK(c, hipMalloc(&c->P.coefH, (size_t)Bpad * KROWS * 4));
-        HIP_OK(c, hipMemset(c->P.coefH, 0, (size_t)Bpad * KROWS * 4));
-        HIP_OK(c, hipMalloc(&c->d_verts, (size_t)B * c->nv * 3 * 4));
-        HIP_OK(c, hipMalloc(&c->d_obs, (size_t)B * sizeof(ObsBlock)));
-        HIP_OK(c, hipMalloc(&c->F.opt, (size_t)B * sizeof(OptBlock)));
-        HIP_OK(c, hipMalloc(&c->F.pose, (size_t)B * sizeof(PoseBlock)));
-        HIP_OK(c, hipMalloc(&c->F.dirs, (size_t)B * LB_HIST * LB_D * 4));
-        HIP_OK(c, hipMalloc(&c->F.stps, (size_t)B * LB_HIST * LB_D * 4));
-        HIP_OK(c, hipMalloc(&c->F.rinv, (size_t)B * LB_RPACK * 4));
-        HIP_OK(c, hipMalloc(&c->F.grow, (size_t)B * LB_GSIZE * 4));
-        HIP_OK(c, hipMalloc(&c->F.gcol, (size_t)B * LB_GSIZE * 4));
-        HIP_OK(c, hipMemset(c->F.grow, 0, (size_t)B * LB_GSIZE * 4));
-        HIP_OK(c, hipMemset(c->F.gcol, 0, (size_t)B * LB_GSIZE * 4));
-        HIP_OK(c, hipMalloc(&c->F.stage_final, (size_t)B * MVFIT_MAX_STAGES * 8));
-        HIP_OK(c, hipMalloc(&c->F.n_done, 12));
-        HIP_OK(c, hipMalloc(&c->F.sdf_gate, (size_t)B * 4));
-        HIP_OK(c, hipMalloc(&c->F.sdf_tag, (size_t)Bpad * 4));
-        HIP_OK(c, hipMalloc(&c->F.vp, (size_t)B * sizeof(VpBlock)));
-        HIP_OK(c, hipMalloc(&c->d_gt3d, (size_t)B * NKP * 3 * 4));
-        HIP_OK(c, hipMalloc(&c->d_c3d, (size_t)B * NKP * 4));
+        DevPool& mem = c->problem_mem;
+        ProblemBufs& pb = c->pb;
+        HIP_OK(c, mem.alloc(&pb.camR, nc * 9 * 4)); HIP_OK(c, mem.alloc(&pb.camt, nc * 3 * 4));
+        HIP_OK(c, mem.alloc(&pb.camf, nc * 4)); HIP_OK(c, mem.alloc(&pb.camc, nc * 2 * 4));
+        HIP_OK(c, mem.alloc(&pb.gt, (size_t)B * V * NKP * 2 * 4)); HIP_OK(c, mem.alloc(&pb.wc, (size_t)B * V * NKP * 4));
+        HIP_OK(c, mem.alloc(&c->P.coefT, (size_t)Bpad * KROWS * 4, true)); HIP_OK(c, mem.alloc(&c->P.Amat, (size_t)Bpad * 288 * 4));
+        HIP_OK(c, mem.alloc(&c->P.tau, (size_t)Bpad * 4 * 4));
+        HIP_OK(c, mem.alloc(&c->P.vposed_sel, (size_t)Bpad * NC_MAX * 4));
+        HIP_OK(c, mem.alloc(&c->P.xs_sel, (size_t)Bpad * NC_MAX * 4));
+        HIP_OK(c, mem.alloc(&c->P.coefH, (size_t)Bpad * KROWS * 4, true));
+        HIP_OK(c, mem.alloc(&pb.verts, (size_t)B * c->nv * 3 * 4));
+        HIP_OK(c, mem.alloc(&pb.obs, (size_t)B * sizeof(ObsBlock)));
+        HIP_OK(c, mem.alloc(&c->F.opt, (size_t)B * sizeof(OptBlock)));
+        HIP_OK(c, mem.alloc(&c->F.pose, (size_t)B * sizeof(PoseBlock)));
+        HIP_OK(c, mem.alloc(&c->F.dirs, (size_t)B * LB_HIST * LB_D * 4));
+        HIP_OK(c, mem.alloc(&c->F.stps, (size_t)B * LB_HIST * LB_D * 4));
+        HIP_OK(c, mem.alloc(&c->F.rinv, (size_t)B * LB_RPACK * 4));
+        HIP_OK(c, mem.alloc(&c->F.grow, (size_t)B * LB_GSIZE * 4, true));
+        HIP_OK(c, mem.alloc(&c->F.gcol, (size_t)B * LB_GSIZE * 4, true));
+        HIP_OK(c, mem.alloc(&c->F.stage_final, (size_t)B * MVFIT_MAX_STAGES * 8));
+        HIP_OK(c, mem.alloc(&c->F.n_done, 12));
+        HIP_OK(c, mem.alloc(&c->F.sdf_gate, (size_t)B * 4));
+        HIP_OK(c, mem.alloc(&c->F.sdf_tag, (size_t)Bpad * 4));
+        HIP_OK(c, mem.alloc(&c->F.vp, (size_t)B * sizeof(VpBlock)));
+        HIP_OK(c, mem.alloc(&pb.gt3d, (size_t)B * NKP * 3 * 4));
+        HIP_OK(c, mem.alloc(&pb.c3d, (size_t)B * NKP * 4));
         c->B = B; c->V = V; c->Bpad = Bpad;      // only now: every buffer of this shape exists
     }
     const size_t nc = cam_batched ? (size_t)B * V : (size_t)V;
-    HIP_OK(c, hipMemcpyAsync(c->d_camR, cam_R, nc * 9 * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_camt, cam_t, nc * 3 * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_camf, cam_f, nc * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_camc, cam_c, nc * 2 * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_gt, gt_xy, (size_t)B * V * NKP * 2 * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_wc, w_conf, (size_t)B * V * NKP * 4, hipMemcpyDefault, c->stream));
-    c->Q = DevProblems{B, V, cam_batched ? 1 : 0, c->d_camR, c->d_camt, c->d_camf, c->d_camc, c->d_gt, c->d_wc};
-    hipLaunchKernelGGL(pack_obs_kernel, dim3(B), dim3(256), 0, c->stream, c->Q, c->d_obs);
+    HIP_OK(c, hipMemcpyAsync(c->pb.camR, cam_R, nc * 9 * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.camt, cam_t, nc * 3 * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.camf, cam_f, nc * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.camc, cam_c, nc * 2 * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.gt, gt_xy, (size_t)B * V * NKP * 2 * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.wc, w_conf, (size_t)B * V * NKP * 4, hipMemcpyDefault, c->stream));
+    c->Q = DevProblems{B, V, cam_batched ? 1 : 0, c->pb.camR, c->pb.camt, c->pb.camf, c->pb.camc, c->pb.gt, c->pb.wc};
+    hipLaunchKernelGGL(pack_obs_kernel, dim3(B), dim3(256), 0, c->stream, c->Q, c->pb.obs);
     c->has_joints3d = false;
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -1189,9 +1150,9 @@ extern "C" int mvfit_set_joints3d(mvfit_ctx* c, const float* gt3d, const float* 
     if (!c || !gt3d || !conf3d) return MVFIT_E_ARG;
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     HIP_OK(c, hipSetDevice(c->device));
-    HIP_OK(c, hipMemcpyAsync(c->d_gt3d, gt3d, (size_t)c->B * NKP * 3 * 4, hipMemcpyDefault, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_c3d, conf3d, (size_t)c->B * NKP * 4, hipMemcpyDefault, c->stream));
-    hipLaunchKernelGGL(pack_joints3d_kernel, dim3(c->B), dim3(64), 0, c->stream, (const float*)c->d_gt3d, (const float*)c->d_c3d, c->d_obs);
+    HIP_OK(c, hipMemcpyAsync(c->pb.gt3d, gt3d, (size_t)c->B * NKP * 3 * 4, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->pb.c3d, conf3d, (size_t)c->B * NKP * 4, hipMemcpyDefault, c->stream));
+    hipLaunchKernelGGL(pack_joints3d_kernel, dim3(c->B), dim3(64), 0, c->stream, (const float*)c->pb.gt3d, (const float*)c->pb.c3d, c->pb.obs);
     HIP_OK(c, hipGetLastError());
     c->has_joints3d = true;
     return MVFIT_OK;
@@ -1199,26 +1160,26 @@ extern "C" int mvfit_set_joints3d(mvfit_ctx* c, const float* gt3d, const float* 
 
 extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, int grid_size) {
     if (!c) return MVFIT_E_ARG;
-    if (c->obst_on && faces && num_faces != 0)
+    if (c->obst.on && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: scene obstacles are the interpenetration term (one per ctx): remove them first");
     HIP_OK(c, hipSetDevice(c->device));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     drop_graph(c);
-    if (c->d_sdf_faces) { hipFree(c->d_sdf_faces); c->d_sdf_faces = nullptr; }
-    if (c->d_sdf_cull) { hipFree(c->d_sdf_cull); c->d_sdf_cull = nullptr; }          // sized by the face count
+    c->sdf_faces.reset();
+    c->sdf_cull.reset();                                           // sized by the face count
     c->sdf_cull_refused = false;
     c->sdf_num_faces = 0; c->sdf_grid = 0;
     if (!faces || num_faces == 0) return MVFIT_OK;                 // term switched off
     if (num_faces < 0 || grid_size < 2 || grid_size > 1024)
         return fail(c, MVFIT_E_ARG, "mvfit_set_sdf: bad argument (num_faces=%d grid_size=%d)", num_faces, grid_size);
     if (c->nv > 8192) return fail(c, MVFIT_E_UNSUPPORTED, "the SDF term supports up to 8192 vertices (model has %d)", c->nv);
-    HIP_OK(c, hipMalloc(&c->d_sdf_faces, (size_t)num_faces * 3 * 4));
-    HIP_OK(c, hipMemcpy(c->d_sdf_faces, faces, (size_t)num_faces * 3 * 4, hipMemcpyDefault));
+    HIP_OK(c, c->sdf_faces.reserve((size_t)num_faces * 3 * 4));
+    HIP_OK(c, hipMemcpy(c->sdf_faces.as<int32_t>(), faces, (size_t)num_faces * 3 * 4, hipMemcpyDefault));
     std::vector<int32_t> h((size_t)num_faces * 3);
-    HIP_OK(c, hipMemcpy(h.data(), c->d_sdf_faces, h.size() * 4, hipMemcpyDeviceToHost));
+    HIP_OK(c, hipMemcpy(h.data(), c->sdf_faces.as<int32_t>(), h.size() * 4, hipMemcpyDeviceToHost));
     for (int32_t vi : h)
         if (vi < 0 || vi >= c->nv) {
-            hipFree(c->d_sdf_faces); c->d_sdf_faces = nullptr;
+            c->sdf_faces.reset();
             return fail(c, MVFIT_E_ARG, "mvfit_set_sdf: face vertex index %d outside [0, %d)", (int)vi, c->nv);
         }
     c->sdf_num_faces = num_faces; c->sdf_grid = grid_size;
@@ -1227,12 +1188,12 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
 
 extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
     if (!c) return MVFIT_E_ARG;
-    if (!c->d_sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
-    if (samples && c->obst_on)
+    if (!c->pb.sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
+    if (samples && c->obst.on)
         return fail(c, MVFIT_E_UNSUPPORTED, "mvfit_sdf_term_read: the scene term keeps no per-vertex samples (sums only)");
     HIP_OK(c, hipSetDevice(c->device));
-    if (samples) HIP_OK(c, hipMemcpyAsync(samples, c->d_sdf_samp, (size_t)c->B * c->nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    if (sums) HIP_OK(c, hipMemcpy2DAsync(sums, sizeof(float), c->d_sdf_adj, sizeof(SdfAdj), sizeof(float), c->B, hipMemcpyDeviceToDevice, c->stream));
+    if (samples) HIP_OK(c, hipMemcpyAsync(samples, c->pb.sdf_samp, (size_t)c->B * c->nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    if (sums) HIP_OK(c, hipMemcpy2DAsync(sums, sizeof(float), c->pb.sdf_adj, sizeof(SdfAdj), sizeof(float), c->B, hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 
@@ -1240,35 +1201,35 @@ extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
 static int ensure_sdf_buffers(mvfit_ctx* c) {
     // all faces (or any list too long for the staged walk): the per-round face lists of sdf_term.hip.
     // mvfit_options::sdf_face_lists = 0 keeps the brute-force kernel (the check of the culled one).
-    if (c->d_sdf_cull && !c->opt.sdf_face_lists) {          // switched off since the workspace was made
+    if (c->sdf_cull.get() && !c->opt.sdf_face_lists) {          // switched off since the workspace was made
         HIP_OK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_sdf_cull);
-        c->d_sdf_cull = nullptr;
+        c->sdf_cull.reset();
     }
-    c->sdf_term_path = c->d_sdf_cull ? 1 : 0;
-    if (!c->d_sdf_cull && c->opt.sdf_face_lists && c->sdf_num_faces >= sdf_cull_min_faces() && !c->sdf_cull_refused) {
+    c->sdf_term_path = c->sdf_cull.get() ? 1 : 0;
+    if (!c->sdf_cull.get() && c->opt.sdf_face_lists && c->sdf_num_faces >= sdf_cull_min_faces() && !c->sdf_cull_refused) {
         // (11.6 MB of lists, records and bins per problem at 13,776 faces: a batch whose workspace would not fit keeps the
         // walk - decided ONCE per (batch, face list): the refusal is remembered (and reported by mvfit_sdf_info) instead of
         // querying the free memory on every fit)
         size_t free_b = 0, total_b = 0;
         HIP_OK(c, hipMemGetInfo(&free_b, &total_b));
         if (sdf_cull_bytes(c->B, c->sdf_num_faces) < free_b / 2) {
-            HIP_OK(c, hipMalloc(&c->d_sdf_cull, sdf_cull_bytes(c->B, c->sdf_num_faces)));
-            HIP_OK(c, hipMemset(reinterpret_cast<unsigned char*>(c->d_sdf_cull) + sdf_cull_zero_offset(c->B, c->sdf_num_faces), 0,
-                                sdf_cull_zero_bytes(c->B)));
+            HIP_OK(c, c->sdf_cull.reserve(sdf_cull_bytes(c->B, c->sdf_num_faces)));
+            HIP_OK(c, hipMemset(c->sdf_cull.as<unsigned char>() + sdf_cull_zero_offset(c->B, c->sdf_num_faces), 0, sdf_cull_zero_bytes(c->B)));
             c->sdf_term_path = 1;
         } else {
             c->sdf_cull_refused = true;
             c->sdf_term_path = 2;
         }
-    } else if (!c->d_sdf_cull && c->sdf_cull_refused) c->sdf_term_path = 2;
-    if (c->d_sdf_adj) return MVFIT_OK;
-    HIP_OK(c, hipMalloc(&c->d_sdf_box, (size_t)c->B * sizeof(SdfBox)));
-    HIP_OK(c, hipMalloc(&c->d_sdf_samp, (size_t)c->B * c->nv * sizeof(float4)));
-    HIP_OK(c, hipMalloc(&c->d_sdf_entries, sdf_work_bytes(c->B, c->nv)));      // entry lists + slice partials + heads + tickets
-    HIP_OK(c, hipMemset(reinterpret_cast<unsigned char*>(c->d_sdf_entries) + sdf_ticket_offset(c->B, c->nv), 0, (size_t)c->B * sizeof(int)));
-    HIP_OK(c, hipMalloc(&c->d_sdf_adj, (size_t)c->B * sizeof(SdfAdj)));
-    HIP_OK(c, hipMalloc(&c->d_sdf_boxpart, (size_t)c->Bpad * c->M.ntiles * 6 * 8));
+    } else if (!c->sdf_cull.get() && c->sdf_cull_refused) c->sdf_term_path = 2;
+    if (c->pb.sdf_adj) return MVFIT_OK;
+    unsigned char* work = nullptr;
+    HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_box, (size_t)c->B * sizeof(SdfBox)));
+    HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_samp, (size_t)c->B * c->nv * sizeof(float4)));
+    HIP_OK(c, c->problem_mem.alloc(&work, sdf_work_bytes(c->B, c->nv)));      // entry lists + slice partials + heads + tickets
+    HIP_OK(c, hipMemset(work + sdf_ticket_offset(c->B, c->nv), 0, (size_t)c->B * sizeof(int)));
+    c->pb.sdf_entries = work;
+    HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_adj, (size_t)c->B * sizeof(SdfAdj)));
+    HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_boxpart, (size_t)c->Bpad * c->M.ntiles * 6 * 8));
     return MVFIT_OK;
 }
 
@@ -1276,28 +1237,22 @@ static int ensure_sdf_buffers(mvfit_ctx* c) {
 // DevPose::box_part is set) when the split-fp16 basis exists and the launch is one 32-problem chunk per workgroup
 static bool pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
     const int chunks = (b_hi + 31) / 32 - b_lo / 32;
-    return !c->obst_on && c->M.bs_h2 != nullptr && c->d_sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
+    return !c->obst.on && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
 }
 
 // the interpenetration term of a chained round behind its vertex pass: against the frozen obstacles when they are set,
 // else the one-person term of mvfit_set_sdf
 static hipError_t launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
-    if (c->obst_on)
-        return launch_scene_term(c->M, c->P, verts, c->B, c->d_obst_tab, c->d_obst_box, c->d_obst_phi, c->obst_grid, c->obst_rob, gate,
-                                 c->d_sdf_box, c->d_sdf_entries, c->d_sdf_adj, st);
-    return launch_sdf_term(c->M, c->P, verts, c->B, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, gate, c->d_sdf_box, c->d_sdf_samp,
-                           c->d_sdf_entries, c->d_sdf_adj, st, c->d_sdf_cull, nullptr, 0u, box_part);
+    if (c->obst.on)
+        return launch_scene_term(c->M, c->P, verts, c->B, c->obst.tab, c->obst.box, c->obst.phi, c->obst.grid, c->obst.rob, gate,
+                                 c->pb.sdf_box, c->pb.sdf_entries, c->pb.sdf_adj, st);
+    return launch_sdf_term(c->M, c->P, verts, c->B, c->sdf_faces.as<int32_t>(), c->sdf_num_faces, c->sdf_grid, gate, c->pb.sdf_box, c->pb.sdf_samp,
+                           c->pb.sdf_entries, c->pb.sdf_adj, st, c->sdf_cull.get(), nullptr, 0u, box_part);
 }
 
 static int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st) {
-    if (c->obst_on) {
-        const hipError_t e = launch_term(c, verts, gate, st, nullptr);
-        if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "scene term launch: %s", hipGetErrorString(e));
-        return MVFIT_OK;
-    }
-    hipError_t e = launch_sdf_term(c->M, c->P, verts, c->B, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, gate, c->d_sdf_box,
-                                   c->d_sdf_samp, c->d_sdf_entries, c->d_sdf_adj, st, c->d_sdf_cull);
-    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "sdf term launch: %s", hipGetErrorString(e));
+    const hipError_t e = launch_term(c, verts, gate, st, nullptr);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s term launch: %s", c->obst.on ? "scene" : "sdf", hipGetErrorString(e));
     return MVFIT_OK;
 }
 
@@ -1342,7 +1297,7 @@ extern "C" int mvfit_vertices(mvfit_ctx* c, const float* params, uint32_t flags,
     int rc = check_flags(c, flags);
     if (rc) return rc;
     HIP_OK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, params, flags,
+    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->P, params, flags,
                        (float*)nullptr);
     HIP_OK(c, hipGetLastError());
     rc = run_vertex_pass(c, verts);
@@ -1365,26 +1320,16 @@ extern "C" int mvfit_vertices_backward(mvfit_ctx* c, const float* params, uint32
     HIP_OK(c, hipSetDevice(c->device));
     if (g_verts) {
         const size_t need = vjp_part_bytes(c->Bpad, c->nv);
-        if (need > c->vjp_part_size || c->B > c->vjp_rec_n) {
+        const size_t need_rec = (size_t)c->B * sizeof(SdfAdj);
+        if (need > c->vjp_part.size() || need_rec > c->vjp_rec.size())
             HIP_OK(c, hipStreamSynchronize(c->stream));          // (a previous call may still read the old buffers)
-            if (need > c->vjp_part_size) {
-                if (c->d_vjp_part) hipFree(c->d_vjp_part);
-                c->d_vjp_part = nullptr; c->vjp_part_size = 0;
-                HIP_OK(c, hipMalloc(&c->d_vjp_part, need));
-                c->vjp_part_size = need;
-            }
-            if (c->B > c->vjp_rec_n) {
-                if (c->d_vjp_rec) hipFree(c->d_vjp_rec);
-                c->d_vjp_rec = nullptr; c->vjp_rec_n = 0;
-                HIP_OK(c, hipMalloc(&c->d_vjp_rec, (size_t)c->B * sizeof(SdfAdj)));
-                c->vjp_rec_n = c->B;
-            }
-        }
+        HIP_OK(c, c->vjp_part.reserve(need));
+        HIP_OK(c, c->vjp_rec.reserve(need_rec));
     }
-    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, params, flags,
+    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->P, params, flags,
                        (float*)nullptr);
     HIP_OK(c, hipGetLastError());
-    HIP_OK(c, launch_vertices_backward(c->M, c->P, c->B, c->Bpad, params, flags, g_verts, g_joints, c->d_vjp_part, c->d_vjp_rec,
+    HIP_OK(c, launch_vertices_backward(c->M, c->P, c->B, c->Bpad, params, flags, g_verts, g_joints, c->vjp_part.as<float>(), c->vjp_rec.as<SdfAdj>(),
                                        g_params, c->stream));
     return MVFIT_OK;
 }
@@ -1395,7 +1340,7 @@ extern "C" int mvfit_full_pose(mvfit_ctx* c, const float* params, uint32_t flags
     int rc = check_flags(c, flags);
     if (rc) return rc;
     HIP_OK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, params, flags,
+    hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->P, params, flags,
                        full_pose);
     HIP_OK(c, hipGetLastError());
     return MVFIT_OK;
@@ -1420,7 +1365,7 @@ static int closure_via_helpers(mvfit_ctx* c, const mvfit_weights* w, const float
     M.vps.fault = 0;
     c->vps_stats[0] = 1;
     hipLaunchKernelGGL(closure_kernel<true>, dim3(n + nsets * VPS_SLICES), dim3(STEP_NT), step_lds(), c->stream, M,
-                       (const ObsBlock*)c->d_obs, c->V, to_dev(*w), c->P, params, 0, loss, grad, joints, (const SdfAdj*)nullptr);
+                       (const ObsBlock*)c->pb.obs, c->V, to_dev(*w), c->P, params, 0, loss, grad, joints, (const SdfAdj*)nullptr);
     HIP_OK(c, hipGetLastError());
     if (verts) return run_vertex_pass(c, verts);
     return MVFIT_OK;
@@ -1433,16 +1378,16 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
     int rc = check_flags(c, w->flags);
     if (rc) return rc;
     const bool sdf = w->coll_loss_weight > 0.f;
-    if (sdf && !c->sdf_num_faces && !c->obst_on)
+    if (sdf && !c->sdf_num_faces && !c->obst.on)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
     HIP_OK(c, hipSetDevice(c->device));
     if (c->opt.closure_vposer_helpers && (w->flags & MVFIT_F_VPOSER) && c->vps_mem && !sdf)
         return closure_via_helpers(c, w, params, loss, grad, verts, joints);
-    float* vbuf = verts ? verts : c->d_verts;
+    float* vbuf = verts ? verts : c->pb.verts;
     // the interpenetration term reads every vertex: it forces the vertex pass
     const bool sparse = (w->flags & MVFIT_F_SPARSE_VERTS) != 0 && !sdf;
     if (!sparse || verts) {
-        hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, params, w->flags,
+        hipLaunchKernelGGL(prep_kernel, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->P, params, w->flags,
                            (float*)nullptr);
         HIP_OK(c, hipGetLastError());
         rc = run_vertex_pass(c, vbuf);
@@ -1454,9 +1399,9 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
         if (rc) return rc;
     }
     prof_begin(c, c->ev_step);
-    hipLaunchKernelGGL(closure_kernel<false>, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->V,
+    hipLaunchKernelGGL(closure_kernel<false>, dim3(c->B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->V,
                        to_dev(*w), c->P, params,
-                       sparse ? 0 : 1, loss, grad, joints, sdf ? (const SdfAdj*)c->d_sdf_adj : (const SdfAdj*)nullptr);
+                       sparse ? 0 : 1, loss, grad, joints, sdf ? (const SdfAdj*)c->pb.sdf_adj : (const SdfAdj*)nullptr);
     prof_end(c, c->ev_step);
     HIP_OK(c, hipGetLastError());
     return MVFIT_OK;
@@ -1510,7 +1455,7 @@ static const int kGraphRounds = 24;
 static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O) {
     // (the scene term's obstacles: buffers and scalars baked into its kernel node; a re-freeze changes none of them)
     struct { const void *tab, *box, *phi; int grid; float rob; } obst = {nullptr, nullptr, nullptr, 0, 0.f};
-    if (c->obst_on) { obst.tab = c->d_obst_tab; obst.box = c->d_obst_box; obst.phi = c->d_obst_phi; obst.grid = c->obst_grid; obst.rob = c->obst_rob; }
+    if (c->obst.on) { obst.tab = c->obst.tab; obst.box = c->obst.box; obst.phi = c->obst.phi; obst.grid = c->obst.grid; obst.rob = c->obst.rob; }
     std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
@@ -1530,12 +1475,12 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         // rounds with the SDF term: the pass writes its tiles' keys of the term's bounding box (single-chunk split kernel), the
         // front kernel reduces the box from them
         DevPose Pg = c->P;
-        if (c->F.sdf_adj && pass_writes_box_parts(c, 0, c->B)) Pg.box_part = c->d_sdf_boxpart;
+        if (c->F.sdf_adj && pass_writes_box_parts(c, 0, c->B)) Pg.box_part = c->pb.sdf_boxpart;
         for (int r = 0; r < kGraphRounds && e == hipSuccess; ++r) {
-            e = launch_vertex_pass(c->M, Pg, c->B, c->d_verts, c->opt.pass_kernel, cs);
+            e = launch_vertex_pass(c->M, Pg, c->B, c->pb.verts, c->opt.pass_kernel, cs);
             if (e == hipSuccess && c->F.sdf_adj)
-                e = launch_term(c, c->d_verts, c->F.sdf_gate, cs, Pg.box_part);
-            hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), cs, c->M, (const ObsBlock*)c->d_obs, c->V, SW, O,
+                e = launch_term(c, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
+            hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), cs, c->M, (const ObsBlock*)c->pb.obs, c->V, SW, O,
                                c->P, c->F);
         }
         hipError_t e2 = hipStreamEndCapture(cs, &g);
@@ -1584,33 +1529,28 @@ static int ensure_async(mvfit_ctx* c, int rb) {
         HIP_OK(c, hipStreamCreateWithFlags(&c->pass_stream, hipStreamNonBlocking));
         for (hipEvent_t& e : c->ev_batch) HIP_OK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_OK(c, hipEventCreateWithFlags(&c->ev_init, hipEventDisableTiming));
-        HIP_OK(c, hipHostMalloc(&c->h_async_done, 64));
-        HIP_OK(c, hipMalloc(&c->d_queue, 64));
+        HIP_OK(c, c->h_async_done.reserve(64));
+        HIP_OK(c, c->queue.reserve(64));
     }
     AsyncRing& R = c->ring;
     if (R.tag && R.Bpad >= rb) return MVFIT_OK;
     if (R.tag) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
         HIP_OK(c, hipStreamSynchronize(c->pass_stream));
-        void* rp[] = {R.coefH, R.Amat, R.tau, R.tag, R.done_round, R.stats, R.pass_done};
-        for (void* q : rp) if (q) hipFree(q);
-        R = AsyncRing{};
     }
+    DevPool& mem = c->ring_mem;
+    mem.release();                       // (also what an earlier call that failed half-way left)
+    R = AsyncRing{};
     const size_t Bp = (size_t)rb;
     R.nslots = kRingSlots; R.Bpad = rb;
-    HIP_OK(c, hipMalloc(&R.coefH, kRingSlots * Bp * KROWS * 4));
-    HIP_OK(c, hipMalloc(&R.Amat, kRingSlots * Bp * 288 * 4));
-    HIP_OK(c, hipMalloc(&R.tau, kRingSlots * Bp * 4 * 4));
-    HIP_OK(c, hipMalloc(&R.tag, kRingSlots * Bp * 4));
-    HIP_OK(c, hipMalloc(&R.done_round, (size_t)c->Bpad * 4));
-    HIP_OK(c, hipMalloc(&R.stats, 4 * 4));
-    HIP_OK(c, hipMalloc(&R.pass_done, 4 * kPassWords));
-    HIP_OK(c, hipMemset(R.coefH, 0, kRingSlots * Bp * KROWS * 4));
-    HIP_OK(c, hipMemset(R.Amat, 0, kRingSlots * Bp * 288 * 4));
-    HIP_OK(c, hipMemset(R.tau, 0, kRingSlots * Bp * 4 * 4));
-    void* dp = nullptr;
-    HIP_OK(c, hipHostGetDevicePointer(&dp, c->h_async_done, 0));
-    R.host_done = reinterpret_cast<int*>(dp);
+    HIP_OK(c, mem.alloc(&R.coefH, kRingSlots * Bp * KROWS * 4, true));
+    HIP_OK(c, mem.alloc(&R.Amat, kRingSlots * Bp * 288 * 4, true));
+    HIP_OK(c, mem.alloc(&R.tau, kRingSlots * Bp * 4 * 4, true));
+    HIP_OK(c, mem.alloc(&R.done_round, (size_t)c->Bpad * 4));
+    HIP_OK(c, mem.alloc(&R.stats, 4 * 4));
+    HIP_OK(c, mem.alloc(&R.pass_done, 4 * kPassWords));
+    HIP_OK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&R.host_done), c->h_async_done.get(), 0));
+    HIP_OK(c, mem.alloc(&R.tag, kRingSlots * Bp * 4));          // last: a ring with a tag is complete
     return MVFIT_OK;
 }
 
@@ -1644,7 +1584,7 @@ static int launch_persistent(mvfit_ctx* c, const StageWeights& SW, const LbOpts&
                 : O.reuse_outer ? (lean ? fit_persistent_kernel<false, true, true> : fit_persistent_kernel<false, true, false>)
                 : lean ? fit_persistent_kernel<false, false, true> : fit_persistent_kernel<false, false, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(STEP_NT), persistent_lds((SW.w[0].flags & MVFIT_F_VPOSER) != 0), c->stream, M,
-                       (const ObsBlock*)c->d_obs, c->V, SW, O, c->P, c->F, cap, R, L.b_lo, L.n_target, pause_stage, queue, b_end);
+                       (const ObsBlock*)c->pb.obs, c->V, SW, O, c->P, c->F, cap, R, L.b_lo, L.n_target, pause_stage, queue, b_end);
     HIP_OK(c, hipGetLastError());
     return MVFIT_OK;
 }
@@ -1653,7 +1593,7 @@ static int launch_persistent(mvfit_ctx* c, const StageWeights& SW, const LbOpts&
 // the operands; busy = a workgroup's own drained - seen (wall clock, 100 MHz)
 static int reduce_pass_log(mvfit_ctx* c, int res_grid) {
     std::vector<unsigned long long> lg((size_t)kVpLogRounds * res_grid * 2);
-    HIP_OK(c, hipMemcpy(lg.data(), c->d_vp_log, lg.size() * 8, hipMemcpyDeviceToHost));
+    HIP_OK(c, hipMemcpy(lg.data(), c->vp_log.as<unsigned long long>(), lg.size() * 8, hipMemcpyDeviceToHost));
     double span = 0.0, busy = 0.0, slowest = 0.0;
     int n = 0;
     for (int r = 0; r < kVpLogRounds; ++r) {
@@ -1692,7 +1632,7 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
     if (rc) return rc;
     AsyncRing R = c->ring;
     const size_t rb = (size_t)R.Bpad;                       // ring stride in problems (>= per)
-    volatile int* h_done = c->h_async_done;
+    volatile int* h_done = c->h_async_done.as<int>();
     // polled words: re-initialised every call
     HIP_OK(c, hipMemsetAsync(R.done_round, 0xff, (size_t)c->Bpad * 4, c->stream));
     HIP_OK(c, hipMemsetAsync(R.stats, 0, 16, c->stream));
@@ -1701,13 +1641,7 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
     c->res_rounds = 0; c->res_span_ms = c->res_busy_ms = c->res_slowest_ms = 0.0;
     const bool log_on = tpw && c->profile;
     if (log_on) {
-        const size_t words = (size_t)kVpLogRounds * res_grid * 2;
-        if (c->vp_log_words < words) {
-            if (c->d_vp_log) hipFree(c->d_vp_log);
-            c->d_vp_log = nullptr; c->vp_log_words = 0;
-            HIP_OK(c, hipMalloc(&c->d_vp_log, words * 8));
-            c->vp_log_words = words;
-        }
+        HIP_OK(c, c->vp_log.reserve((size_t)kVpLogRounds * res_grid * 2 * 8));
     }
     for (const FitLaunch& L : ph.launches) {
         const int b_lo = L.b_lo, b_hi = L.b_hi, n_target = L.n_target;
@@ -1724,14 +1658,14 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
             HIP_OK(c, hipMemsetAsync(c->F.sdf_tag, 0, (size_t)c->Bpad * 4, c->stream));
             HIP_OK(c, hipMemsetAsync(c->F.sdf_gate, 0, (size_t)B * 4, c->stream));
         }
-        if (log_on) HIP_OK(c, hipMemsetAsync(c->d_vp_log, 0, c->vp_log_words * 8, c->stream));      // (a profiled fit keeps the last sub-batch's stamps)
+        if (log_on) HIP_OK(c, hipMemsetAsync(c->vp_log.get(), 0, c->vp_log.size(), c->stream));      // (a profiled fit keeps the last sub-batch's stamps)
         HIP_OK(c, hipEventRecord(c->ev_init, c->stream));
         HIP_OK(c, hipStreamWaitEvent(c->pass_stream, c->ev_init, 0));
         if (refill) {
             c->h_queue0 = b_hi;                                   // problems [0, rows) start on their rows, the queue hands out the rest
-            HIP_OK(c, hipMemcpyAsync(c->d_queue, &c->h_queue0, 4, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(c, hipMemcpyAsync(c->queue.as<int>(), &c->h_queue0, 4, hipMemcpyHostToDevice, c->stream));
         }
-        rc = launch_persistent(c, SW, O, ph.launch_cap, R, L, ph.pause_stage, sdf_service, refill ? c->d_queue : nullptr, B);
+        rc = launch_persistent(c, SW, O, ph.launch_cap, R, L, ph.pause_stage, sdf_service, refill ? c->queue.as<int>() : nullptr, B);
         if (rc) return rc;
         int k = 0;
         if (tpw) {
@@ -1740,8 +1674,8 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
             ResidentArgs RA{};
             RA.coefH = R.coefH; RA.Amat = R.Amat; RA.tau = R.tau; RA.tag = R.tag;
             RA.done_round = R.done_round; RA.stats = R.stats; RA.wg_round = R.pass_done;
-            RA.log = log_on ? c->d_vp_log : nullptr; RA.log_rounds = kVpLogRounds;
-            RA.verts = c->d_verts;
+            RA.log = log_on ? c->vp_log.as<unsigned long long>() : nullptr; RA.log_rounds = kVpLogRounds;
+            RA.verts = c->pb.verts;
             RA.capture_verts = c->capture_verts; RA.capture_round = c->capture_verts ? c->capture_round : -1;
             RA.nslots = kRingSlots; RA.rb = (int)rb;
             RA.b_lo = b_lo; RA.n = b_hi - b_lo;
@@ -1769,9 +1703,9 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
                 P.round = r;
                 P.chunk0 = b_lo / 32;
                 P.pad_ = (unsigned)debug_hook("MVFIT_DEBUG_NT_OFF");      // (hooks build only) bit 0 = plain basis loads, bit 1 = plain vertex stores
-                float* vout = c->d_verts;
+                float* vout = c->pb.verts;
                 if (c->capture_verts && (int)r == c->capture_round) vout = c->capture_verts;      // test hook
-                if (sdf_service && pass_writes_box_parts(c, b_lo, b_hi)) P.box_part = c->d_sdf_boxpart;      // (the term's box from the pass's tile keys)
+                if (sdf_service && pass_writes_box_parts(c, b_lo, b_hi)) P.box_part = c->pb.sdf_boxpart;      // (the term's box from the pass's tile keys)
                 hipError_t e = launch_pass_gate(P, b_lo, b_hi, c->pass_stream);
                 hipEvent_t ea = nullptr, eb = nullptr;
                 if (c->profile && c->ev_vp.size() < 4096) {            // mvfit_profile: the dispatch's own begin / end stamps
@@ -1785,8 +1719,8 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
                     // front of the round's tag); transforms from the ring slot, float32 coefficients from the chained layout
                     DevPose Ps = P;
                     Ps.coefT = c->P.coefT;
-                    e = launch_sdf_term(c->M, Ps, vout, b_hi, c->d_sdf_faces, c->sdf_num_faces, c->sdf_grid, c->F.sdf_gate, c->d_sdf_box,
-                                        c->d_sdf_samp, c->d_sdf_entries, c->d_sdf_adj, c->pass_stream, c->d_sdf_cull, c->F.sdf_tag, r + 1u, P.box_part);
+                    e = launch_sdf_term(c->M, Ps, vout, b_hi, c->sdf_faces.as<int32_t>(), c->sdf_num_faces, c->sdf_grid, c->F.sdf_gate, c->pb.sdf_box,
+                                        c->pb.sdf_samp, c->pb.sdf_entries, c->pb.sdf_adj, c->pass_stream, c->sdf_cull.get(), c->F.sdf_tag, r + 1u, P.box_part);
                     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "SDF term launch: %s", hipGetErrorString(e));
                 }
             }
@@ -1802,13 +1736,13 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
     }
     // one host wait for all of it
     HIP_OK(c, hipMemcpyAsync(c->async_stats, R.stats, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->h_done, c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->h_done + 1, c->F.n_done + 2, 4, hipMemcpyDeviceToHost, c->stream));   // problems that left, all sub-batches
+    HIP_OK(c, hipMemcpyAsync(c->h_done.as<int>(), c->F.n_done, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->h_done.as<int>() + 1, c->F.n_done + 2, 4, hipMemcpyDeviceToHost, c->stream));   // problems that left, all sub-batches
     HIP_OK(c, hipStreamSynchronize(c->stream));
     // a lead phase: every problem must have LEFT the single-launch kernel at the stage boundary (or finished): one that stopped
     // at the round cap mid-history would be continued by the chained step kernel, whose two-loop direction reads Gram rows the
     // single-launch kernel (compact direction form) does not maintain
-    *complete = c->h_done[ph.pause_stage <= MVFIT_MAX_STAGES ? 1 : 0];
+    *complete = c->h_done.as<int>()[ph.pause_stage <= MVFIT_MAX_STAGES ? 1 : 0];
     // automatic mode: a fit whose resident workgroups (or whose optimiser) gave up waiting has shown that the launch does not get
     // the CUs the choice assumes (a shared device, a CU mask): later fits on this ctx use the per-round launches
     if (tpw && c->opt.resident_pass < 0 && c->async_stats[3]) c->resident_auto_off = true;
@@ -1818,7 +1752,7 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
 
 // DRIVER_SPARSE: the persistent kernel alone, sub-batch after sub-batch
 static int run_sparse(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
-    int* h_done = c->h_done;
+    int* h_done = c->h_done.as<int>();
     *h_done = 0;
     for (const FitLaunch& L : ph.launches) {
         const int done_before = *h_done;          // (synchronised: problems finished by the earlier sub-batches)
@@ -1837,14 +1771,14 @@ static int run_sparse(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, con
 
 // DRIVER_EAGER: chained rounds as eager launches bracketed by events (bench.py's per-launch timing of the vertex pass)
 static int run_eager(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
-    int* h_done = c->h_done;
+    int* h_done = c->h_done.as<int>();
     for (int rounds = 0; rounds < ph.launch_cap;) {
         for (int r = 0; r < kGraphRounds; ++r) {
-            int rc = run_vertex_pass(c, c->d_verts);
-            if (!rc && c->F.sdf_adj) rc = run_sdf_term(c, c->d_verts, c->F.sdf_gate, c->stream);
+            int rc = run_vertex_pass(c, c->pb.verts);
+            if (!rc && c->F.sdf_adj) rc = run_sdf_term(c, c->pb.verts, c->F.sdf_gate, c->stream);
             if (rc) return rc;
             prof_begin(c, c->ev_step);
-            hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->V, SW, O,
+            hipLaunchKernelGGL(O.reuse_outer ? fit_step_kernel<true> : fit_step_kernel<false>, dim3(c->B), dim3(STEP_NT), step_gram_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->V, SW, O,
                                c->P, c->F);
             prof_end(c, c->ev_step);
         }
@@ -1861,7 +1795,7 @@ static int run_eager(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
 // DRIVER_GRAPH: chained rounds, kGraphRounds of them per graph replay
 static int run_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, const FitPhase& ph, int* complete) {
     const int B = c->B;
-    int* h_done = c->h_done;
+    int* h_done = c->h_done.as<int>();
     if (const int rc = ensure_round_graph(c, SW, O)) return rc;
     // While at most half of the problems have finished, the next replay is queued before the host looks at the
     // done counter of the current one (the GPU does not idle through the ~30 us host turnaround); later the
@@ -1939,14 +1873,14 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
         SW.w[s] = to_dev(sw[s]);
     }
     const bool any_sdf = in.sdf_stages != 0;
-    if (any_sdf && !c->sdf_num_faces && !c->obst_on)
+    if (any_sdf && !c->sdf_num_faces && !c->obst.on)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
-    if (c->obst_on) in.sdf_service = 0;          // the scene term runs in chained rounds only (no service path for it)
+    if (c->obst.on) in.sdf_service = 0;          // the scene term runs in chained rounds only (no service path for it)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;
     }
-    c->F.sdf_adj = any_sdf ? c->d_sdf_adj : nullptr;
+    c->F.sdf_adj = any_sdf ? c->pb.sdf_adj : nullptr;
     c->F.trace = c->trace; c->F.trace_cap = c->trace ? c->trace_cap : 0;
     LbOpts O;
     int rc = make_opts(c, o, sw[0].flags, O);
@@ -1963,7 +1897,7 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
     const int B = c->B;
     HIP_OK(c, hipMemsetAsync(c->F.n_done, 0, 12, c->stream));
     HIP_OK(c, hipMemsetAsync(c->F.sdf_gate, sw[0].coll_loss_weight > 0.f ? 1 : 0, (size_t)B * 4, c->stream));
-    hipLaunchKernelGGL(fit_init_kernel, dim3(B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->d_obs, c->P, c->F,
+    hipLaunchKernelGGL(fit_init_kernel, dim3(B), dim3(STEP_NT), step_lds(), c->stream, c->M, (const ObsBlock*)c->pb.obs, c->P, c->F,
                        (const float*)params,
                        sw[0].flags, plan.init_full_pass ? 1 : 0);
     HIP_OK(c, hipGetLastError());
@@ -2075,18 +2009,18 @@ extern "C" int mvfit_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, cons
     if (sdf_op_uses_lists(num_faces) && c->opt.sdf_face_lists) {
         if (c->sdf_op_B != B || c->sdf_op_F != num_faces) {       // a new shape: decide once (the decision, also a refusal, is kept)
             HIP_OK(c, hipStreamSynchronize(c->stream));
-            if (c->d_sdf_op_ws) { hipFree(c->d_sdf_op_ws); c->d_sdf_op_ws = nullptr; }
+            c->sdf_op_ws.reset();
             size_t free_b = 0, total_b = 0;
             HIP_OK(c, hipMemGetInfo(&free_b, &total_b));
             if (sdf_op_ws_bytes(B, num_faces) < free_b / 2) {
-                HIP_OK(c, hipMalloc(&c->d_sdf_op_ws, sdf_op_ws_bytes(B, num_faces)));
-                HIP_OK(c, hipMemsetAsync(reinterpret_cast<unsigned char*>(c->d_sdf_op_ws) + sdf_cull_zero_offset(B, num_faces), 0,
-                                         sdf_cull_zero_bytes(B), c->stream));
+                HIP_OK(c, c->sdf_op_ws.reserve(sdf_op_ws_bytes(B, num_faces)));
+                HIP_OK(c, hipMemsetAsync(c->sdf_op_ws.as<unsigned char>() + sdf_cull_zero_offset(B, num_faces), 0, sdf_cull_zero_bytes(B),
+                                         c->stream));
             }
             c->sdf_op_B = B; c->sdf_op_F = num_faces;
         }
-        if (c->d_sdf_op_ws) {
-            hipError_t e = launch_sdf_voxelize_culled(faces, num_faces, vertices, B, num_vertices, G, phi, c->d_sdf_op_ws, c->stream);
+        if (c->sdf_op_ws.get()) {
+            hipError_t e = launch_sdf_voxelize_culled(faces, num_faces, vertices, B, num_vertices, G, phi, c->sdf_op_ws.get(), c->stream);
             if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "sdf launch: %s", hipGetErrorString(e));
             c->sdf_op_path = 1;
             return MVFIT_OK;
@@ -2164,34 +2098,28 @@ static int scene_sdf_run(mvfit_ctx* c, const char* who, const float* vertices, i
     const size_t o_part = o_box + al((size_t)N * 16), o_local = o_part + al((size_t)nb_max * nblk * 4);
     const size_t o_phi = o_local + al((size_t)nb_max * num_vertices * 12), o_cull = o_phi + (phi_out ? 0 : al((size_t)nb_max * nvox * 4));
     size_t need = o_cull + (lists ? sdf_op_ws_bytes(run, num_faces) : 0);
-    if (need > c->scn_ws_size) {
-        if (c->d_scn_ws) hipFree(c->d_scn_ws);
-        c->d_scn_ws = nullptr; c->scn_ws_size = 0;
+    if (need > c->scn_ws.size()) {
+        c->scn_ws.reset();
         size_t free_b = 0, total_b = 0;
         HIP_OK(c, hipMemGetInfo(&free_b, &total_b));
         while (run > 1 && need > free_b / 2) {
             run = (run + 1) / 2;
             need = o_cull + sdf_op_ws_bytes(run, num_faces);
         }
-        HIP_OK(c, hipMalloc(&c->d_scn_ws, need));
-        c->scn_ws_size = need;
+        HIP_OK(c, c->scn_ws.reserve(need));
     }
     const size_t tb = o_box;                     // tables: a row per body, then scene_first
-    if (tb > c->h_scn_tab_bytes) {
-        if (c->h_scn_tab) hipHostFree(c->h_scn_tab);
-        c->h_scn_tab = nullptr; c->h_scn_tab_bytes = 0;
-        HIP_OK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_scn_tab), tb));
-        c->h_scn_tab_bytes = tb;
-    }
+    HIP_OK(c, c->h_scn_tab.reserve(tb));
+    int32_t* h_tab = c->h_scn_tab.as<int32_t>();
     for (int s = 0; s < num_scenes; ++s)
         for (int b = scene_first[s]; b < scene_first[s + 1]; ++b) {
-            int32_t* r = c->h_scn_tab + (size_t)b * 4;
+            int32_t* r = h_tab + (size_t)b * 4;
             r[0] = scene_first[s]; r[1] = scene_first[s + 1] - scene_first[s]; r[2] = 0; r[3] = 0;
         }
-    memcpy(reinterpret_cast<unsigned char*>(c->h_scn_tab) + o_first, scene_first, (size_t)(num_scenes + 1) * 4);
-    unsigned char* ws = reinterpret_cast<unsigned char*>(c->d_scn_ws);
-    HIP_OK(c, hipMemcpyAsync(ws, c->h_scn_tab, tb, hipMemcpyHostToDevice, c->stream));
-    if (freeze) HIP_OK(c, hipMemcpyAsync(keep_tab, c->h_scn_tab, (size_t)N * 16, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->h_scn_tab.as<unsigned char>() + o_first, scene_first, (size_t)(num_scenes + 1) * 4);
+    unsigned char* ws = c->scn_ws.as<unsigned char>();
+    HIP_OK(c, hipMemcpyAsync(ws, h_tab, tb, hipMemcpyHostToDevice, c->stream));
+    if (freeze) HIP_OK(c, hipMemcpyAsync(keep_tab, h_tab, (size_t)N * 16, hipMemcpyHostToDevice, c->stream));
     float4* box = freeze ? keep_box : reinterpret_cast<float4*>(ws + o_box);
     float* part = reinterpret_cast<float*>(ws + o_part);
     float* local = reinterpret_cast<float*>(ws + o_local);
@@ -2239,7 +2167,7 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (!c) return MVFIT_E_ARG;
     HIP_OK(c, hipSetDevice(c->device));
     if (!vertices) {                                         // remove: the buffers stay for the next freeze of this batch
-        c->obst_on = false;
+        c->obst.on = false;
         return MVFIT_OK;
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
@@ -2254,34 +2182,34 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (scene_first[num_scenes] != c->B)
         return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: the scenes hold %d bodies, the ctx %d problems", scene_first[num_scenes], c->B);
     const size_t nvox = (size_t)grid_size * grid_size * grid_size;
-    if (c->obst_grid != grid_size || !c->d_obst_phi) {
+    if (c->obst.grid != grid_size || !c->obst.phi) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
         free_obstacles(c);
-        HIP_OK(c, hipMalloc(&c->d_obst_tab, (size_t)c->B * 16));
-        HIP_OK(c, hipMalloc(&c->d_obst_box, (size_t)c->B * sizeof(float4)));
-        HIP_OK(c, hipMalloc(&c->d_obst_phi, (size_t)c->B * nvox * 4));
-        c->obst_grid = grid_size;
+        HIP_OK(c, c->obst_mem.alloc(&c->obst.tab, (size_t)c->B * 16));
+        HIP_OK(c, c->obst_mem.alloc(&c->obst.box, (size_t)c->B * sizeof(float4)));
+        HIP_OK(c, c->obst_mem.alloc(&c->obst.phi, (size_t)c->B * nvox * 4));
+        c->obst.grid = grid_size;
     }
-    c->obst_on = false;                                      // a failed freeze leaves no term behind
+    c->obst.on = false;                                      // a failed freeze leaves no term behind
     rc = ensure_sdf_buffers(c);
     if (rc) return rc;
-    hipError_t e = launch_scene_null_boxes(c->d_sdf_box, c->B, c->stream);
+    hipError_t e = launch_scene_null_boxes(c->pb.sdf_box, c->B, c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_set_scene_obstacles: box launch: %s", hipGetErrorString(e));
     rc = scene_sdf_run(c, "mvfit_set_scene_obstacles", vertices, c->nv, c->d_faces, c->num_faces, scene_first, num_scenes, grid_size,
-                       scale_factor, robustifier, nullptr, nullptr, c->d_obst_phi, c->d_obst_box, c->d_obst_tab);
+                       scale_factor, robustifier, nullptr, nullptr, c->obst.phi, c->obst.box, c->obst.tab);
     if (rc) return rc;
-    c->obst_rob = robustifier;
-    c->obst_on = true;
+    c->obst.rob = robustifier;
+    c->obst.on = true;
     return MVFIT_OK;
 }
 
 extern "C" int mvfit_scene_obstacles_read(mvfit_ctx* c, float* phi, float* boxes) {
     if (!c) return MVFIT_E_ARG;
-    if (!c->obst_on) return fail(c, MVFIT_E_STATE, "mvfit_scene_obstacles_read: no obstacles are set");
+    if (!c->obst.on) return fail(c, MVFIT_E_STATE, "mvfit_scene_obstacles_read: no obstacles are set");
     HIP_OK(c, hipSetDevice(c->device));
-    const size_t nvox = (size_t)c->obst_grid * c->obst_grid * c->obst_grid;
-    if (phi) HIP_OK(c, hipMemcpyAsync(phi, c->d_obst_phi, (size_t)c->B * nvox * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (boxes) HIP_OK(c, hipMemcpyAsync(boxes, c->d_obst_box, (size_t)c->B * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    const size_t nvox = (size_t)c->obst.grid * c->obst.grid * c->obst.grid;
+    if (phi) HIP_OK(c, hipMemcpyAsync(phi, c->obst.phi, (size_t)c->B * nvox * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (boxes) HIP_OK(c, hipMemcpyAsync(boxes, c->obst.box, (size_t)c->B * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 
@@ -2362,16 +2290,11 @@ extern "C" int mvfit_associate_views(mvfit_ctx* c, int F, int V, int Nmax, const
     const size_t cap = (size_t)256 << 20, per = assoc_frame_bytes(D);
     const int group = (int)std::min<size_t>({(size_t)F, std::max<size_t>(1, (cap - assoc_head_bytes()) / per), (size_t)32768});
     const size_t need = assoc_head_bytes() + (size_t)group * per;
-    if (need > c->assoc_ws_size) {
-        HIP_OK(c, hipStreamSynchronize(c->stream));          // an earlier call may still run on the old one
-        if (c->d_assoc_ws) hipFree(c->d_assoc_ws);
-        c->d_assoc_ws = nullptr; c->assoc_ws_size = 0;
-        HIP_OK(c, hipMalloc(&c->d_assoc_ws, need));
-        c->assoc_ws_size = need;
-    }
+    if (need > c->assoc_ws.size()) HIP_OK(c, hipStreamSynchronize(c->stream));          // an earlier call may still run on the old one
+    HIP_OK(c, c->assoc_ws.reserve(need));
     for (int f0 = 0; f0 < F; f0 += group) {
         const hipError_t e = launch_associate_group(keypoints, count, intris, extris, f0, std::min(group, F - f0), V, Nmax, max_cost,
-                                                    min_joints, min_views, c->d_assoc_ws, cost_out, labels, num_clusters, c->stream);
+                                                    min_joints, min_views, c->assoc_ws.get(), cost_out, labels, num_clusters, c->stream);
         if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_associate_views: launch: %s", hipGetErrorString(e));
     }
     return MVFIT_OK;
@@ -2411,21 +2334,10 @@ extern "C" int mvfit_project_points(mvfit_ctx* c, const float* points, int num_p
 
 // grows the renderer's workspace and normal buffer (kept in the ctx) to at least ws / nb bytes
 static int render_reserve(mvfit_ctx* c, size_t ws, size_t nb) {
-    if (ws > c->render_ws_size || nb > c->render_nrm_bytes) {
+    if (ws > c->render_ws.size() || nb > c->render_nrm.size())
         HIP_OK(c, hipStreamSynchronize(c->stream));             // earlier calls may still read the old buffers
-        if (ws > c->render_ws_size) {
-            if (c->d_render_ws) hipFree(c->d_render_ws);
-            c->d_render_ws = nullptr; c->render_ws_size = 0;
-            HIP_OK(c, hipMalloc(&c->d_render_ws, ws));
-            c->render_ws_size = ws;
-        }
-        if (nb > c->render_nrm_bytes) {
-            if (c->d_render_nrm) hipFree(c->d_render_nrm);
-            c->d_render_nrm = nullptr; c->render_nrm_bytes = 0;
-            HIP_OK(c, hipMalloc(&c->d_render_nrm, nb));
-            c->render_nrm_bytes = nb;
-        }
-    }
+    HIP_OK(c, c->render_ws.reserve(ws));
+    HIP_OK(c, c->render_nrm.reserve(nb));
     return MVFIT_OK;
 }
 
@@ -2452,13 +2364,13 @@ extern "C" int mvfit_render_overlay(mvfit_ctx* c, const float* vertices, const f
     const size_t ws = render_ws_bytes(G, c->nv, c->num_faces, height, width);
     const size_t nb = (size_t)c->B * c->nv * 3 * sizeof(double);
     if (int rc = render_reserve(c, ws, nb)) return rc;
-    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->d_render_nrm, c->stream);
+    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->render_nrm.as<double>(), c->stream);
     const size_t px = (size_t)height * width;
     for (int i0 = 0; i0 < num_images && e == hipSuccess; i0 += G) {
         const int n = std::min(G, num_images - i0);
-        e = launch_render_group(c->Q, image_problem + i0, image_view + i0, n, vertices, c->d_render_nrm, c->nv, c->d_faces,
+        e = launch_render_group(c->Q, image_problem + i0, image_view + i0, n, vertices, c->render_nrm.as<double>(), c->nv, c->d_faces,
                                 c->num_faces, points, points ? num_points : 0, height, width, images + (size_t)i0 * px * 3,
-                                out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr, c->d_render_ws,
+                                out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr, c->render_ws.get(),
                                 c->stream);
     }
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "render launch: %s", hipGetErrorString(e));
@@ -2507,13 +2419,8 @@ extern "C" int mvfit_render_scene(mvfit_ctx* c, const float* vertices, const flo
     c->scene_slot ^= 1;
     if (c->scene_copied[slot]) HIP_OK(c, hipEventSynchronize(c->scene_copied[slot]));
     else HIP_OK(c, hipEventCreateWithFlags(&c->scene_copied[slot], hipEventDisableTiming));
-    if (tb > c->h_scene_tab_bytes[slot]) {
-        if (c->h_scene_tab[slot]) hipHostFree(c->h_scene_tab[slot]);
-        c->h_scene_tab[slot] = nullptr; c->h_scene_tab_bytes[slot] = 0;
-        HIP_OK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_scene_tab[slot]), tb));
-        c->h_scene_tab_bytes[slot] = tb;
-    }
-    int32_t* ti = c->h_scene_tab[slot];
+    HIP_OK(c, c->h_scene_tab[slot].reserve(tb));
+    int32_t* ti = c->h_scene_tab[slot].as<int32_t>();
     int32_t* tj = ti + (size_t)num_images * SCENE_IMAGE_WORDS;
     for (int i = 0; i < num_images; ++i) {
         const int first = image_first[i], cnt = image_first[i + 1] - first;
@@ -2542,24 +2449,19 @@ extern "C" int mvfit_render_scene(mvfit_ctx* c, const float* vertices, const flo
     }
     const size_t nb = (size_t)c->B * c->nv * 3 * sizeof(double);
     if (int rc = render_reserve(c, ws, nb)) return rc;
-    if (tb > c->scene_tab_bytes) {
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        if (c->d_scene_tab) hipFree(c->d_scene_tab);
-        c->d_scene_tab = nullptr; c->scene_tab_bytes = 0;
-        HIP_OK(c, hipMalloc(&c->d_scene_tab, tb));
-        c->scene_tab_bytes = tb;
-    }
-    HIP_OK(c, hipMemcpyAsync(c->d_scene_tab, c->h_scene_tab[slot], tb, hipMemcpyHostToDevice, c->stream));
+    if (tb > c->scene_tab.size()) HIP_OK(c, hipStreamSynchronize(c->stream));
+    HIP_OK(c, c->scene_tab.reserve(tb));
+    HIP_OK(c, hipMemcpyAsync(c->scene_tab.get(), ti, tb, hipMemcpyHostToDevice, c->stream));
     HIP_OK(c, hipEventRecord(c->scene_copied[slot], c->stream));
-    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->d_render_nrm, c->stream);
+    hipError_t e = launch_render_normals(vertices, c->B, c->nv, c->d_faces, c->d_vf_ptr, c->d_vf_idx, c->render_nrm.as<double>(), c->stream);
     const size_t px = (size_t)height * width;
     int i0 = 0;
     for (size_t g = 0; g < group_end.size() && e == hipSuccess; ++g) {
         const int i1 = group_end[g], j0 = image_first[i0], m = image_first[i1] - j0;
-        e = launch_scene_group(c->Q, c->d_scene_tab, num_images, i0, i1 - i0, j0, m, vertices, c->d_render_nrm, c->nv, c->d_faces,
+        e = launch_scene_group(c->Q, c->scene_tab.as<int32_t>(), num_images, i0, i1 - i0, j0, m, vertices, c->render_nrm.as<double>(), c->nv, c->d_faces,
                                c->num_faces, points, points ? num_points : 0, height, width, images + (size_t)i0 * px * 3,
                                out + (size_t)i0 * px * 3, face_id ? face_id + (size_t)i0 * px : nullptr,
-                               body_id ? body_id + (size_t)i0 * px : nullptr, c->d_render_ws, c->stream);
+                               body_id ? body_id + (size_t)i0 * px : nullptr, c->render_ws.get(), c->stream);
         i0 = i1;
     }
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "render launch: %s", hipGetErrorString(e));
@@ -2603,7 +2505,7 @@ static int profile_vertex_pass(mvfit_ctx* c, int launches, int flavour, double* 
         HIP_OK(c, hipMemset(R.pass_done, 0, 4 * kPassWords));
         ResidentArgs RA{};
         RA.coefH = R.coefH; RA.Amat = R.Amat; RA.tau = R.tau; RA.tag = R.tag; RA.done_round = R.done_round; RA.stats = R.stats;
-        RA.wg_round = R.pass_done; RA.verts = c->d_verts; RA.capture_round = -1; RA.nslots = R.nslots; RA.rb = R.Bpad;
+        RA.wg_round = R.pass_done; RA.verts = c->pb.verts; RA.capture_round = -1; RA.nslots = R.nslots; RA.rb = R.Bpad;
         RA.b_lo = 0; RA.n = n; RA.max_rounds = (unsigned)rounds + 1u;
         hipEvent_t a, b;
         HIP_OK(c, hipEventCreate(&a)); HIP_OK(c, hipEventCreate(&b));
@@ -2620,9 +2522,9 @@ static int profile_vertex_pass(mvfit_ctx* c, int launches, int flavour, double* 
     }
     hipEvent_t a, b;
     HIP_OK(c, hipEventCreate(&a)); HIP_OK(c, hipEventCreate(&b));
-    hipError_t e = launch_vertex_pass(c->M, P, c->B, c->d_verts, c->opt.pass_kernel, c->stream);      // warm
+    hipError_t e = launch_vertex_pass(c->M, P, c->B, c->pb.verts, c->opt.pass_kernel, c->stream);      // warm
     HIP_OK(c, hipEventRecord(a, c->stream));
-    for (int i = 0; i < launches && e == hipSuccess; ++i) e = launch_vertex_pass(c->M, P, c->B, c->d_verts, c->opt.pass_kernel, c->stream);
+    for (int i = 0; i < launches && e == hipSuccess; ++i) e = launch_vertex_pass(c->M, P, c->B, c->pb.verts, c->opt.pass_kernel, c->stream);
     HIP_OK(c, hipEventRecord(b, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
@@ -2691,17 +2593,12 @@ extern "C" int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs,
     double *dx, *dtrace, *dfl, *ddirs, *dstps, *dro, *dgrow, *dgcol, *dcmat;
     int* dn;
     const size_t tb = (size_t)std::max(max_trace, 1) * (D + 1) * 8;
-    if (hipMalloc(&dx, LB_D * 8) || hipMalloc(&dtrace, tb) || hipMalloc(&dfl, 8) || hipMalloc(&dn, 4) ||
-        hipMalloc(&ddirs, LB_HIST * LB_D * 8) || hipMalloc(&dstps, LB_HIST * LB_D * 8) || hipMalloc(&dro, LB_HIST * 8) ||
-        hipMalloc(&dgrow, LB_GSIZE * 8) || hipMalloc(&dgcol, LB_GSIZE * 8) || hipMalloc(&dcmat, 3 * LB_HIST * LB_HIST * 8))
+    DevPool mem;                         // (every return frees what was allocated)
+    if (mem.alloc(&dx, LB_D * 8) || mem.alloc(&dtrace, tb, true) || mem.alloc(&dfl, 8) || mem.alloc(&dn, 4) ||
+        mem.alloc(&ddirs, LB_HIST * LB_D * 8, true) || mem.alloc(&dstps, LB_HIST * LB_D * 8, true) || mem.alloc(&dro, LB_HIST * 8) ||
+        mem.alloc(&dgrow, LB_GSIZE * 8, true) || mem.alloc(&dgcol, LB_GSIZE * 8, true) || mem.alloc(&dcmat, 3 * LB_HIST * LB_HIST * 8, true))
         return MVFIT_E_HIP;
     hipMemcpy(dx, x_inout, D * 8, hipMemcpyHostToDevice);
-    hipMemset(dtrace, 0, tb);
-    hipMemset(dgrow, 0, LB_GSIZE * 8);
-    hipMemset(dgcol, 0, LB_GSIZE * 8);
-    hipMemset(ddirs, 0, LB_HIST * LB_D * 8);
-    hipMemset(dstps, 0, LB_HIST * LB_D * 8);
-    hipMemset(dcmat, 0, 3 * LB_HIST * LB_HIST * 8);
     hipLaunchKernelGGL(lbfgs_kat_kernel, dim3(1), dim3(64), 0, 0, kind, D, O, dx, dtrace, max_trace, dn, dfl, ddirs, dstps, dro,
                        dgrow, dgcol, dcmat);
     hipError_t e = hipDeviceSynchronize();
@@ -2709,6 +2606,5 @@ extern "C" int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs,
     if (trace && max_trace > 0) hipMemcpy(trace, dtrace, tb, hipMemcpyDeviceToHost);
     if (n_closure) hipMemcpy(n_closure, dn, 4, hipMemcpyDeviceToHost);
     if (final_loss) hipMemcpy(final_loss, dfl, 8, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dtrace); hipFree(dfl); hipFree(dn); hipFree(ddirs); hipFree(dstps); hipFree(dro); hipFree(dgrow); hipFree(dgcol); hipFree(dcmat);
     return e == hipSuccess ? MVFIT_OK : MVFIT_E_HIP;
 }

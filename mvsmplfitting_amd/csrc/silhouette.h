@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.h"
+
 namespace mvfit {
 
 struct SilState {
@@ -17,13 +19,11 @@ struct SilState {
     int nchunks = 0;                    // workgroups of the search kernel
     int body_min = 0, body_max = -1;    // range of image_body (checked against num_bodies at loss time)
     // device memory sized by (M, H, W, nv): fields, mask copy, row offsets, tables, fixed-point accumulators, term A partials
-    unsigned char* ws = nullptr;
-    size_t ws_size = 0;
+    DevBuf ws;
     size_t o_field = 0, o_mask = 0, o_row = 0, o_flags = 0, o_total = 0, o_cam = 0, o_body = 0, o_sbody = 0, o_simg = 0,
            o_first = 0, o_cfirst = 0, o_acc = 0, o_partA = 0;
     // device memory sized by the contour: points, chunk table, term B partials; grows to the largest set seen
-    unsigned char* cs = nullptr;
-    size_t cs_size = 0;
+    DevBuf cs;
     size_t o_xy = 0, o_chunk = 0, o_partB = 0;
     std::vector<int32_t> h_tab;         // host staging of the tables (kept while a copy may read it)
 };
@@ -33,6 +33,5 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
 int sil_read(const SilState& S, float* field, int32_t* contour_first, int32_t* contour_xy, hipStream_t stream, std::string& err);
 int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, float* loss,
              float* g_vertices, int32_t* winner, hipStream_t stream, std::string& err);
-void sil_free(SilState& S);
 
 }  // namespace mvfit

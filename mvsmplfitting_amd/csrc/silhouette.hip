@@ -373,12 +373,6 @@ static int sil_fail(std::string& err, int code, const char* fmt, ...) {
 
 static size_t sil_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-void sil_free(SilState& S) {
-    if (S.ws) hipFree(S.ws);
-    if (S.cs) hipFree(S.cs);
-    S = SilState();
-}
-
 int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, const int32_t* image_body, const float* cam_R,
             const float* cam_t, const float* cam_f, const float* cam_c, int stride, hipStream_t stream, std::string& err) {
     S.on = false;                                // a failed set leaves no mask set behind
@@ -390,13 +384,12 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
                  o_total = take((size_t)M * 4), o_cam = take((size_t)M * sizeof(SilCam)), o_body = take((size_t)M * 4),
                  o_sbody = take((size_t)M * 4), o_simg = take((size_t)M * 4), o_first = take((size_t)(M + 1) * 4),
                  o_cfirst = take((size_t)(M + 1) * 4), o_acc = take((size_t)M * nv * 16), o_partA = take((size_t)M * nblk * 8);
-    if (o != S.ws_size) {                        // a set of the same size reuses the workspace
+    if (o != S.ws.size()) {                      // a set of the same size reuses the workspace
         SIL_HIP(hipStreamSynchronize(stream));
-        if (S.ws) hipFree(S.ws);
-        S.ws = nullptr; S.ws_size = 0;
-        SIL_HIP(hipMalloc(reinterpret_cast<void**>(&S.ws), o));
-        S.ws_size = o;
+        S.ws.reset();
+        SIL_HIP(S.ws.reserve(o));
     }
+    unsigned char* const ws = S.ws.as<unsigned char>();
     S.M = M; S.H = H; S.W = W; S.stride = stride; S.nv = nv; S.C = 0; S.nchunks = 0;
     S.o_field = o_field; S.o_mask = o_mask; S.o_row = o_row; S.o_flags = o_flags; S.o_total = o_total; S.o_cam = o_cam;
     S.o_body = o_body; S.o_sbody = o_sbody; S.o_simg = o_simg; S.o_first = o_first; S.o_cfirst = o_cfirst; S.o_acc = o_acc;
@@ -420,14 +413,14 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
         reinterpret_cast<int32_t*>(hb + (o_sbody - o_cam))[i] = image_body[order[i]];
         reinterpret_cast<int32_t*>(hb + (o_simg - o_cam))[i] = order[i];
     }
-    SIL_HIP(hipMemcpyAsync(S.ws + o_cam, hb, tab_bytes, hipMemcpyHostToDevice, stream));
-    SIL_HIP(hipMemcpyAsync(S.ws + o_mask, masks, npix, hipMemcpyDefault, stream));
-    SIL_HIP(hipMemsetAsync(S.ws + o_flags, 0, (size_t)M * 4, stream));
-    const uint8_t* d_mask = S.ws + o_mask;
-    int* g2 = reinterpret_cast<int*>(S.ws + o_field);
-    int* flags = reinterpret_cast<int*>(S.ws + o_flags);
-    int* row = reinterpret_cast<int*>(S.ws + o_row);
-    int* total = reinterpret_cast<int*>(S.ws + o_total);
+    SIL_HIP(hipMemcpyAsync(ws + o_cam, hb, tab_bytes, hipMemcpyHostToDevice, stream));
+    SIL_HIP(hipMemcpyAsync(ws + o_mask, masks, npix, hipMemcpyDefault, stream));
+    SIL_HIP(hipMemsetAsync(ws + o_flags, 0, (size_t)M * 4, stream));
+    const uint8_t* d_mask = ws + o_mask;
+    int* g2 = reinterpret_cast<int*>(ws + o_field);
+    int* flags = reinterpret_cast<int*>(ws + o_flags);
+    int* row = reinterpret_cast<int*>(ws + o_row);
+    int* total = reinterpret_cast<int*>(ws + o_total);
     hipLaunchKernelGGL(sil_dt_cols_kernel, dim3((W + SIL_NT - 1) / SIL_NT, M), dim3(SIL_NT), 0, stream, d_mask, H, W, g2, flags);
     hipLaunchKernelGGL(sil_dt_rows_kernel, dim3(H, M), dim3(SIL_NT), (size_t)W * 4, stream, g2, H, W, (const int*)flags);
     const dim3 cgrid((H + SIL_NT / 64 - 1) / (SIL_NT / 64), M);
@@ -456,18 +449,14 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
     size_t oc = 0;
     auto takec = [&oc](size_t bytes) { const size_t at = oc; oc += sil_al(bytes); return at; };
     S.o_xy = takec((size_t)C * 8); S.o_chunk = takec((size_t)nch * sizeof(SilChunk)); S.o_partB = takec((size_t)nch * 8);
-    if (oc > S.cs_size) {
-        if (S.cs) hipFree(S.cs);
-        S.cs = nullptr; S.cs_size = 0;
-        SIL_HIP(hipMalloc(reinterpret_cast<void**>(&S.cs), oc));
-        S.cs_size = oc;
-    }
-    SIL_HIP(hipMemcpyAsync(S.ws + o_first, first.data(), (size_t)(M + 1) * 4, hipMemcpyHostToDevice, stream));
-    SIL_HIP(hipMemcpyAsync(S.ws + o_cfirst, cfirst.data(), (size_t)(M + 1) * 4, hipMemcpyHostToDevice, stream));
+    SIL_HIP(S.cs.reserve(oc));
+    unsigned char* const cs = S.cs.as<unsigned char>();
+    SIL_HIP(hipMemcpyAsync(ws + o_first, first.data(), (size_t)(M + 1) * 4, hipMemcpyHostToDevice, stream));
+    SIL_HIP(hipMemcpyAsync(ws + o_cfirst, cfirst.data(), (size_t)(M + 1) * 4, hipMemcpyHostToDevice, stream));
     if (nch) {
-        SIL_HIP(hipMemcpyAsync(S.cs + S.o_chunk, chunks.data(), (size_t)nch * sizeof(SilChunk), hipMemcpyHostToDevice, stream));
+        SIL_HIP(hipMemcpyAsync(cs + S.o_chunk, chunks.data(), (size_t)nch * sizeof(SilChunk), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(sil_contour_kernel<true>, cgrid, dim3(SIL_NT), 0, stream, d_mask, H, W, row, stride,
-                           reinterpret_cast<const int*>(S.ws + o_first), reinterpret_cast<int2*>(S.cs + S.o_xy));
+                           reinterpret_cast<const int*>(ws + o_first), reinterpret_cast<int2*>(cs + S.o_xy));
         SIL_HIP(hipGetLastError());
     }
     SIL_HIP(hipStreamSynchronize(stream));       // the host tables above are free again
@@ -477,35 +466,37 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
 }
 
 int sil_read(const SilState& S, float* field, int32_t* contour_first, int32_t* contour_xy, hipStream_t stream, std::string& err) {
-    if (field) SIL_HIP(hipMemcpyAsync(field, S.ws + S.o_field, (size_t)S.M * S.H * S.W * 4, hipMemcpyDeviceToDevice, stream));
+    const unsigned char *ws = S.ws.as<unsigned char>(), *cs = S.cs.as<unsigned char>();
+    if (field) SIL_HIP(hipMemcpyAsync(field, ws + S.o_field, (size_t)S.M * S.H * S.W * 4, hipMemcpyDeviceToDevice, stream));
     if (contour_first)
-        SIL_HIP(hipMemcpyAsync(contour_first, S.ws + S.o_first, (size_t)(S.M + 1) * 4, hipMemcpyDeviceToDevice, stream));
+        SIL_HIP(hipMemcpyAsync(contour_first, ws + S.o_first, (size_t)(S.M + 1) * 4, hipMemcpyDeviceToDevice, stream));
     if (contour_xy && S.C)
-        SIL_HIP(hipMemcpyAsync(contour_xy, S.cs + S.o_xy, (size_t)S.C * 8, hipMemcpyDeviceToDevice, stream));
+        SIL_HIP(hipMemcpyAsync(contour_xy, cs + S.o_xy, (size_t)S.C * 8, hipMemcpyDeviceToDevice, stream));
     return MVFIT_OK;
 }
 
 int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, float* loss,
              float* g_vertices, int32_t* winner, hipStream_t stream, std::string& err) {
     const int nv = S.nv, nblk = (nv + SIL_NT - 1) / SIL_NT;
-    const SilCam* cams = reinterpret_cast<const SilCam*>(S.ws + S.o_cam);
-    const int* sbody = reinterpret_cast<const int*>(S.ws + S.o_sbody);
-    const int* simg = reinterpret_cast<const int*>(S.ws + S.o_simg);
+    unsigned char *ws = S.ws.as<unsigned char>(), *cs = S.cs.as<unsigned char>();
+    const SilCam* cams = reinterpret_cast<const SilCam*>(ws + S.o_cam);
+    const int* sbody = reinterpret_cast<const int*>(ws + S.o_sbody);
+    const int* simg = reinterpret_cast<const int*>(ws + S.o_simg);
     const bool accumulate = g_vertices && S.nchunks;
-    unsigned long long* acc = accumulate ? reinterpret_cast<unsigned long long*>(S.ws + S.o_acc) : nullptr;
+    unsigned long long* acc = accumulate ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
     if (accumulate) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * nv * 16, stream));
     if (S.nchunks)
         hipLaunchKernelGGL(sil_search_kernel, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
-                           reinterpret_cast<const int*>(S.ws + S.o_body), reinterpret_cast<const SilChunk*>(S.cs + S.o_chunk),
-                           reinterpret_cast<const int2*>(S.cs + S.o_xy), sigma, S.stride, acc,
-                           reinterpret_cast<double*>(S.cs + S.o_partB), winner);
+                           reinterpret_cast<const int*>(ws + S.o_body), reinterpret_cast<const SilChunk*>(cs + S.o_chunk),
+                           reinterpret_cast<const int2*>(cs + S.o_xy), sigma, S.stride, acc,
+                           reinterpret_cast<double*>(cs + S.o_partB), winner);
     hipLaunchKernelGGL(sil_vertex_kernel, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg, S.M,
-                       reinterpret_cast<const float*>(S.ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(S.ws + S.o_flags),
+                       reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(ws + S.o_flags),
                        w_in, w_out, sigma, reinterpret_cast<const long long*>(acc), g_vertices,
-                       reinterpret_cast<double*>(S.ws + S.o_partA));
+                       reinterpret_cast<double*>(ws + S.o_partA));
     hipLaunchKernelGGL(sil_loss_kernel, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
-                       reinterpret_cast<const double*>(S.ws + S.o_partA), nblk,
-                       reinterpret_cast<const double*>(S.cs + S.o_partB), reinterpret_cast<const int*>(S.ws + S.o_cfirst), w_in,
+                       reinterpret_cast<const double*>(ws + S.o_partA), nblk,
+                       reinterpret_cast<const double*>(cs + S.o_partB), reinterpret_cast<const int*>(ws + S.o_cfirst), w_in,
                        w_out, S.stride, loss);
     SIL_HIP(hipGetLastError());
     return MVFIT_OK;
