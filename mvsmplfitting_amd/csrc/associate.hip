@@ -33,6 +33,7 @@
 
 #include "camera_math.h"
 #include "wave_ops.h"
+#include "launchers.h"
 
 namespace mvfit {
 

@@ -131,4 +131,12 @@ FitPlan plan_fit(const FitPlanIn& in) {
     return plan;
 }
 
+PersistentVariant plan_persistent_variant(bool sdf_service, bool queue, bool helpers, bool reuse_outer, bool lean) {
+    if (sdf_service) return helpers ? PV_SDF_HELPERS : PV_SDF;
+    if (queue) return lean ? PV_QUEUE_LEAN : PV_QUEUE;
+    if (helpers) return reuse_outer ? PV_HELPERS_REUSE : PV_HELPERS;
+    if (reuse_outer) return lean ? PV_REUSE_LEAN : PV_REUSE;
+    return lean ? PV_LEAN : PV_PLAIN;
+}
+
 }  // namespace mvfit

@@ -84,4 +84,23 @@ int plan_nsets(const FitPlanIn& in, int n, int vposer_sets, bool with_passes);
 // workgroups of the resident pass in form 1 / 3 (FitPhase::form)
 int plan_resident_grid(int form, int ntiles);
 
+// The instantiations of the single-launch kernel (fit_kernels.hip: persistent_kernel() names one kernel per value):
+// fit_persistent_kernel<REMOTE, REUSE, LEAN, SDFS, QUEUE>
+enum PersistentVariant {
+    PV_PLAIN = 0,          // <0,0,0>
+    PV_LEAN,               // <0,0,1>      the stage flags carry none of VPoser / GMM / 3-D term
+    PV_REUSE,              // <0,1,0>      MVFIT_F_REUSE_OUTER_VALUE
+    PV_REUSE_LEAN,         // <0,1,1>
+    PV_HELPERS,            // <1,0,0>      the launch carries decoder helpers
+    PV_HELPERS_REUSE,      // <1,1,0>
+    PV_QUEUE,              // <0,0,0,0,1>  the launch has a work queue
+    PV_QUEUE_LEAN,         // <0,0,1,0,1>
+    PV_SDF,                // <0,0,0,1>    the launch serves stages with the SDF term
+    PV_SDF_HELPERS,        // <1,0,0,1>
+    PV_COUNT
+};
+// which one a launch runs: the service first, then the queue, then helpers; reuse_outer and lean count only where the row above
+// has an instantiation for them
+PersistentVariant plan_persistent_variant(bool sdf_service, bool queue, bool helpers, bool reuse_outer, bool lean);
+
 }  // namespace mvfit

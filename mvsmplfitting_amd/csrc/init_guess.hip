@@ -9,6 +9,7 @@
 
 #include "camera_math.h"
 #include "lapack_svd3.h"
+#include "launchers.h"
 
 namespace mvfit {
 

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "mvfit_device.h"
+#include "launchers.h"
 
 namespace mvfit {
 

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "mvfit_device.h"
+#include "launchers.h"
 
 #pragma clang fp contract(off)
 
@@ -51,7 +52,7 @@ struct RenderGroup {           // the images of one group: problem and view per 
     int view[RENDER_GROUP_MAX];
 };
 
-struct RenderWs {              // one group's workspace (mvfit_api.hip sizes it)
+struct RenderWs {              // one group's workspace (mvfit_scene.hip sizes it)
     RenderVert* vert;          // [G][Nv]
     float4* pcam;              // [G][Nv] camera-space position (w unused)
     double* ncam;              // [G][Nv][3] camera-space unit normal

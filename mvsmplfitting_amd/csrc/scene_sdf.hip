@@ -26,6 +26,7 @@
 #include "mvfit_device.h"
 #include "wave_ops.h"
 #include "sdf_entries.h"
+#include "launchers.h"
 
 namespace mvfit {
 

@@ -16,6 +16,7 @@
 // ~60 FMA-class ops per triangle.  Arithmetic is kept un-contracted (no FMA fusion) so that it is
 // the expression tree of the restatement in oracle/sdf_np.py.
 #include "sdf_device.h"
+#include "launchers.h"
 
 namespace mvfit {
 

@@ -1,4 +1,4 @@
-// Host interface of the silhouette term (silhouette.hip) as mvfit_api.hip drives it: the mask set a ctx keeps between
+// Host interface of the silhouette term (silhouette.hip) as mvfit_scene.hip drives it: the mask set a ctx keeps between
 // mvfit_set_silhouettes and the loss calls.  Every function returns an MVFIT_* code and, on failure, a message in err.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // Reverse mode of mvfit_vertices (include/mvfit.h: mvfit_vertices_backward): the vector-Jacobian product of
 // (vertices, keypoints) = SMPL.forward (body_models_scale.py:327-412, lbs.py:135-222) at the parameters x.
 //
-//   prep_kernel (mvfit_api.hip)   x -> blendshape coefficients (coefT), skinning transforms (Amat): the pass's operands
+//   prep_kernel (fit_kernels.hip)   x -> blendshape coefficients (coefT), skinning transforms (Amat): the pass's operands
 //   vjp_tile_kernel               one workgroup per (vertex slice, 32-problem chunk): the dense part of the adjoint over the
 //                                 slice's vertices, from the vertex cotangent, into one partial record per problem
 //   vjp_reduce_kernel             the slice partials of a problem, added in slice order -> one SdfAdj-shaped record
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "closure_device.h"
+#include "launchers.h"
 
 namespace mvfit {
 

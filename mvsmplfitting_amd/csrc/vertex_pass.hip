@@ -27,6 +27,7 @@
 #include <utility>
 #include <hip/hip_ext.h>
 #include "mvfit_device.h"
+#include "launchers.h"
 
 namespace mvfit {
 
@@ -1370,7 +1371,7 @@ __global__ __launch_bounds__(VP_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if constexpr (P == 0) tq = tau_0[bb]; else tq = tau_1[bb];
             const float tau3[3] = {tq.x, tq.y, tq.z};
             // the problem this ring row held in this round (the translation word's spare lane; rows take new problems from the
-            // launch's work queue when theirs has finished - mvfit_api.hip: fit_persistent_kernel)
+            // launch's work queue when theirs has finished - fit_kernels.hip: fit_persistent_kernel)
             // (through a float rvalue: __builtin_bit_cast applied to the swizzle expression `tq.w` itself reads the VECTOR's first
             // four bytes - element x - with this compiler, ROCm 7.2 clang; found as a memory fault, confirmed on a ten-line kernel)
             const float tq_w = tq.w;

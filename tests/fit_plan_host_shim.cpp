@@ -42,6 +42,11 @@ extern "C" int fit_plan_nsets(const int32_t* in, int n, int vposer_sets, int wit
     return plan_nsets(inputs(in), n, vposer_sets, with_passes != 0);
 }
 
+extern "C" int fit_plan_persistent_variant(int sdf_service, int queue, int helpers, int reuse_outer, int lean) {
+    return plan_persistent_variant(sdf_service != 0, queue != 0, helpers != 0, reuse_outer != 0, lean != 0);
+}
+extern "C" int fit_plan_persistent_variant_count() { return PV_COUNT; }
+
 // kAsyncMaxB, kResidentMaxB, kPassWords, kVpsSets, kVpsMaxSparse, kVpsMaxAsync, VPS_PMAX, VPS_MAX_SETS, VPS_SLICES, MVFIT_MAX_STAGES
 extern "C" void fit_plan_constants(int32_t* out10) {
     const int v[10] = {kAsyncMaxB, kResidentMaxB, kPassWords, kVpsSets, kVpsMaxSparse, kVpsMaxAsync, VPS_PMAX, VPS_MAX_SETS, VPS_SLICES,

@@ -375,3 +375,37 @@ def test_properties_of_every_batch_size(shim):
                 else:
                     r = rows(ph)
                     assert r[0][0] == 0 and r[-1][1] == B and all(a[1] == b[0] for a, b in zip(r, r[1:])), where
+
+
+# ---- which instantiation of the single-launch kernel a launch runs (fit_plan.h: PersistentVariant) ----
+PLAIN, LEAN, REUSE, REUSE_LEAN, HELPERS, HELPERS_REUSE, QUEUE, QUEUE_LEAN, SDF_SERVICE, SDF_HELPERS = range(10)
+# (sdf_service, queue, helpers, reuse_outer, lean) -> variant: the service first, then the queue, then the helpers; reuse_outer
+# and lean count only where the row above has an instantiation for them.  All 32 rows, written out.
+VARIANTS = {
+    (0, 0, 0, 0, 0): PLAIN,         (0, 0, 0, 0, 1): LEAN,
+    (0, 0, 0, 1, 0): REUSE,         (0, 0, 0, 1, 1): REUSE_LEAN,
+    (0, 0, 1, 0, 0): HELPERS,       (0, 0, 1, 0, 1): HELPERS,
+    (0, 0, 1, 1, 0): HELPERS_REUSE, (0, 0, 1, 1, 1): HELPERS_REUSE,
+    (0, 1, 0, 0, 0): QUEUE,         (0, 1, 0, 0, 1): QUEUE_LEAN,
+    (0, 1, 0, 1, 0): QUEUE,         (0, 1, 0, 1, 1): QUEUE_LEAN,
+    (0, 1, 1, 0, 0): QUEUE,         (0, 1, 1, 0, 1): QUEUE_LEAN,
+    (0, 1, 1, 1, 0): QUEUE,         (0, 1, 1, 1, 1): QUEUE_LEAN,
+    (1, 0, 0, 0, 0): SDF_SERVICE,   (1, 0, 0, 0, 1): SDF_SERVICE,
+    (1, 0, 0, 1, 0): SDF_SERVICE,   (1, 0, 0, 1, 1): SDF_SERVICE,
+    (1, 0, 1, 0, 0): SDF_HELPERS,   (1, 0, 1, 0, 1): SDF_HELPERS,
+    (1, 0, 1, 1, 0): SDF_HELPERS,   (1, 0, 1, 1, 1): SDF_HELPERS,
+    (1, 1, 0, 0, 0): SDF_SERVICE,   (1, 1, 0, 0, 1): SDF_SERVICE,
+    (1, 1, 0, 1, 0): SDF_SERVICE,   (1, 1, 0, 1, 1): SDF_SERVICE,
+    (1, 1, 1, 0, 0): SDF_HELPERS,   (1, 1, 1, 0, 1): SDF_HELPERS,
+    (1, 1, 1, 1, 0): SDF_HELPERS,   (1, 1, 1, 1, 1): SDF_HELPERS,
+}
+
+
+@pytest.mark.parametrize('case', sorted(VARIANTS), ids=lambda c: ''.join(map(str, c)))
+def test_persistent_variant(shim, case):
+    assert shim.fit_plan_persistent_variant(*case) == VARIANTS[case]
+
+
+def test_persistent_variant_count(shim):
+    assert len(VARIANTS) == 32
+    assert shim.fit_plan_persistent_variant_count() == 10 == len(set(VARIANTS.values()))

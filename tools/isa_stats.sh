@@ -1,14 +1,14 @@
 #!/bin/bash
-# Developer tool: emit the gfx950 ISA of mvfit_api.hip and print, per fit kernel, registers / scratch / code size and
+# Developer tool: emit the gfx950 ISA of fit_kernels.hip and print, per fit kernel, registers / scratch / code size and
 # instruction-class counts (the numbers DESIGN.md quotes: .private_segment_fixed_size, spills, barriers).
-# usage: tools/isa_stats.sh [extra hipcc flags]     -> /tmp/mvfit_api.s
+# usage: tools/isa_stats.sh [extra hipcc flags]     -> /tmp/fit_kernels.s
 set -e
 cd "$(dirname "$0")/../mvsmplfitting_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-value -I../../include \
-    --cuda-device-only -S mvfit_api.hip -o /tmp/mvfit_api.s "$@" 2>/dev/null
+    --cuda-device-only -S fit_kernels.hip -o /tmp/fit_kernels.s "$@" 2>/dev/null
 python3 - <<'PY'
 import re
-txt = open('/tmp/mvfit_api.s').read()
+txt = open('/tmp/fit_kernels.s').read()
 meta = re.findall(r'\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+(\d+)\n\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n){0,4}?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)', txt)
 lines = txt.split('\n')
 for name, priv, sg, sgs, vg, vgs in meta:

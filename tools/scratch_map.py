@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Developer tool: where (between which barriers) a kernel of /tmp/mvfit_api.s touches scratch. usage: scratch_map.py <mangled-prefix>"""
+"""Developer tool: where (between which barriers) a kernel of /tmp/fit_kernels.s touches scratch. usage: scratch_map.py <mangled-prefix>"""
 import sys, collections
 name = sys.argv[1] if len(sys.argv) > 1 else '_ZN5mvfit21fit_persistent_kernelILb0ELb0ELb1E'
-lines = open('/tmp/mvfit_api.s').read().split('\n')
+lines = open('/tmp/fit_kernels.s').read().split('\n')
 a = next(i for i, l in enumerate(lines) if l.startswith(name))
 b = next(i for i in range(a, len(lines)) if lines[i].startswith('\t.amdhsa_kernel ' + name))
 body = [l for l in lines[a:b] if l.startswith('\t') and not l.startswith('\t.') and not l.startswith('\t;')]

@@ -1,10 +1,10 @@
-"""Developer tool: where the spill code of a fit kernel sits (tools/isa_stats.sh writes /tmp/mvfit_api.s first).
+"""Developer tool: where the spill code of a fit kernel sits (tools/isa_stats.sh writes /tmp/fit_kernels.s first).
 usage: python tools/scratch_where.py [substring of the mangled kernel name, default the lean single-launch kernel]"""
 import re
 import sys
 
 sub = sys.argv[1] if len(sys.argv) > 1 else 'fit_persistent_kernelILb0ELb0ELb1ELb0'
-lines = open('/tmp/mvfit_api.s').read().split('\n')
+lines = open('/tmp/fit_kernels.s').read().split('\n')
 a = next(i for i, l in enumerate(lines) if l.startswith('_ZN') and sub in l and ': ' in l and not l.startswith('\t'))
 name = lines[a].split(':')[0]
 b = next(i for i in range(a, len(lines)) if lines[i].startswith('\t.amdhsa_kernel ' + name))
