@@ -448,6 +448,32 @@ int mvfit_silhouettes_read(mvfit_ctx* ctx, float* field, int32_t* contour_first,
 int mvfit_silhouette_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float w_in, float w_out, float sigma,
                           float* loss, float* g_vertices, int32_t* winner);
 
+/* The silhouette loss as a term of the fit, over the ctx's current mask set (enable != 0; enable = 0 switches it off and
+ * ignores the other arguments).  While it is on, a weight set with coll_loss_weight > 0 adds to problem j
+ *   pen_j = coll_loss_weight^2 * L_j,
+ * L_j exactly loss[j] of mvfit_silhouette_loss(vertices of the trial point, num_bodies = B, w_in, w_out, sigma):
+ * image_body[i] is the problem index.  The term is linear in L; the weight enters squared like every other weight of
+ * mvfit_weights.  Its gradient is coll_loss_weight^2 times the pull-back of that call's g_vertices through the fp32 model to
+ * the parameters (the adjoint mvfit_vertices_backward computes); field, contour and winners are constants, as in the op, and
+ * the winners are searched anew at every trial point.  A problem with no image pays exactly 0: its loss and gradient have the
+ * bits they have without the term.  A problem's numbers do not depend on B, on its position in the batch or on the other
+ * problems' masks.
+ * mvfit_closure and mvfit_fit both honour the term.  mvfit_fit runs the stages that carry it as chained rounds (pass ->
+ * silhouette evaluation -> dense pull-back -> record -> step kernel, the term's kernels skipping finished problems);
+ * stages without it in front keep their single-launch phase.  MVFIT_F_SPARSE_VERTS is ignored while the term is active;
+ * MVFIT_F_VPOSER / FIX_SHAPE / FIX_SCALE behave as in the closure.  mvfit_sdf_term_read returns L_j in sums (the loss, not a
+ * root of it); samples: MVFIT_E_UNSUPPORTED.
+ * The mask set may be replaced while the term is on: the next fit uses the new set (the captured round graph is rebuilt when
+ * the new set has other sizes or another contour, and kept otherwise).  mvfit_set_silhouettes(num_images = 0) switches the
+ * term off, and so does a replacing set that fails or whose image_body reaches B (that call returns MVFIT_E_ARG);
+ * mvfit_set_problems with another B switches it off too.  The round's buffers (12 B Nv + 4 bytes of cotangent and loss, and
+ * 2112 ceil(Nv / 32) bytes of pull-back partials, per problem of the batch rounded up to 32) are allocated by the first enable
+ * and keep their addresses while B stays.
+ * One term slot per ctx: MVFIT_E_STATE while mvfit_set_sdf's term or scene obstacles are configured (and those two calls
+ * return it while this term is on).  MVFIT_E_STATE also without mvfit_set_problems or without a mask set.  MVFIT_E_ARG: a
+ * non-finite or negative w_in / w_out, a non-finite sigma, a mask set whose image_body lies outside [0, B). */
+int mvfit_set_silhouette_term(mvfit_ctx* ctx, int enable, float w_in, float w_out, float sigma);
+
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear
  * triangulation of the 17 keypoints from V calibrated views, batched over B frames.
  *   keypoints[B,V,17,3] float32 dev (u, v, confidence) ; intris[V,3,3], extris[V,4,4] float64 dev (the reference

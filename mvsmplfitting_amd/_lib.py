@@ -70,7 +70,8 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_closure', 'mvfit_vertices', 'mvfit_vertices_backward', 'mvfit_full_pose', 'mvfit_fit', 'mvfit_fit_trace', 'mvfit_fit_stats', 'mvfit_decoder_stats', 'mvfit_debug_capture_pass', 'mvfit_sdf', 'mvfit_set_sdf', 'mvfit_sdf_term_read', 'mvfit_triangulate', 'mvfit_depth_guess', 'mvfit_umeyama', 'mvfit_project_points', 'mvfit_gather', 'mvfit_profile', 'mvfit_profile_read', 'mvfit_profile_vertex_pass', 'mvfit_profile_vertex_pass_ex', 'mvfit_pass_profile',
            'mvfit_options_default', 'mvfit_create_ex', 'mvfit_set_options', 'mvfit_get_options', 'mvfit_sdf_info',
            'mvfit_lbfgs_kat', 'mvfit_render_overlay', 'mvfit_render_scene', 'mvfit_scene_sdf_loss', 'mvfit_set_scene_obstacles', 'mvfit_scene_obstacles_read',
-           'mvfit_associate_views', 'mvfit_set_silhouettes', 'mvfit_silhouettes_read', 'mvfit_silhouette_loss']
+           'mvfit_associate_views', 'mvfit_set_silhouettes', 'mvfit_silhouettes_read', 'mvfit_silhouette_loss',
+           'mvfit_set_silhouette_term']
 
 
 def load(path=None):
@@ -154,6 +155,8 @@ def load(path=None):
     lib.mvfit_silhouettes_read.restype = C.c_int
     lib.mvfit_silhouette_loss.argtypes = [vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, vp, vp, vp]
     lib.mvfit_silhouette_loss.restype = C.c_int
+    lib.mvfit_set_silhouette_term.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.mvfit_set_silhouette_term.restype = C.c_int
     lib.mvfit_full_pose.argtypes = [vp, vp, C.c_uint32, vp]
     lib.mvfit_full_pose.restype = C.c_int
     lib.mvfit_gather.argtypes = [vp, vp, vp, vp, C.c_size_t]

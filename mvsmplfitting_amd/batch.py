@@ -40,6 +40,7 @@ from .engine import MvFit, SCENE_PALETTE, stage_weights
 from .init_guess import init_guess_batch, initial_params
 from .scene_fit import refine_scenes
 from .sequence import fit_sequences
+from .silhouette import refine_fit
 
 
 # pose format -> the model kind whose joint tensor it maps (reference code/utils/utils.py:441-457 smpl_to_annotation)
@@ -209,10 +210,96 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scen
     return paths
 
 
+SILHOUETTE_DEFAULTS = dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31)
+
+
+def check_silhouettes(silhouettes, is_seq=False, scene_collision=None):
+    """fit_folder's ``silhouettes`` option with the defaults filled in, or ValueError."""
+    if not isinstance(silhouettes, dict) or 'mask_root' not in silhouettes or 'weight' not in silhouettes:
+        raise ValueError("silhouettes: a dict with at least 'mask_root' and 'weight' (the term's coll_loss_weight)")
+    unknown = set(silhouettes) - set(SILHOUETTE_DEFAULTS) - {'mask_root', 'weight'}
+    if unknown:
+        raise ValueError('silhouettes: unknown keys %s' % sorted(unknown))
+    if is_seq:
+        raise ValueError('silhouettes is not available with is_seq=True')
+    if scene_collision is not None:
+        raise ValueError('silhouettes and scene_collision both use the fit\'s one term slot: choose one')
+    cfg = dict(SILHOUETTE_DEFAULTS, **silhouettes)
+    if int(cfg['downscale']) < 1 or int(cfg['contour_stride']) < 1:
+        raise ValueError('silhouettes: downscale and contour_stride must be >= 1')
+    if not float(cfg['weight']) > 0.0:
+        raise ValueError('silhouettes: weight must be > 0')
+    return cfg
+
+
+def mask_path(mask_root, serial, camera, frame, person=None):
+    """The mask file of one view of one frame: `<mask_root>/<serial>/<camera>/<frame>.png`, or `<frame>_<id:03d>.png` for
+    person ``id`` of the multi-person path."""
+    name = frame + '.png' if person is None else '%s_%03d.png' % (frame, int(person))
+    return os.path.join(mask_root, serial, camera, name)
+
+
+def silhouette_workspace_bytes(M, H, W, Nv):
+    """The mask set's workspace of include/mvfit.h (mvfit_set_silhouettes), without the contour lists."""
+    return M * H * W * 5 + M * H * 4 + M * (16 * Nv + 8 * -(-Nv // 256) + 92) + 8
+
+
+def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problems, rig, num_verts):
+    """The silhouette refinement of one serial's fitted problems (silhouette.refine_fit, the term inside the engine's fit).
+
+    problems: [(frame index, person id or None)] per row of xf; cams: the serial's camera folder names, view v = rig row v;
+    rig = (R, t, f, c) of set_problems.  Every existing mask file of a (problem, view) is one image of that problem; masks
+    are brought to 1 / downscale of their resolution (io_formats.downscale_mask) and the cameras follow with f and c divided
+    by it.  Returns (params, report); the engine is left without mask set and term."""
+    k = int(cfg['downscale'])
+    found = []
+    for n, (f, person) in enumerate(problems):
+        for v, cam in enumerate(cams):
+            path = mask_path(cfg['mask_root'], serial, cam, frames[f][0], person)
+            if os.path.isfile(path):
+                found.append((n, v, path))
+    if not found:
+        raise ValueError('silhouettes: serial %s has no mask file under %s (looked for e.g. %s)'
+                         % (serial, cfg['mask_root'], mask_path(cfg['mask_root'], serial, cams[0], frames[problems[0][0]][0],
+                                                                problems[0][1])))
+    H0, W0 = iof.image_size(found[0][2])
+    M = len(found)
+
+    def need(kk):
+        return silhouette_workspace_bytes(M, -(-H0 // kk), -(-W0 // kk), int(num_verts))
+    if need(k) > int(cfg['max_mask_bytes']):
+        fit = k + 1
+        while need(fit) > int(cfg['max_mask_bytes']) and (-(-H0 // fit) > 2 or -(-W0 // fit) > 2):
+            fit += 1
+        raise ValueError('silhouettes: %d masks of %d x %d at downscale=%d need a workspace of %d bytes, more than '
+                         'max_mask_bytes=%d; the smallest downscale that fits is %d'
+                         % (M, H0, W0, k, need(k), int(cfg['max_mask_bytes']), fit))
+    masks = np.empty((M, -(-H0 // k), -(-W0 // k)), np.uint8)
+    for i, (_, _, path) in enumerate(found):
+        m = iof.read_mask(path)
+        if m.shape != (H0, W0):
+            raise ValueError('silhouettes: the masks of serial %s differ in size: %s is %s, %s is %s'
+                             % (serial, found[0][2], (H0, W0), path, m.shape))
+        masks[i] = iof.downscale_mask(m, k)
+    body = np.array([n for n, _, _ in found], np.int32)
+    view = np.array([v for _, v, _ in found])
+    R, t, f, c = (np.asarray(a, np.float32) for a in rig)
+    per_image = (R[view], t[view], (f[view] / np.float32(k)).astype(np.float32), (c[view] / np.float32(k)).astype(np.float32))
+    eng.set_silhouettes(masks, body, per_image, contour_stride=int(cfg['contour_stride']))
+    try:
+        out, report = refine_fit(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), w_in=float(cfg['w_in']),
+                                 w_out=float(cfg['w_out']), sigma=float(cfg['sigma']))
+    finally:
+        eng.clear_silhouettes()
+    report = dict(report, images=[(int(n), int(v)) for n, v, _ in found], mask_size=tuple(masks.shape[1:]))
+    return out, report
+
+
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
-               save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None):
+               save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
+               silhouettes=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -247,7 +334,19 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     ``association`` (the report of associate_serial) and ``timing`` an 'associate' entry (reading the detections
     included).  ValueError with persons=0 (one
     identity needs no association), for an unknown key, and with use_3d: the files' 3-D annotations are keyed by
-    ``person_id`` and matching them to tracks is not built."""
+    ``person_id`` and matching them to tracks is not built.
+    silhouettes: None, or dict(mask_root=..., weight=..., w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1,
+    max_mask_bytes=2**31) - after the batched keypoint fit the serial's problems are refined against person masks by
+    silhouette.refine_fit (the silhouette term inside the engine's fit) with the last stage's weights plus
+    coll_loss_weight = weight; a problem keeps the refined row only if its objective fell.  Mask files:
+    `<mask_root>/<serial>/<camera>/<frame>.png` for persons=0, `<frame>_<id:03d>.png` on the multi-person path (any Pillow
+    image, non-zero = person; io_formats.read_mask).  A missing file means that (problem, view) has no image; a serial with
+    no mask at all is a ValueError, and so are masks of different sizes within a serial.  downscale=k fits against masks of
+    1/k the resolution (io_formats.downscale_mask) with the rig's f and c divided by k.  ValueError for unknown keys, a
+    missing mask_root / weight, is_seq=True, together with scene_collision (one term slot), or when the mask workspace of
+    include/mvfit.h exceeds max_mask_bytes (the message names the smallest downscale that fits).  The serial's result gains
+    ``silhouette_report`` (refine_fit's, plus images = [(problem, view)] and mask_size), ``timing`` a 'silhouette' entry, and
+    ``final_loss`` is the refined objective."""
     import time as _time
 
     def _tick(key, t0):
@@ -278,6 +377,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         unknown = set(scene_collision) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
         if unknown:
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
+    sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision) if silhouettes is not None else None
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -458,6 +558,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             xf = xr.to(xf.dtype)
             final = torch.as_tensor(scene_report['loss'], dtype=final.dtype, device=final.device)
             _t = _tick('refine', _t)
+        silhouette_report = None
+        if sil_cfg is not None:
+            xr, silhouette_report = refine_serial_silhouettes(eng, xf, stages_for(bool(has.all()))[-1], sil_cfg, serial, cams,
+                                                              frames, [(int(f), int(p)) for f, p in prob], rig, eng.nv)
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('silhouette', _t)
         full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
         xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
         res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
@@ -478,6 +585,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                    problem_frame=pf, problem_person=pp, persons=sorted(set(pp.tolist())))
         if scene_report is not None:
             out['scene_report'] = scene_report
+        if silhouette_report is not None:
+            out['silhouette_report'] = silhouette_report
         if association is not None:
             out['association'] = association
         _t = _tick('write', _t)
@@ -575,6 +684,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                     eng.set_problems(rig, gt_xy, conf)
                 restarted = np.ones(F, bool)
             _t = _tick('fit', _t)
+            silhouette_report = None
+            if sil_cfg is not None:
+                xr, silhouette_report = refine_serial_silhouettes(eng, xf, stages_for(bool(has.all()))[-1], sil_cfg, serial, cams,
+                                                                  frames, [(f, None) for f in range(F)], rig, eng.nv)
+                xf = xr.to(xf.dtype)
+                final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
+                _t = _tick('silhouette', _t)
             full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
             xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
             res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
@@ -595,6 +711,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             results[serial] = dict(frames=[fr[0] for fr in frames], params=xf_h, final_loss=final_h,
                                    n_closure=ncl.cpu().numpy(), files=files, init=x0.cpu().numpy(), restarted=restarted,
                                    used_3d=has.copy(), views_per_frame=vmask.sum(1))
+            if silhouette_report is not None:
+                results[serial]['silhouette_report'] = silhouette_report
             _t = _tick('write', _t)
             if save_images:
                 results[serial]['images'] = render_serial_images(
@@ -608,4 +726,5 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     return results
 
 
-__all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS']
+__all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
+           'check_silhouettes', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes']

@@ -52,6 +52,8 @@ hipError_t launch_vertices_backward(const DevModel& M, const DevPose& P, int B, 
                                     const float* g_verts, const float* g_joints, float* part, SdfAdj* rec, float* g_params,
                                     hipStream_t stream);
 size_t vjp_part_bytes(int Bpad, int nv);
+hipError_t launch_silhouette_pullback(const DevModel& M, const DevPose& P, int B, int Bpad, const int* gate, const float* g_verts,
+                                      const float* loss, float* part, SdfAdj* rec, hipStream_t stream);
 hipError_t launch_render_group(const DevProblems& Q, const int* prob, const int* view, int n, const float* verts,
                                const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points, int num_points,
                                int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, void* ws_mem,

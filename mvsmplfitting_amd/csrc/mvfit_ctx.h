@@ -46,6 +46,16 @@ struct Obstacles {
     float* phi = nullptr;              // [B][G^3]
 };
 
+// the silhouette term inside the fit (mvfit_set_silhouette_term): weights and the buffers of a chained round, owned by
+// mvfit_ctx::silterm_mem.  They are allocated by the first enable for the batch and keep their addresses while B stays.
+struct SilTerm {
+    bool on = false;
+    float w_in = 1.f, w_out = 1.f, sigma = 0.f;
+    float* g_verts = nullptr;          // [B][nv][3] the round's vertex cotangent
+    float* loss = nullptr;             // [B] L_j of the last evaluation
+    float* part = nullptr;             // slice partials of the pull-back (vjp_part_bytes)
+};
+
 struct mvfit_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -56,7 +66,7 @@ struct mvfit_ctx {
     DevPool model_mem;
     // problem lifetime (free_problem_buffers): what mvfit_set_problems and ensure_sdf_buffers allocate; the ring (its done_round
     // is sized by Bpad) and the obstacles go whenever the problems go, and each may be replaced on its own before that
-    DevPool problem_mem, ring_mem, obst_mem;
+    DevPool problem_mem, ring_mem, obst_mem, silterm_mem;
     // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
     DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
     DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
@@ -74,6 +84,7 @@ struct mvfit_ctx {
     PinnedBuf h_async_done;            // host word the last finishing problem writes
     // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
     SilState sil;
+    SilTerm silt;
     // ---- model ----
     DevModel M{};
     bool upload_failed = false, alloc_failed = false;
@@ -172,5 +183,6 @@ hipError_t launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStr
 int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st);
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
+inline const char* term_name(const mvfit_ctx* c) { return c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf"; }
 
 }  // namespace mvfit

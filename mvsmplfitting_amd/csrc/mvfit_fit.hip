@@ -52,7 +52,16 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     // (the scene term's obstacles: buffers and scalars baked into its kernel node; a re-freeze changes none of them)
     struct { const void *tab, *box, *phi; int grid; float rob; } obst = {nullptr, nullptr, nullptr, 0, 0.f};
     if (c->obst.on) { obst.tab = c->obst.tab; obst.box = c->obst.box; obst.phi = c->obst.phi; obst.grid = c->obst.grid; obst.rob = c->obst.rob; }
-    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst));
+    // (the silhouette term: mask workspace and contour buffers, the sizes their offsets and grids derive from, the round's
+    // buffers and the weights; a re-set of a mask set of the same sizes and contour changes none of them)
+    struct { const void *ws, *cs, *g_verts, *loss, *part; int M, H, W, C, nchunks, stride; float w_in, w_out, sigma; } silk;
+    memset(&silk, 0, sizeof(silk));
+    if (c->silt.on) {
+        silk.ws = c->sil.ws.get(); silk.cs = c->sil.cs.get(); silk.g_verts = c->silt.g_verts; silk.loss = c->silt.loss; silk.part = c->silt.part;
+        silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
+        silk.w_in = c->silt.w_in; silk.w_out = c->silt.w_out; silk.sigma = c->silt.sigma;
+    }
+    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
     memcpy(k, &O, sizeof(O)); k += sizeof(O);
@@ -60,7 +69,8 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     memcpy(k, &c->F, sizeof(FitBuffers)); k += sizeof(FitBuffers);
     memcpy(k, &c->Q, sizeof(DevProblems)); k += sizeof(DevProblems);
     memcpy(k, &c->opt.pass_kernel, sizeof(int)); k += sizeof(int);
-    memcpy(k, &obst, sizeof(obst));
+    memcpy(k, &obst, sizeof(obst)); k += sizeof(obst);
+    memcpy(k, &silk, sizeof(silk));
     if (c->round_graph && key == c->graph_key) return MVFIT_OK;
     drop_graph(c);
     hipStream_t cs;
@@ -463,9 +473,9 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
         SW.w[s] = to_dev(sw[s]);
     }
     const bool any_sdf = in.sdf_stages != 0;
-    if (any_sdf && !c->sdf_num_faces && !c->obst.on)
+    if (any_sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
-    if (c->obst.on) in.sdf_service = 0;          // the scene term runs in chained rounds only (no service path for it)
+    if (c->obst.on || c->silt.on) in.sdf_service = 0;      // the scene and silhouette terms run in chained rounds only (no service path for them)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;

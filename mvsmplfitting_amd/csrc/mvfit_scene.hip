@@ -180,6 +180,8 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the model was created without (valid) faces");
     if (c->sdf_num_faces)
         return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: mvfit_set_sdf's term is the interpenetration term (one per ctx): remove it first");
+    if (c->silt.on)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the silhouette term uses the ctx's term slot: switch it off first");
     if (c->nv > 8192) return fail(c, MVFIT_E_UNSUPPORTED, "the scene term supports up to 8192 vertices (model has %d)", c->nv);
     if (!scene_first || num_scenes <= 0) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: bad argument (num_scenes=%d)", num_scenes);
     if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: grid_size %d outside [2, 128]", grid_size);
@@ -227,6 +229,7 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
     HIP_OK(c, hipSetDevice(c->device));
     if (num_images == 0) {                                   // clear: the work areas stay for a next set of the same size
         c->sil.on = false;
+        c->silt.on = false;                                  // no masks, no term
         return MVFIT_OK;
     }
     if (num_images < 0 || num_images > 65535 || height < 2 || height > 8192 || width < 2 || width > 8192)
@@ -236,8 +239,52 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
     if (!masks || !image_body || !cam_R || !cam_t || !cam_f || !cam_c)
         return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: null %s", !masks ? "masks" : !image_body ? "image_body" : !cam_R ? "cam_R" :
                     !cam_t ? "cam_t" : !cam_f ? "cam_f" : "cam_c");
-    return sil_set(c->sil, c->nv, num_images, height, width, masks, image_body, cam_R, cam_t, cam_f, cam_c, contour_stride,
-                   c->stream, c->err);
+    const int rc = sil_set(c->sil, c->nv, num_images, height, width, masks, image_body, cam_R, cam_t, cam_f, cam_c, contour_stride,
+                           c->stream, c->err);
+    // a set that replaces the one of an enabled term must fit the batch like the first (the term's kernels index the
+    // problems' buffers by image_body); a failed or unfit set leaves no term behind
+    if (c->silt.on && (rc || c->sil.body_min < 0 || c->sil.body_max >= c->B)) {
+        c->silt.on = false;
+        if (!rc)
+            return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: image_body holds %d .. %d, outside the %d problems of the enabled "
+                        "silhouette term (the term is switched off)", c->sil.body_min, c->sil.body_max, c->B);
+    }
+    return rc;
+}
+
+// The silhouette term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (mvfit_api.hip: launch_term).
+extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, float w_out, float sigma) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (!enable) {                                           // off: the buffers stay for the next enable of this batch
+        c->silt.on = false;
+        return MVFIT_OK;
+    }
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: no mask set is present (mvfit_set_silhouettes)");
+    if (c->sdf_num_faces || c->obst.on)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: %s the ctx's term slot (one term per ctx): remove %s first",
+                    c->obst.on ? "scene obstacles use" : "mvfit_set_sdf's term uses", c->obst.on ? "them" : "it");
+    if (!std::isfinite(w_in) || !std::isfinite(w_out) || !std::isfinite(sigma) || w_in < 0.f || w_out < 0.f)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_term: w_in = %g and w_out = %g must be finite and >= 0, sigma = %g finite",
+                    (double)w_in, (double)w_out, (double)sigma);
+    if (c->sil.body_min < 0 || c->sil.body_max >= c->B)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_term: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min,
+                    c->sil.body_max, c->B);
+    if (!c->silt.part) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        c->silterm_mem.release();                            // (what an earlier call that failed half-way left)
+        c->silt = SilTerm{};
+        float *g = nullptr, *l = nullptr;
+        HIP_OK(c, c->silterm_mem.alloc(&g, (size_t)c->B * c->nv * 3 * sizeof(float), true));
+        HIP_OK(c, c->silterm_mem.alloc(&l, (size_t)c->B * sizeof(float), true));
+        c->silt.g_verts = g; c->silt.loss = l;
+        HIP_OK(c, c->silterm_mem.alloc(&c->silt.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
+    }
+    if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
+    c->silt.w_in = w_in; c->silt.w_out = w_out; c->silt.sigma = sigma;
+    c->silt.on = true;
+    return MVFIT_OK;
 }
 
 extern "C" int mvfit_silhouettes_read(mvfit_ctx* c, float* field, int32_t* contour_first, int32_t* contour_xy, int32_t* num_points) {

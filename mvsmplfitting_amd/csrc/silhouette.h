@@ -33,5 +33,9 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
 int sil_read(const SilState& S, float* field, int32_t* contour_first, int32_t* contour_xy, hipStream_t stream, std::string& err);
 int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, float* loss,
              float* g_vertices, int32_t* winner, hipStream_t stream, std::string& err);
+// the same evaluation for the fit's chained rounds (mvfit_set_silhouette_term): gate[body] == 0 skips the body (its loss and
+// gradient rows keep what they held), null = every body; capturable
+int sil_round(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, const int* gate,
+              float* loss, float* g_vertices, hipStream_t stream, std::string& err);
 
 }  // namespace mvfit

@@ -20,6 +20,8 @@
 //       projection into a float64 sum that is rounded and stored once.  Term A's loss: a float64 partial per (image, block).
 //   sil_loss_kernel: a wave per body, its images in ascending order, per image the partials in order.
 // No float atomics; nothing a body gets depends on the other bodies of the call or on its position in it.
+// Inside the fit (mvfit_set_silhouette_term): sil_round launches the <GATED = true> instantiations of the three evaluation
+// kernels on the stream a chained round is captured on; they skip the bodies whose gate word is 0.
 #include "silhouette.h"
 
 #include <algorithm>
@@ -165,19 +167,31 @@ __global__ __launch_bounds__(SIL_NT) void sil_scan_kernel(int* __restrict__ row_
     for (int y = y0; y < y1; ++y) { const int c = r[y]; r[y] = a; a += c; }
 }
 
+// The gate of the term inside the fit's chained rounds (sil_round): gate[body] == 0 - a finished problem, or a stage without
+// the term - ends the workgroup at once; a null pointer keeps every body.  The ungated instantiations carry an empty
+// argument and are the kernels as they were.
+template <bool GATED> struct SilGate { __device__ __forceinline__ bool off(int) const { return false; } };
+template <> struct SilGate<true> {
+    const int* gate;
+    __device__ __forceinline__ bool off(int body) const { return gate && !gate[body]; }
+};
+
 // ------------------------------------------------------------------------------------------------ term B: the search
 // grid (chunks): SIL_CHUNK contour points of one image against all vertices of its body.
 // acc[(image * nv + j) * 2 + {0, 1}] += round(2^28 * stride * rho_B'(m) * 2 (dx, dy)); partB[chunk] = sum of rho_B.
+template <bool GATED>
 __global__ __launch_bounds__(SIL_NT) void sil_search_kernel(const float* __restrict__ verts, int nv, const SilCam* __restrict__ cams,
                                                             const int* __restrict__ image_body,
                                                             const SilChunk* __restrict__ chunks, const int2* __restrict__ xy,
                                                             float sigma, int stride, unsigned long long* __restrict__ acc,
-                                                            double* __restrict__ partB, int* __restrict__ winner) {
+                                                            double* __restrict__ partB, int* __restrict__ winner,
+                                                            SilGate<GATED> gate) {
     __shared__ __attribute__((aligned(16))) float2 sh_uv[SIL_VT];
     __shared__ double sh_d[SIL_NT / 64];
     static_assert(SIL_VT % 2 == 0, "two vertices per read");
     const int tid = threadIdx.x;
     const SilChunk ch = chunks[blockIdx.x];
+    if (GATED && gate.off(image_body[ch.image])) return;          // (uniform)
     const SilCam cam = cams[ch.image];
     const float* vb = verts + (size_t)image_body[ch.image] * nv * 3;
     float cx[SIL_PPT], cy[SIL_PPT];
@@ -265,14 +279,16 @@ __device__ __forceinline__ int sil_lower_bound(const int* __restrict__ sbody, in
 
 // grid (ceil(nv / SIL_NT), N): thread = (body n, vertex j).  sbody / simg: the images sorted by (body, image).
 // partA[i * gridDim.x + blockIdx.x] = the workgroup's sum of rho_A in image i.
+template <bool GATED>
 __global__ __launch_bounds__(SIL_NT) void sil_vertex_kernel(const float* __restrict__ verts, int nv, const SilCam* __restrict__ cams,
                                                             const int* __restrict__ sbody, const int* __restrict__ simg, int M,
                                                             const float* __restrict__ field, int H, int W,
                                                             const int* __restrict__ flags, float w_in, float w_out, float sigma,
                                                             const long long* __restrict__ acc, float* __restrict__ g_verts,
-                                                            double* __restrict__ partA) {
+                                                            double* __restrict__ partA, SilGate<GATED> gate) {
     __shared__ double sh_d[SIL_NT / 64];
     const int n = blockIdx.y, tid = threadIdx.x, j = blockIdx.x * SIL_NT + tid;
+    if (GATED && gate.off(n)) return;                               // (uniform)
     const bool live = j < nv;
     const float* pv = verts + ((size_t)n * nv + (live ? j : 0)) * 3;
     double g[3] = {0.0, 0.0, 0.0};
@@ -339,11 +355,14 @@ __device__ __forceinline__ double sil_ordered_sum(const double* __restrict__ p, 
 }
 
 // grid (N), one wave: loss[n] = sum over the body's images, ascending, of w_in A_i + w_out stride B_i
+template <bool GATED>
 __global__ __launch_bounds__(64) void sil_loss_kernel(const int* __restrict__ sbody, const int* __restrict__ simg, int M,
                                                       const double* __restrict__ partA, int nblk,
                                                       const double* __restrict__ partB, const int* __restrict__ chunk_first,
-                                                      float w_in, float w_out, int stride, float* __restrict__ loss) {
+                                                      float w_in, float w_out, int stride, float* __restrict__ loss,
+                                                      SilGate<GATED> gate) {
     const int n = blockIdx.x, lane = threadIdx.x;
+    if (GATED && gate.off(n)) return;
     double tot = 0.0;
     for (int s = sil_lower_bound(sbody, M, n); s < M && sbody[s] == n; ++s) {
         const int i = simg[s];
@@ -486,18 +505,46 @@ int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, flo
     unsigned long long* acc = accumulate ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
     if (accumulate) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * nv * 16, stream));
     if (S.nchunks)
-        hipLaunchKernelGGL(sil_search_kernel, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
+        hipLaunchKernelGGL(sil_search_kernel<false>, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
                            reinterpret_cast<const int*>(ws + S.o_body), reinterpret_cast<const SilChunk*>(cs + S.o_chunk),
                            reinterpret_cast<const int2*>(cs + S.o_xy), sigma, S.stride, acc,
-                           reinterpret_cast<double*>(cs + S.o_partB), winner);
-    hipLaunchKernelGGL(sil_vertex_kernel, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg, S.M,
+                           reinterpret_cast<double*>(cs + S.o_partB), winner, SilGate<false>{});
+    hipLaunchKernelGGL(sil_vertex_kernel<false>, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg, S.M,
                        reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(ws + S.o_flags),
                        w_in, w_out, sigma, reinterpret_cast<const long long*>(acc), g_vertices,
-                       reinterpret_cast<double*>(ws + S.o_partA));
-    hipLaunchKernelGGL(sil_loss_kernel, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
+                       reinterpret_cast<double*>(ws + S.o_partA), SilGate<false>{});
+    hipLaunchKernelGGL(sil_loss_kernel<false>, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
                        reinterpret_cast<const double*>(ws + S.o_partA), nblk,
                        reinterpret_cast<const double*>(cs + S.o_partB), reinterpret_cast<const int*>(ws + S.o_cfirst), w_in,
-                       w_out, S.stride, loss);
+                       w_out, S.stride, loss, SilGate<false>{});
+    SIL_HIP(hipGetLastError());
+    return MVFIT_OK;
+}
+
+// One evaluation for the fit's chained rounds: sil_loss's sequence with the gated kernels, every body's loss and vertex
+// gradient; no host work, so a stream capture records it as it is (one memset node and three kernel nodes).
+int sil_round(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, const int* gate,
+              float* loss, float* g_vertices, hipStream_t stream, std::string& err) {
+    const int nv = S.nv, nblk = (nv + SIL_NT - 1) / SIL_NT;
+    unsigned char *ws = S.ws.as<unsigned char>(), *cs = S.cs.as<unsigned char>();
+    const SilCam* cams = reinterpret_cast<const SilCam*>(ws + S.o_cam);
+    const int* sbody = reinterpret_cast<const int*>(ws + S.o_sbody);
+    const int* simg = reinterpret_cast<const int*>(ws + S.o_simg);
+    unsigned long long* acc = S.nchunks ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
+    if (acc) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * nv * 16, stream));
+    if (S.nchunks)
+        hipLaunchKernelGGL(sil_search_kernel<true>, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
+                           reinterpret_cast<const int*>(ws + S.o_body), reinterpret_cast<const SilChunk*>(cs + S.o_chunk),
+                           reinterpret_cast<const int2*>(cs + S.o_xy), sigma, S.stride, acc,
+                           reinterpret_cast<double*>(cs + S.o_partB), (int*)nullptr, SilGate<true>{gate});
+    hipLaunchKernelGGL(sil_vertex_kernel<true>, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg,
+                       S.M, reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(ws + S.o_flags),
+                       w_in, w_out, sigma, reinterpret_cast<const long long*>(acc), g_vertices,
+                       reinterpret_cast<double*>(ws + S.o_partA), SilGate<true>{gate});
+    hipLaunchKernelGGL(sil_loss_kernel<true>, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
+                       reinterpret_cast<const double*>(ws + S.o_partA), nblk,
+                       reinterpret_cast<const double*>(cs + S.o_partB), reinterpret_cast<const int*>(ws + S.o_cfirst), w_in,
+                       w_out, S.stride, loss, SilGate<true>{gate});
     SIL_HIP(hipGetLastError());
     return MVFIT_OK;
 }

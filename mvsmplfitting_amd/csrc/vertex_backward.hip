@@ -5,6 +5,8 @@
 //   vjp_tile_kernel               one workgroup per (vertex slice, 32-problem chunk): the dense part of the adjoint over the
 //                                 slice's vertices, from the vertex cotangent, into one partial record per problem
 //   vjp_reduce_kernel             the slice partials of a problem, added in slice order -> one SdfAdj-shaped record
+//   vjp_tile_kernel<gated>,       the same dense part for the silhouette term inside the fit's chained rounds: chunks without a
+//   vjp_record_kernel             live problem skipped, the record published in the form the closure consumes (SdfAdj)
 //   vjp_tail_kernel               one workgroup per problem: the closure's adjoint stages (closure_device.h: closure_backward)
 //                                 with the record entering at factor 1 and the keypoint cotangent in place of the data
 //                                 term's keypoint gradient; every prior off
@@ -50,12 +52,29 @@ struct VjpTileLds {
     float vp[32][VB_GS];                                    // v_posed [problem][row]
 };
 
+// GATED (the silhouette term of the fit's chained rounds): a chunk none of whose problems has its gate word set returns at
+// once; otherwise the same arithmetic in the same order - a live problem's partial record has the bits of the ungated
+// kernel's (a gated-off neighbour's cotangent rows are whatever the buffer holds: its record is never read, and no sum
+// mixes problems).  A null gate keeps every chunk.  The ungated instantiation carries an empty argument and is the kernel
+// as it was.
+template <bool GATED> struct VjpGate {};
+template <> struct VjpGate<true> { const int* gate; };
+
+template <bool GATED>
 __global__ __launch_bounds__(VB_NT) void vjp_tile_kernel(DevModel M, DevPose P, int B, int Bpad,
-                                                         const float* __restrict__ g_verts, float* __restrict__ part) {
+                                                         const float* __restrict__ g_verts, float* __restrict__ part,
+                                                         VjpGate<GATED> G) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     VjpTileLds& S = *reinterpret_cast<VjpTileLds*>(smem_raw);
     const int tid = threadIdx.x, slice = blockIdx.x, chunk = blockIdx.y;
     const int nv = M.nv, b0 = chunk * 32;
+    if constexpr (GATED) {
+        if (G.gate) {
+            int live = 0;
+            for (int p = 0; p < 32 && b0 + p < B; ++p) live |= G.gate[b0 + p];      // (uniform: scalar loads)
+            if (!live) return;
+        }
+    }
     // the chunk's operands (problems past B: zero transforms, zero cotangent - their records are never read)
     for (int i = tid; i < 32 * KROWS; i += VB_NT) {
         const int k = i >> 5, p = i & 31;
@@ -213,6 +232,33 @@ __global__ __launch_bounds__(VB_PSTR) void vjp_reduce_kernel(const float* __rest
     if (e == 0) R.S = 0.f;
 }
 
+// The silhouette term's record of a live problem b (gate null or gate[b] != 0): the slice partials in slice order, as
+// vjp_reduce_kernel adds them, = the adjoint of L = loss[b] with respect to the pass's operands.  The closure forms (w S)^2
+// and applies 2 w^2 S to the record (closure_device.h: loss_combine), so S = sqrt(L) and the adjoint times 1 / (2 sqrt(L))
+// make it yield w^2 L and w^2 grad L unchanged.  L < FLT_MIN (no image, or nothing to pay): an all-zero record - the closure
+// then adds 0 and never reads the adjoint.
+__global__ __launch_bounds__(VB_PSTR) void vjp_record_kernel(const float* __restrict__ part, int nslices, int Bpad,
+                                                             const float* __restrict__ loss, const int* __restrict__ gate,
+                                                             SdfAdj* __restrict__ rec) {
+    const int b = blockIdx.x, e = threadIdx.x;
+    if (gate && !gate[b]) return;
+    if (e >= KROWS + NJ * 12 + 3) return;
+    const float* p = part + (size_t)b * VB_PSTR + e;
+    float s = 0.f;
+#pragma unroll 16
+    for (int y = 0; y < nslices; ++y) s += p[(size_t)y * Bpad * VB_PSTR];      // (loads ahead of the adds; the adds in order)
+    const float L = loss[b];
+    const bool zero = L < 1.17549435e-38f;                                     // FLT_MIN
+    const float S = zero ? 0.f : sqrtf(L);
+    const float k = zero ? 0.f : 1.f / (2.f * S);
+    s = zero ? 0.f : s * k;
+    SdfAdj& R = rec[b];
+    if (e < KROWS) R.gcoef[e] = s;
+    else if (e < KROWS + NJ * 12) R.gA[e - KROWS] = s;
+    else R.gtau[e - KROWS - NJ * 12] = s;
+    if (e == 0) R.S = S;
+}
+
 // per problem: the closure's adjoint with the record at factor 1 (rec may be null: no vertex cotangent) and the keypoint
 // cotangent g_joints (null: zero) where the data term's keypoint gradient goes; every prior weight 0 and both prior guards
 // set (their gradients are then not formed at all - the angle prior's exp could overflow into 0 * inf)
@@ -249,8 +295,11 @@ int vjp_slices(int nv) { return (nv + VB_SLICE_V - 1) / VB_SLICE_V; }
 size_t vjp_part_bytes(int Bpad, int nv) { return (size_t)vjp_slices(nv) * Bpad * VB_PSTR * sizeof(float); }
 
 hipError_t vertex_backward_configure() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vjp_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vjp_tile_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)sizeof(VjpTileLds));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(vjp_tile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)sizeof(VjpTileLds));
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(vjp_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)((sizeof(ClosureLds) + 15) & ~(size_t)15));
@@ -262,11 +311,22 @@ hipError_t launch_vertices_backward(const DevModel& M, const DevPose& P, int B, 
                                     hipStream_t stream) {
     if (g_verts) {
         const int ns = vjp_slices(M.nv);
-        hipLaunchKernelGGL(vjp_tile_kernel, dim3(ns, Bpad / 32), dim3(VB_NT), sizeof(VjpTileLds), stream, M, P, B, Bpad, g_verts, part);
+        hipLaunchKernelGGL(vjp_tile_kernel<false>, dim3(ns, Bpad / 32), dim3(VB_NT), sizeof(VjpTileLds), stream, M, P, B, Bpad, g_verts, part,
+                           VjpGate<false>{});
         hipLaunchKernelGGL(vjp_reduce_kernel, dim3(B), dim3(VB_PSTR), 0, stream, (const float*)part, ns, Bpad, rec);
     }
     hipLaunchKernelGGL(vjp_tail_kernel, dim3(B), dim3(STEP_NT), (sizeof(ClosureLds) + 15) & ~(size_t)15, stream, M, params, flags,
                        g_joints, g_verts ? (const SdfAdj*)rec : (const SdfAdj*)nullptr, g_params);
+    return hipGetLastError();
+}
+
+// the silhouette term's pull-back of a chained round: g_verts[B][nv][3] (rows of live problems) and loss[B] -> rec[B]
+hipError_t launch_silhouette_pullback(const DevModel& M, const DevPose& P, int B, int Bpad, const int* gate, const float* g_verts,
+                                      const float* loss, float* part, SdfAdj* rec, hipStream_t stream) {
+    const int ns = vjp_slices(M.nv);
+    hipLaunchKernelGGL(vjp_tile_kernel<true>, dim3(ns, Bpad / 32), dim3(VB_NT), sizeof(VjpTileLds), stream, M, P, B, Bpad, g_verts,
+                       part, VjpGate<true>{gate});
+    hipLaunchKernelGGL(vjp_record_kernel, dim3(B), dim3(VB_PSTR), 0, stream, (const float*)part, ns, Bpad, loss, gate, rec);
     return hipGetLastError();
 }
 

@@ -124,6 +124,7 @@ class MvFit:
         self.B = 0
         self.V = 0
         self._obstacles = False
+        self._sil_term = False
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -223,6 +224,7 @@ class MvFit:
             gt.data_ptr(), wc.data_ptr()))
         if B != self.B or V != self.V:
             self._obstacles = False              # (the C side drops them with the batch they were frozen for)
+            self._sil_term = False               # (and switches the silhouette term off)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -439,14 +441,31 @@ class MvFit:
         if M == 0:
             return self.clear_silhouettes()
         fp = C.POINTER(C.c_float)
-        self._check(self._lib.mvfit_set_silhouettes(
+        rc = self._lib.mvfit_set_silhouettes(
             self._ctx, M, H, W, m.data_ptr(), body.ctypes.data_as(_lib._ip), R.ctypes.data_as(fp), t.ctypes.data_as(fp),
-            f.ctypes.data_as(fp), c.ctypes.data_as(fp), int(contour_stride)))
+            f.ctypes.data_as(fp), c.ctypes.data_as(fp), int(contour_stride))
+        if rc:
+            self._sil_term = False               # (a set that fails, or does not fit an enabled term, switches the term off)
+        self._check(rc)
         self._sil_shape = (M, H, W)
 
     def clear_silhouettes(self):
         """Remove the mask set of set_silhouettes."""
         self._check(self._lib.mvfit_set_silhouettes(self._ctx, 0, 0, 0, None, None, None, None, None, None, 1))
+        self._sil_term = False                   # (no masks, no term: the C side switches it off)
+
+    def set_silhouette_term(self, w_in=1.0, w_out=1.0, sigma=0.0):
+        """Make the silhouette loss of the current mask set a term of closure() and fit() (include/mvfit.h:
+        mvfit_set_silhouette_term): a stage with coll_loss_weight w > 0 adds w^2 * L_j to problem j, L_j = silhouette_loss of
+        the trial point's vertices (image_body = the problem index), with its gradient through the model.  fit() runs such
+        stages as chained rounds.  Needs set_problems and set_silhouettes; excludes set_sdf's term and scene obstacles."""
+        self._check(self._lib.mvfit_set_silhouette_term(self._ctx, 1, float(w_in), float(w_out), float(sigma)))
+        self._sil_term = True
+
+    def clear_silhouette_term(self):
+        """Switch the term of set_silhouette_term off (the mask set stays)."""
+        self._check(self._lib.mvfit_set_silhouette_term(self._ctx, 0, 0.0, 0.0, 0.0))
+        self._sil_term = False
 
     def silhouettes(self):
         """Diagnostics: (field [M,H,W] float32, contour_first [M+1] int32, contour_xy [C,2] int32) of the mask set."""
@@ -697,8 +716,9 @@ class MvFit:
 
     def sdf_term_read(self):
         """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
-        (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set."""
-        smp = None if self._obstacles else torch.empty(self.B, self.nv, 4, device=self.device)
+        (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set; so does the silhouette term
+        (set_silhouette_term), whose S is the loss L_j itself."""
+        smp = None if (self._obstacles or self._sil_term) else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S

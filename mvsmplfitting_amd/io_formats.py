@@ -19,6 +19,10 @@ and fitted parameters written the way the reference's tools read them.
   image_size         (H, W) read_image will return, from the file header (no pixel decode)
   save_image         RGB uint8 [H,W,3] -> file, JPEG quality 95 like cv2.imwrite's default (utils.py:700-712)
                      (both through PIL, imported when first used)
+  read_mask          person mask file -> uint8 [H,W], non-zero = on: any Pillow mode converted to 8-bit grey, EXIF
+                     orientation applied as for the overlay inputs
+  downscale_mask     [H,W] -> [ceil(H/k), ceil(W/k)]: a low-res pixel is on when at least half of the pixels its k x k block
+                     has are on
 """
 from __future__ import annotations
 
@@ -161,6 +165,36 @@ def read_image(path):
         return np.asarray(ImageOps.exif_transpose(im).convert('RGB'), dtype=np.uint8)
 
 
+def read_mask(path):
+    """A person mask -> uint8 [H, W], non-zero = on (what MvFit.set_silhouettes takes per image)."""
+    from PIL import ImageOps
+    with _pil().open(path) as im:
+        return np.asarray(ImageOps.exif_transpose(im).convert('L'), dtype=np.uint8)
+
+
+def downscale_mask(mask, k):
+    """mask [H, W] (non-zero = on) at 1/k of the resolution: low-res pixel (y, x) covers the block rows k y .. k y + k - 1,
+    columns likewise, cut at the image's edge, and is on (1) when at least half of the pixels the block HAS are on.  k = 1
+    gives the mask back unchanged.  Cameras follow with f / k and c / k."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError('downscale_mask: expected [H, W], got %s' % (m.shape,))
+    k = int(k)
+    if k < 1:
+        raise ValueError('downscale_mask: k = %d < 1' % k)
+    if k == 1:
+        return np.ascontiguousarray(m, dtype=np.uint8)
+    H, W = m.shape
+    h, w = -(-H // k), -(-W // k)
+    on = np.zeros((h * k, w * k), np.int64)
+    on[:H, :W] = m != 0
+    have = np.zeros((h * k, w * k), np.int64)
+    have[:H, :W] = 1
+    on = on.reshape(h, k, w, k).sum(axis=(1, 3))
+    have = have.reshape(h, k, w, k).sum(axis=(1, 3))
+    return (2 * on >= have).astype(np.uint8)
+
+
 def image_size(path):
     with _pil().open(path) as im:                # opening reads the header only
         w, h = im.size
@@ -177,5 +211,5 @@ def save_image(path, rgb, quality=95):
     return path
 
 
-__all__ = ['read_image', 'image_size', 'save_image', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'read_people', 'read_people3d', 'problem_tensors', 'result_dict',
+__all__ = ['read_image', 'image_size', 'save_image', 'read_mask', 'downscale_mask', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'read_people', 'read_people3d', 'problem_tensors', 'result_dict',
            'save_result_pkl', 'save_obj']

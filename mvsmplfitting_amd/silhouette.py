@@ -15,8 +15,10 @@ differentiable body model:
 One autograd node maps the vertices to the loss; the forward call already computes the gradient and the node keeps it,
 backward scales it by each body's incoming gradient.  Once differentiable: there is no double backward.
 
-Not built here: reading mask files, fit_folder(silhouettes=...), the term inside the fit's own rounds, multi-person instance
-masks, visibility or occlusion between bodies, point-to-edge distances (the contour term measures the distance to the
+refine_fit runs the term inside the engine's own fit instead (include/mvfit.h:mvfit_set_silhouette_term): every parameter
+the stage frees moves, the optimiser is the project's L-BFGS and no closure leaves the device.
+
+Not built here: instance masks shared between persons, visibility or occlusion between bodies, point-to-edge distances (the contour term measures the distance to the
 nearest projected *vertex*; its floor is about half the projected vertex spacing).
 """
 from __future__ import annotations
@@ -199,3 +201,48 @@ def refine_shape(layer, params, masks, image_body, cams, *, free=('betas', 'scal
     report = dict(groups=groups.tolist(), before=before.tolist(), after=after.tolist(), accepted=accepted.tolist(),
                   silhouette_before=sil_before.tolist(), silhouette_after=sil_after.tolist(), iterations=n_iter)
     return out, report
+
+
+def refine_fit(engine, params, stage, *, w_in=1.0, w_out=1.0, sigma=0.0, **fit_kwargs):
+    """One fit of the engine's B problems with the silhouette term inside the fit's rounds.
+
+    params [B,118] (set_problems and set_silhouettes done: image_body indexes the problems); ``stage``: one weight dict with
+    coll_loss_weight w > 0.  The objective of problem j is its closure loss under ``stage`` with the term on: the stage's
+    keypoint and prior terms + w^2 * silhouette_loss_j.
+
+      1. the term is switched on; one closure gives J(x_0) and the silhouette losses L(x_0);
+      2. x' = engine.fit(x_0, [stage], **fit_kwargs); one closure gives J(x'), L(x');
+      3. problem j keeps its row of x' iff J_j(x') < J_j(x_0); otherwise the row reverts to x_0 exactly;
+      4. the engine is left with the term cleared (also when something raises); the mask set stays.
+
+    Returns (params, report).  report: dict(before [B], after [B] = J of the returned rows, accepted [B] bool,
+    silhouette_before [B], silhouette_after [B] = L of the returned rows, n_closure [B] of the fit, loss [B] = after)."""
+    if float(stage.get('coll_loss_weight', 0.0)) <= 0.0:
+        raise ValueError('refine_fit: the stage needs coll_loss_weight > 0')
+    x0 = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, np.float32))
+    x0 = x0.to(engine.device).clone()
+
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+    def objective(x):
+        J = engine.closure(x, stage, want_grad=False)['loss']
+        return host(J).astype(np.float64), host(engine.sdf_term_read()[1]).astype(np.float64)
+
+    engine.set_silhouette_term(w_in=w_in, w_out=w_out, sigma=sigma)
+    try:
+        before, sil_before = objective(x0)
+        x1, st = engine.fit(x0, [stage], **fit_kwargs)
+        x1 = x1.to(x0.dtype)
+        after, sil_after = objective(x1)
+        accepted = after < before
+        for j in np.flatnonzero(~accepted):
+            x1[int(j)] = x0[int(j)]
+        after = np.where(accepted, after, before)
+        sil_after = np.where(accepted, sil_after, sil_before)
+        report = dict(before=before, after=after, accepted=accepted, silhouette_before=sil_before,
+                      silhouette_after=sil_after, n_closure=host(st['n_closure']), loss=after.copy())
+        return x1, report
+    finally:
+        engine.clear_silhouette_term()
+
