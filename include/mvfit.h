@@ -474,6 +474,52 @@ int mvfit_silhouette_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies,
  * non-finite or negative w_in / w_out, a non-finite sigma, a mask set whose image_body lies outside [0, B). */
 int mvfit_set_silhouette_term(mvfit_ctx* ctx, int enable, float w_in, float w_out, float sigma);
 
+/* ---- Vertex-target term: squared distance of a problem's vertices to weighted target vertex sets ----
+ * The frozen form of every "stay close to these bodies" energy (temporal smoothing against the neighbouring frames, a
+ * registered mesh of another method): problem j has K target vertex sets T_jk [Nv,3] with weights a_jk >= 0.
+ *
+ * mvfit_set_vertex_targets copies targets[B,K,Nv,3] (device) and weights[B,K] (host) into buffers the ctx owns; the
+ * caller may free its own afterwards.  1 <= K <= MVFIT_VERTEX_TARGETS_MAX, every weight finite and >= 0.  K = 0 or
+ * targets = NULL clears the set and switches the term (mvfit_set_vertex_target_term) off.  A target row with a_jk == 0 is
+ * never read: it may hold anything, NaN included.  A second set with the same (B, K) keeps every buffer address (the
+ * weights live in a device buffer the kernel reads; a captured round graph stays valid), another K replaces the buffers and
+ * keeps an enabled term on.  mvfit_set_problems with another B clears the set.  MVFIT_E_STATE without mvfit_set_problems;
+ * MVFIT_E_ARG: K outside the range, a null weights pointer, a negative or non-finite weight (the set in place stays). */
+#define MVFIT_VERTEX_TARGETS_MAX 4
+int mvfit_set_vertex_targets(mvfit_ctx* ctx, int K, const float* targets, const float* weights);
+
+/* The term at vertices[B,Nv,3] (device): loss[B] and, unless NULL, g_vertices[B,Nv,3] (device).  The contract, over a
+ * problem's vertices as n = 3 Nv flat floats (the term is separable per float):
+ *   d_k[e] = V[e] - T_k[e]                              one fp32 subtraction, for the k with a_k > 0 in ascending k;
+ *   g[e]   = float32(2 * sum_k double(a_k) * double(d_k[e]))          the sum in float64, ascending k, from 0.0;
+ *   L      = float32(sum_e sum_k double(a_k) * double(d_k[e])^2)      accumulated in float64.
+ * A product of two floats is exact in float64, so a fused multiply-add changes no bit of g: g_vertices is reproducible bit
+ * for bit by a NumPy restatement.  The order of L's sum is fixed by Nv and the kernel's shape (csrc/vertex_target.hip: 1024
+ * pairs of floats per workgroup, a wave64 butterfly, the waves and then the workgroups in order), never by B or the
+ * problem's position; float64 keeps its error far below the one final fp32 rounding.  No atomics: a problem's L and g are
+ * bit-identical alone, in any batch, at any position and from run to run.  A problem whose weights are all zero gets L = 0
+ * and an exactly zero gradient.
+ * MVFIT_E_STATE when no target set is present; MVFIT_E_ARG for a null vertices or loss. */
+int mvfit_vertex_target_loss(mvfit_ctx* ctx, const float* vertices, float* loss, float* g_vertices);
+
+/* The vertex-target loss as a term of the fit (enable != 0; 0 switches it off).  While it is on, a weight set with
+ * coll_loss_weight = w > 0 adds w^2 * L_j to problem j, L_j exactly loss[j] of mvfit_vertex_target_loss at the trial point's
+ * vertices; its gradient is w^2 times the pull-back of that call's g_vertices through the fp32 model (the adjoint
+ * mvfit_vertices_backward computes).  The form, the record and the L < FLT_MIN rule are the silhouette term's: a problem
+ * whose weights are all zero keeps the loss and gradient bits it has without the term.
+ * mvfit_closure and mvfit_fit both honour the term.  mvfit_fit runs the stages that carry it as chained rounds (pass ->
+ * target kernel -> dense pull-back -> record -> step kernel, the term's kernels skipping finished problems); stages without it
+ * in front keep their single-launch phase.  MVFIT_F_SPARSE_VERTS is ignored while the term is active.  mvfit_sdf_term_read
+ * returns L_j in sums; samples: MVFIT_E_UNSUPPORTED.
+ * The target set may be replaced while the term is on: the next fit uses the new set, and the captured round graph is kept
+ * when (B, K) are the same.  The round's buffers (12 B Nv + 4 bytes of cotangent and loss, 2112 ceil(Nv / 32) bytes of
+ * pull-back partials per problem of the batch rounded up to 32) are allocated by the first enable and keep their addresses
+ * while B stays.
+ * One term slot per ctx: MVFIT_E_STATE while mvfit_set_sdf's term, scene obstacles or the silhouette term are configured
+ * (and those three setters return it while this term is on).  MVFIT_E_STATE also without mvfit_set_problems or without a
+ * target set. */
+int mvfit_set_vertex_target_term(mvfit_ctx* ctx, int enable);
+
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear
  * triangulation of the 17 keypoints from V calibrated views, batched over B frames.
  *   keypoints[B,V,17,3] float32 dev (u, v, confidence) ; intris[V,3,3], extris[V,4,4] float64 dev (the reference

@@ -41,6 +41,7 @@ from .init_guess import init_guess_batch, initial_params
 from .scene_fit import refine_scenes
 from .sequence import fit_sequences
 from .silhouette import refine_fit
+from .temporal import smooth_sequences
 
 
 # pose format -> the model kind whose joint tensor it maps (reference code/utils/utils.py:441-457 smpl_to_annotation)
@@ -232,6 +233,24 @@ def check_silhouettes(silhouettes, is_seq=False, scene_collision=None):
     return cfg
 
 
+def check_temporal(temporal, scene_collision=None, silhouettes=None):
+    """fit_folder's ``temporal`` option with the defaults filled in, or ValueError."""
+    if not isinstance(temporal, dict) or 'weight' not in temporal:
+        raise ValueError("temporal: a dict with at least 'weight' (the smoothing term's coll_loss_weight)")
+    unknown = set(temporal) - {'weight', 'sweeps'}
+    if unknown:
+        raise ValueError('temporal: unknown keys %s' % sorted(unknown))
+    if scene_collision is not None or silhouettes is not None:
+        raise ValueError('temporal and %s both use the fit\'s one term slot: choose one'
+                         % ('scene_collision' if scene_collision is not None else 'silhouettes'))
+    cfg = dict(dict(sweeps=3), **temporal)
+    if not float(cfg['weight']) > 0.0:
+        raise ValueError('temporal: weight must be > 0')
+    if int(cfg['sweeps']) < 1:
+        raise ValueError('temporal: sweeps must be >= 1')
+    return cfg
+
+
 def mask_path(mask_root, serial, camera, frame, person=None):
     """The mask file of one view of one frame: `<mask_root>/<serial>/<camera>/<frame>.png`, or `<frame>_<id:03d>.png` for
     person ``id`` of the multi-person path."""
@@ -299,7 +318,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
                save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
-               silhouettes=None):
+               silhouettes=None, temporal=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -346,7 +365,15 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     missing mask_root / weight, is_seq=True, together with scene_collision (one term slot), or when the mask workspace of
     include/mvfit.h exceeds max_mask_bytes (the message names the smallest downscale that fits).  The serial's result gains
     ``silhouette_report`` (refine_fit's, plus images = [(problem, view)] and mask_size), ``timing`` a 'silhouette' entry, and
-    ``final_loss`` is the refined objective."""
+    ``final_loss`` is the refined objective.
+    temporal: None, or dict(weight=..., sweeps=3) - after the serial's batched fit (or its is_seq chain) every person's track
+    over the serial's sorted frame list is smoothed by temporal.smooth_sequences (the vertex-target term inside the engine's
+    fit: first-order smoothness of the vertices over consecutive frames) with the last stage's weights plus
+    coll_loss_weight = weight; a sequence keeps a sweep's rows only if its joint energy fell.  One sequence per serial for
+    persons=0, one per person id on the multi-person path, where a frame the person is absent from breaks the chain.  The
+    serial's result gains ``temporal_report`` (smooth_sequences'), ``timing`` a 'temporal' entry, and ``final_loss`` is the
+    report's loss (smoothing term included, neighbours frozen at the result).  ValueError for unknown keys, a missing or
+    non-positive weight, sweeps < 1, or together with scene_collision or silhouettes (one term slot)."""
     import time as _time
 
     def _tick(key, t0):
@@ -378,6 +405,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         if unknown:
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
     sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision) if silhouettes is not None else None
+    tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -565,6 +593,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             xf = xr.to(xf.dtype)
             final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
             _t = _tick('silhouette', _t)
+        temporal_report = None
+        if tmp_cfg is not None:
+            # a person's track: frame_idx = position in the serial's frame list, so an absence breaks the chain
+            if has.all():
+                eng.set_joints3d(ann[:, :, :3], c3)
+            st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(tmp_cfg['weight']))
+            xr, temporal_report = smooth_sequences(eng, xf, st_, pp, pf, sweeps=int(tmp_cfg['sweeps']))
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('temporal', _t)
         full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
         xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
         res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
@@ -587,6 +625,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             out['scene_report'] = scene_report
         if silhouette_report is not None:
             out['silhouette_report'] = silhouette_report
+        if temporal_report is not None:
+            out['temporal_report'] = temporal_report
         if association is not None:
             out['association'] = association
         _t = _tick('write', _t)
@@ -691,6 +731,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 xf = xr.to(xf.dtype)
                 final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
                 _t = _tick('silhouette', _t)
+            temporal_report = None
+            if tmp_cfg is not None:
+                if has.all():
+                    eng.set_joints3d(ann[:, :, :3], c3)
+                st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(tmp_cfg['weight']))
+                xr, temporal_report = smooth_sequences(eng, xf, st_, np.zeros(F, np.int64), np.arange(F),
+                                                       sweeps=int(tmp_cfg['sweeps']))
+                xf = xr.to(xf.dtype)
+                final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
+                _t = _tick('temporal', _t)
             full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
             xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
             res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
@@ -713,6 +763,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                                    used_3d=has.copy(), views_per_frame=vmask.sum(1))
             if silhouette_report is not None:
                 results[serial]['silhouette_report'] = silhouette_report
+            if temporal_report is not None:
+                results[serial]['temporal_report'] = temporal_report
             _t = _tick('write', _t)
             if save_images:
                 results[serial]['images'] = render_serial_images(
@@ -727,4 +779,4 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
 
 
 __all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
-           'check_silhouettes', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes']
+           'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes']

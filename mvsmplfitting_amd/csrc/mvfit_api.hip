@@ -194,6 +194,12 @@ void mvfit::free_obstacles(mvfit_ctx* c) {
     c->obst = Obstacles{};
 }
 
+void mvfit::free_vertex_targets(mvfit_ctx* c) {
+    c->vtgt_mem.release();
+    c->vtterm_mem.release();
+    c->vt = VtxTargets{};
+}
+
 static void free_problem_buffers(mvfit_ctx* c) {
     drop_graph(c);
     c->problem_mem.release();
@@ -208,6 +214,7 @@ static void free_problem_buffers(mvfit_ctx* c) {
     free_obstacles(c);
     c->silterm_mem.release();           // the silhouette term goes with the batch it was enabled for
     c->silt = SilTerm{};
+    free_vertex_targets(c);             // and so do the vertex targets and their term
 }
 
 extern "C" void mvfit_destroy(mvfit_ctx* c) {
@@ -306,6 +313,8 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: scene obstacles are the interpenetration term (one per ctx): remove them first");
     if (c->silt.on && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the silhouette term uses the ctx's term slot: switch it off first");
+    if (c->vt.term && faces && num_faces != 0)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the vertex-target term uses the ctx's term slot: switch it off first");
     HIP_OK(c, hipSetDevice(c->device));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     drop_graph(c);
@@ -333,11 +342,12 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
 extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
     if (!c) return MVFIT_E_ARG;
     if (!c->pb.sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
-    if (samples && (c->obst.on || c->silt.on))
+    if (samples && (c->obst.on || c->silt.on || c->vt.term))
         return fail(c, MVFIT_E_UNSUPPORTED, "mvfit_sdf_term_read: the %s term keeps no per-vertex samples (sums only)", term_name(c));
     HIP_OK(c, hipSetDevice(c->device));
-    if (c->silt.on) {                                              // L_j itself (the record holds its root)
-        if (sums) HIP_OK(c, hipMemcpyAsync(sums, c->silt.loss, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (c->silt.on || c->vt.term) {                                // L_j itself (the record holds its root)
+        const float* L = c->vt.term ? c->vt.loss : c->silt.loss;
+        if (sums) HIP_OK(c, hipMemcpyAsync(sums, L, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         return MVFIT_OK;
     }
     if (samples) HIP_OK(c, hipMemcpyAsync(samples, c->pb.sdf_samp, (size_t)c->B * c->nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -385,12 +395,19 @@ int mvfit::ensure_sdf_buffers(mvfit_ctx* c) {
 // DevPose::box_part is set) when the split-fp16 basis exists and the launch is one 32-problem chunk per workgroup
 bool mvfit::pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
     const int chunks = (b_hi + 31) / 32 - b_lo / 32;
-    return !c->obst.on && !c->silt.on && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
+    return !c->obst.on && !c->silt.on && !c->vt.term && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
 }
 
 // the interpenetration term of a chained round behind its vertex pass: against the frozen obstacles when they are set,
-// the silhouette term when it is on (silhouette evaluation -> dense pull-back -> record), else the one-person term of mvfit_set_sdf
+// the silhouette term when it is on (silhouette evaluation -> dense pull-back -> record), the vertex-target term when it is
+// (target kernel -> the same pull-back), else the one-person term of mvfit_set_sdf
 hipError_t mvfit::launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
+    if (c->vt.term) {
+        const VtxTargets& T = c->vt;
+        const hipError_t e = launch_vertex_target(verts, c->nv, c->B, T.K, T.targets, T.weights, gate, T.partial, T.loss, T.g_verts, st);
+        if (e != hipSuccess) return e;
+        return launch_silhouette_pullback(c->M, c->P, c->B, c->Bpad, gate, T.g_verts, T.loss, T.part, c->pb.sdf_adj, st);
+    }
     if (c->silt.on) {
         const SilTerm& T = c->silt;
         if (sil_round(c->sil, verts, c->B, T.w_in, T.w_out, T.sigma, gate, T.loss, T.g_verts, st, c->err)) return hipErrorLaunchFailure;
@@ -526,7 +543,7 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
     int rc = check_flags(c, w->flags);
     if (rc) return rc;
     const bool sdf = w->coll_loss_weight > 0.f;
-    if (sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on)
+    if (sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on && !c->vt.term)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
     HIP_OK(c, hipSetDevice(c->device));
     if (c->opt.closure_vposer_helpers && (w->flags & MVFIT_F_VPOSER) && c->vps_mem && !sdf)

@@ -18,6 +18,7 @@
 #include "fit_plan.h"
 #include "launchers.h"
 #include "silhouette.h"
+#include "vertex_target.h"
 
 using namespace mvfit;          // (the three host files only: their bodies name the library's types unqualified)
 
@@ -67,6 +68,7 @@ struct mvfit_ctx {
     // problem lifetime (free_problem_buffers): what mvfit_set_problems and ensure_sdf_buffers allocate; the ring (its done_round
     // is sized by Bpad) and the obstacles go whenever the problems go, and each may be replaced on its own before that
     DevPool problem_mem, ring_mem, obst_mem, silterm_mem;
+    DevPool vtgt_mem, vtterm_mem;      // the vertex-target set (re-made when (B, K) change) and its term's round buffers
     // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
     DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
     DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
@@ -85,6 +87,8 @@ struct mvfit_ctx {
     // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
     SilState sil;
     SilTerm silt;
+    // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
+    VtxTargets vt;
     // ---- model ----
     DevModel M{};
     bool upload_failed = false, alloc_failed = false;
@@ -183,6 +187,7 @@ hipError_t launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStr
 int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st);
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
-inline const char* term_name(const mvfit_ctx* c) { return c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf"; }
+void free_vertex_targets(mvfit_ctx* c);
+inline const char* term_name(const mvfit_ctx* c) { return c->vt.term ? "vertex-target" : c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf"; }
 
 }  // namespace mvfit

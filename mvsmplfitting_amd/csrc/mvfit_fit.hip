@@ -61,7 +61,15 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
         silk.w_in = c->silt.w_in; silk.w_out = c->silt.w_out; silk.sigma = c->silt.sigma;
     }
-    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk));
+    // (the vertex-target term: the set's buffers and K, the round's buffers; the weights are read from their device buffer, so
+    // a re-freeze with the same (B, K) changes nothing here)
+    struct { const void *targets, *weights, *partial, *g_verts, *loss, *part; long long K; } vtk;
+    memset(&vtk, 0, sizeof(vtk));
+    if (c->vt.term) {
+        vtk.targets = c->vt.targets; vtk.weights = c->vt.weights; vtk.partial = c->vt.partial; vtk.g_verts = c->vt.g_verts;
+        vtk.loss = c->vt.loss; vtk.part = c->vt.part; vtk.K = c->vt.K;
+    }
+    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk) + sizeof(vtk));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
     memcpy(k, &O, sizeof(O)); k += sizeof(O);
@@ -70,7 +78,8 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     memcpy(k, &c->Q, sizeof(DevProblems)); k += sizeof(DevProblems);
     memcpy(k, &c->opt.pass_kernel, sizeof(int)); k += sizeof(int);
     memcpy(k, &obst, sizeof(obst)); k += sizeof(obst);
-    memcpy(k, &silk, sizeof(silk));
+    memcpy(k, &silk, sizeof(silk)); k += sizeof(silk);
+    memcpy(k, &vtk, sizeof(vtk));
     if (c->round_graph && key == c->graph_key) return MVFIT_OK;
     drop_graph(c);
     hipStream_t cs;
@@ -473,9 +482,9 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
         SW.w[s] = to_dev(sw[s]);
     }
     const bool any_sdf = in.sdf_stages != 0;
-    if (any_sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on)
+    if (any_sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on && !c->vt.term)
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
-    if (c->obst.on || c->silt.on) in.sdf_service = 0;      // the scene and silhouette terms run in chained rounds only (no service path for them)
+    if (c->obst.on || c->silt.on || c->vt.term) in.sdf_service = 0;      // the scene, silhouette and vertex-target terms run in chained rounds only (no service path for them)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;

@@ -182,6 +182,8 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
         return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: mvfit_set_sdf's term is the interpenetration term (one per ctx): remove it first");
     if (c->silt.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the silhouette term uses the ctx's term slot: switch it off first");
+    if (c->vt.term)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->nv > 8192) return fail(c, MVFIT_E_UNSUPPORTED, "the scene term supports up to 8192 vertices (model has %d)", c->nv);
     if (!scene_first || num_scenes <= 0) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: bad argument (num_scenes=%d)", num_scenes);
     if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: grid_size %d outside [2, 128]", grid_size);
@@ -262,6 +264,8 @@ extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, f
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: no mask set is present (mvfit_set_silhouettes)");
+    if (c->vt.term)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->sdf_num_faces || c->obst.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: %s the ctx's term slot (one term per ctx): remove %s first",
                     c->obst.on ? "scene obstacles use" : "mvfit_set_sdf's term uses", c->obst.on ? "them" : "it");
@@ -307,6 +311,83 @@ extern "C" int mvfit_silhouette_loss(mvfit_ctx* c, const float* vertices, int nu
                     c->sil.body_max, num_bodies);
     HIP_OK(c, hipSetDevice(c->device));
     return sil_loss(c->sil, vertices, num_bodies, w_in, w_out, sigma, loss, g_vertices, winner, c->stream, c->err);
+}
+
+// The vertex-target set (include/mvfit.h; vertex_target.hip).  The set's three buffers are re-made only when K changes (B
+// cannot: free_problem_buffers drops them), so a re-freeze keeps their addresses.
+extern "C" int mvfit_set_vertex_targets(mvfit_ctx* c, int K, const float* targets, const float* weights) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (K == 0 || !targets) {                                // clear: the buffers stay for a next set of the same shape
+        c->vt.on = false;
+        c->vt.term = false;                                  // no targets, no term
+        return MVFIT_OK;
+    }
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (K < 1 || K > MVFIT_VERTEX_TARGETS_MAX)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_vertex_targets: K = %d outside [1, %d]", K, MVFIT_VERTEX_TARGETS_MAX);
+    if (!weights) return fail(c, MVFIT_E_ARG, "mvfit_set_vertex_targets: null weights");
+    for (size_t i = 0; i < (size_t)c->B * K; ++i)
+        if (!std::isfinite(weights[i]) || weights[i] < 0.f)
+            return fail(c, MVFIT_E_ARG, "mvfit_set_vertex_targets: weight %g of problem %d, target %d must be finite and >= 0",
+                        (double)weights[i], (int)(i / K), (int)(i % K));
+    const size_t row = (size_t)c->nv * 3 * sizeof(float);
+    VtxTargets& T = c->vt;
+    if (!T.partial || T.K != K) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        const bool term = T.term;
+        c->vtgt_mem.release();
+        T.on = false; T.term = false;                        // (a failed allocation leaves no set and no term behind)
+        T.targets = nullptr; T.weights = nullptr; T.partial = nullptr; T.K = 0;
+        HIP_OK(c, c->vtgt_mem.alloc(&T.targets, (size_t)c->B * K * row));
+        HIP_OK(c, c->vtgt_mem.alloc(&T.weights, (size_t)c->B * K * sizeof(float)));
+        HIP_OK(c, c->vtgt_mem.alloc(&T.partial, (size_t)c->B * vertex_target_blocks(c->nv) * sizeof(double), true));   // last: a set with partials is complete
+        T.K = K;
+        T.term = term;
+    }
+    HIP_OK(c, hipMemcpyAsync(T.targets, targets, (size_t)c->B * K * row, hipMemcpyDefault, c->stream));
+    HIP_OK(c, hipMemcpyAsync(T.weights, weights, (size_t)c->B * K * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));              // the caller may free both now
+    T.on = true;
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_vertex_target_loss(mvfit_ctx* c, const float* vertices, float* loss, float* g_vertices) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_vertex_target_loss: no target set is present (mvfit_set_vertex_targets)");
+    if (!vertices || !loss) return fail(c, MVFIT_E_ARG, "mvfit_vertex_target_loss: null %s", !vertices ? "vertices" : "loss");
+    HIP_OK(c, hipSetDevice(c->device));
+    const VtxTargets& T = c->vt;
+    const hipError_t e = launch_vertex_target(vertices, c->nv, c->B, T.K, T.targets, T.weights, nullptr, T.partial, loss, g_vertices, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "vertex-target launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+// The vertex-target term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (mvfit_api.hip: launch_term).
+extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (!enable) {                                           // off: the buffers stay for the next enable of this batch
+        c->vt.term = false;
+        return MVFIT_OK;
+    }
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: no target set is present (mvfit_set_vertex_targets)");
+    if (c->sdf_num_faces || c->obst.on || c->silt.on)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: the %s term uses the ctx's term slot (one term per ctx): remove it first",
+                    term_name(c));
+    VtxTargets& T = c->vt;
+    if (!T.part) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        c->vtterm_mem.release();                             // (what an earlier call that failed half-way left)
+        T.g_verts = nullptr; T.loss = nullptr;
+        HIP_OK(c, c->vtterm_mem.alloc(&T.g_verts, (size_t)c->B * c->nv * 3 * sizeof(float), true));
+        HIP_OK(c, c->vtterm_mem.alloc(&T.loss, (size_t)c->B * sizeof(float), true));
+        HIP_OK(c, c->vtterm_mem.alloc(&T.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
+    }
+    if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
+    T.term = true;
+    return MVFIT_OK;
 }
 
 extern "C" int mvfit_triangulate(mvfit_ctx* c, int B, int V, const float* keypoints, const double* intris, const double* extris,

@@ -125,6 +125,7 @@ class MvFit:
         self.V = 0
         self._obstacles = False
         self._sil_term = False
+        self._vt_term = False
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -225,6 +226,7 @@ class MvFit:
         if B != self.B or V != self.V:
             self._obstacles = False              # (the C side drops them with the batch they were frozen for)
             self._sil_term = False               # (and switches the silhouette term off)
+            self._vt_term = False                # (and clears the vertex targets with their term)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -502,6 +504,51 @@ class MvFit:
             return loss, g, win[:int(n.value)]
         return loss, g
 
+    def set_vertex_targets(self, targets, weights):
+        """Target vertex sets of the vertex-target term (include/mvfit.h:mvfit_set_vertex_targets): targets [B,K,Nv,3]
+        (tensor or array; copied), weights [B,K] finite and >= 0, 1 <= K <= 4.  A row whose weight is 0 is never read and may
+        hold anything.  A second call with the same K keeps the library's buffers (and the captured round graph)."""
+        t = self._dev(targets)
+        if t.dim() != 4 or t.shape[0] != self.B or t.shape[2] != self.nv or t.shape[3] != 3:
+            raise MvFitError('targets must be [%d, K, %d, 3], got %r' % (self.B, self.nv, tuple(t.shape)))
+        K = int(t.shape[1])
+        w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else weights
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(self.B, K))
+        rc = self._lib.mvfit_set_vertex_targets(self._ctx, K, t.data_ptr() if K else None, w.ctypes.data_as(C.POINTER(C.c_float)))
+        if K == 0 or rc not in (0, -1):          # (cleared, or a failed allocation: no set and no term; an argument error keeps both)
+            self._vt_term = False
+        self._check(rc)
+
+    def clear_vertex_targets(self):
+        """Remove the targets of set_vertex_targets (and switch their term off)."""
+        self._check(self._lib.mvfit_set_vertex_targets(self._ctx, 0, None, None))
+        self._vt_term = False
+
+    def vertex_target_loss(self, vertices, need_grad=True):
+        """The vertex-target loss at vertices[B,Nv,3] (include/mvfit.h:mvfit_vertex_target_loss): L_j = sum_k a_jk
+        ||V_j - T_jk||^2 and its vertex gradient 2 sum_k a_jk (V_j - T_jk).  Returns (loss[B], g_vertices[B,Nv,3] or None)."""
+        v = self._dev(vertices)
+        if tuple(v.shape) != (self.B, self.nv, 3):
+            raise MvFitError('vertices must be [%d, %d, 3], got %r' % (self.B, self.nv, tuple(v.shape)))
+        loss = torch.empty(self.B, device=self.device)
+        g = torch.empty_like(v) if need_grad else None
+        self._check(self._lib.mvfit_vertex_target_loss(self._ctx, v.data_ptr(), loss.data_ptr(),
+                                                       g.data_ptr() if need_grad else None))
+        return loss, g
+
+    def set_vertex_target_term(self):
+        """Make the vertex-target loss of the current targets a term of closure() and fit() (include/mvfit.h:
+        mvfit_set_vertex_target_term): a stage with coll_loss_weight w > 0 adds w^2 * L_j to problem j, with its gradient
+        through the model.  fit() runs such stages as chained rounds.  Needs set_problems and set_vertex_targets; excludes
+        set_sdf's term, scene obstacles and the silhouette term."""
+        self._check(self._lib.mvfit_set_vertex_target_term(self._ctx, 1))
+        self._vt_term = True
+
+    def clear_vertex_target_term(self):
+        """Switch the term of set_vertex_target_term off (the targets stay)."""
+        self._check(self._lib.mvfit_set_vertex_target_term(self._ctx, 0))
+        self._vt_term = False
+
     def set_sdf(self, faces, num_faces=1, grid_size=128):
         """Configure the interpenetration term (include/mvfit.h:mvfit_set_sdf).  ``faces`` [F,3]; ``num_faces``
         = how many leading triangles the op sees: 1 reproduces the reference's call site
@@ -717,8 +764,8 @@ class MvFit:
     def sdf_term_read(self):
         """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
         (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set; so does the silhouette term
-        (set_silhouette_term), whose S is the loss L_j itself."""
-        smp = None if (self._obstacles or self._sil_term) else torch.empty(self.B, self.nv, 4, device=self.device)
+        (set_silhouette_term) and the vertex-target term (set_vertex_target_term), whose S is the loss L_j itself."""
+        smp = None if (self._obstacles or self._sil_term or self._vt_term) else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S
