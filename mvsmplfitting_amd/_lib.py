@@ -66,12 +66,21 @@ class Options(C.Structure):
                 ('closure_vposer_helpers', C.c_int32), ('pass_kernel', C.c_int32), ('sdf_service', C.c_int32), ('work_queue', C.c_int32)]
 
 
+class TermMix(C.Structure):
+    """mvfit_term_mix (include/mvfit.h): the shares of the scene, silhouette and vertex-target terms in one fit."""
+    _fields_ = [('size', C.c_uint32), ('scene', C.c_float), ('silhouette', C.c_float), ('sil_w_in', C.c_float),
+                ('sil_w_out', C.c_float), ('sil_sigma', C.c_float), ('vertex_targets', C.c_float)]
+
+
+TERM_RECORD_FLOATS = 516      # MVFIT_TERM_RECORD_FLOATS
+
 EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'mvfit_set_problems', 'mvfit_set_joints3d',
            'mvfit_closure', 'mvfit_vertices', 'mvfit_vertices_backward', 'mvfit_full_pose', 'mvfit_fit', 'mvfit_fit_trace', 'mvfit_fit_stats', 'mvfit_decoder_stats', 'mvfit_debug_capture_pass', 'mvfit_sdf', 'mvfit_set_sdf', 'mvfit_sdf_term_read', 'mvfit_triangulate', 'mvfit_depth_guess', 'mvfit_umeyama', 'mvfit_project_points', 'mvfit_gather', 'mvfit_profile', 'mvfit_profile_read', 'mvfit_profile_vertex_pass', 'mvfit_profile_vertex_pass_ex', 'mvfit_pass_profile',
            'mvfit_options_default', 'mvfit_create_ex', 'mvfit_set_options', 'mvfit_get_options', 'mvfit_sdf_info',
            'mvfit_lbfgs_kat', 'mvfit_render_overlay', 'mvfit_render_scene', 'mvfit_scene_sdf_loss', 'mvfit_set_scene_obstacles', 'mvfit_scene_obstacles_read',
            'mvfit_associate_views', 'mvfit_set_silhouettes', 'mvfit_silhouettes_read', 'mvfit_silhouette_loss',
-           'mvfit_set_silhouette_term', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term']
+           'mvfit_set_silhouette_term', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
+           'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge']
 
 
 def load(path=None):
@@ -163,6 +172,14 @@ def load(path=None):
     lib.mvfit_vertex_target_loss.restype = C.c_int
     lib.mvfit_set_vertex_target_term.argtypes = [vp, C.c_int]
     lib.mvfit_set_vertex_target_term.restype = C.c_int
+    lib.mvfit_set_term_mix.argtypes = [vp, C.POINTER(TermMix)]
+    lib.mvfit_set_term_mix.restype = C.c_int
+    lib.mvfit_term_mix_read.argtypes = [vp, vp]
+    lib.mvfit_term_mix_read.restype = C.c_int
+    lib.mvfit_term_mix_cotangent.argtypes = [vp, C.c_float, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.mvfit_term_mix_cotangent.restype = C.c_int
+    lib.mvfit_term_mix_merge.argtypes = [vp, C.c_float, vp, vp, vp]
+    lib.mvfit_term_mix_merge.restype = C.c_int
     lib.mvfit_full_pose.argtypes = [vp, vp, C.c_uint32, vp]
     lib.mvfit_full_pose.restype = C.c_int
     lib.mvfit_gather.argtypes = [vp, vp, vp, vp, C.c_size_t]

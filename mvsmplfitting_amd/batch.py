@@ -41,6 +41,7 @@ from .init_guess import init_guess_batch, initial_params
 from .scene_fit import refine_scenes
 from .sequence import fit_sequences
 from .silhouette import refine_fit
+from .joint_refine import refine_joint
 from .temporal import smooth_sequences
 
 
@@ -251,6 +252,53 @@ def check_temporal(temporal, scene_collision=None, silhouettes=None):
     return cfg
 
 
+JOINT_PARTS = dict(scene_collision=dict(grid_size=32, robustifier=0.05, scale_factor=0.2),
+                   silhouettes=dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31),
+                   temporal=dict())
+
+
+def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouettes=None, temporal=None):
+    """fit_folder's ``joint`` option with the defaults filled in, or ValueError."""
+    if not isinstance(joint, dict) or 'weight' not in joint:
+        raise ValueError("joint: a dict with at least 'weight' (the mixed term's coll_loss_weight) and two parts")
+    unknown = set(joint) - {'weight', 'sweeps'} - set(JOINT_PARTS)
+    if unknown:
+        raise ValueError('joint: unknown keys %s' % sorted(unknown))
+    for name, single in (('scene_collision', scene_collision), ('silhouettes', silhouettes), ('temporal', temporal)):
+        if single is not None:
+            raise ValueError('joint and %s: the joint refinement takes the place of the single ones - name its parts inside joint' % name)
+    if is_seq:
+        raise ValueError('joint is not available with is_seq=True')
+    cfg = dict(weight=float(joint['weight']), sweeps=int(joint.get('sweeps', 3)))
+    if not cfg['weight'] > 0.0:
+        raise ValueError('joint: weight must be > 0')
+    if cfg['sweeps'] < 1:
+        raise ValueError('joint: sweeps must be >= 1')
+    parts = [k for k in JOINT_PARTS if joint.get(k) is not None]
+    if len(parts) < 2:
+        raise ValueError('joint: at least two of scene_collision, silhouettes and temporal must be given (a single part has an option of its own)')
+    for k in parts:
+        part = joint[k]
+        if not isinstance(part, dict) or 'share' not in part:
+            raise ValueError("joint: %s: a dict with at least 'share'" % k)
+        if k == 'silhouettes' and 'mask_root' not in part:
+            raise ValueError("joint: silhouettes: a dict with at least 'share' and 'mask_root'")
+        unknown = set(part) - {'share', 'mask_root' if k == 'silhouettes' else 'share'} - set(JOINT_PARTS[k])
+        if unknown:
+            raise ValueError('joint: %s: unknown keys %s' % (k, sorted(unknown)))
+        c = dict(JOINT_PARTS[k], **part)
+        if not float(c['share']) > 0.0 or not np.isfinite(float(c['share'])):
+            raise ValueError('joint: %s: share must be > 0' % k)
+        if k == 'scene_collision' and (int(c['grid_size']) < 2 or not float(c['robustifier']) > 0.0 or not float(c['scale_factor']) > 0.0):
+            raise ValueError('joint: scene_collision: grid_size must be >= 2, robustifier and scale_factor > 0')
+        if k == 'silhouettes' and (int(c['downscale']) < 1 or int(c['contour_stride']) < 1):
+            raise ValueError('joint: silhouettes: downscale and contour_stride must be >= 1')
+        cfg[k] = c
+    if 'scene_collision' in cfg and not multi:
+        raise ValueError('joint: scene_collision refines the persons of a frame together: it needs persons= a list of ids or \'all\'')
+    return cfg
+
+
 def mask_path(mask_root, serial, camera, frame, person=None):
     """The mask file of one view of one frame: `<mask_root>/<serial>/<camera>/<frame>.png`, or `<frame>_<id:03d>.png` for
     person ``id`` of the multi-person path."""
@@ -263,13 +311,14 @@ def silhouette_workspace_bytes(M, H, W, Nv):
     return M * H * W * 5 + M * H * 4 + M * (16 * Nv + 8 * -(-Nv // 256) + 92) + 8
 
 
-def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problems, rig, num_verts):
-    """The silhouette refinement of one serial's fitted problems (silhouette.refine_fit, the term inside the engine's fit).
+def load_serial_masks(cfg, serial, cams, frames, problems, rig, num_verts):
+    """The mask set of one serial's problems for MvFit.set_silhouettes: (masks uint8 [M,H,W], image_body [M], cams per image,
+    found = [(problem, view, path)]).
 
-    problems: [(frame index, person id or None)] per row of xf; cams: the serial's camera folder names, view v = rig row v;
+    problems: [(frame index, person id or None)] per problem; cams: the serial's camera folder names, view v = rig row v;
     rig = (R, t, f, c) of set_problems.  Every existing mask file of a (problem, view) is one image of that problem; masks
     are brought to 1 / downscale of their resolution (io_formats.downscale_mask) and the cameras follow with f and c divided
-    by it.  Returns (params, report); the engine is left without mask set and term."""
+    by it.  ValueError: no mask file at all, masks of different sizes, a workspace above max_mask_bytes."""
     k = int(cfg['downscale'])
     found = []
     for n, (f, person) in enumerate(problems):
@@ -304,6 +353,13 @@ def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problem
     view = np.array([v for _, v, _ in found])
     R, t, f, c = (np.asarray(a, np.float32) for a in rig)
     per_image = (R[view], t[view], (f[view] / np.float32(k)).astype(np.float32), (c[view] / np.float32(k)).astype(np.float32))
+    return masks, body, per_image, found
+
+
+def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problems, rig, num_verts):
+    """The silhouette refinement of one serial's fitted problems (silhouette.refine_fit, the term inside the engine's fit)
+    against the mask set of load_serial_masks.  Returns (params, report); the engine is left without mask set and term."""
+    masks, body, per_image, found = load_serial_masks(cfg, serial, cams, frames, problems, rig, num_verts)
     eng.set_silhouettes(masks, body, per_image, contour_stride=int(cfg['contour_stride']))
     try:
         out, report = refine_fit(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), w_in=float(cfg['w_in']),
@@ -314,11 +370,43 @@ def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problem
     return out, report
 
 
+def refine_serial_joint(eng, xf, stage, cfg, serial, cams, frames, problems, rig, num_verts, scene_sizes, seq_id, frame_idx):
+    """The joint refinement of one serial's fitted problems (joint_refine.refine_joint: the term mix inside the engine's fit)
+    with the parts of ``cfg`` (check_joint).  problems, cams, rig as for load_serial_masks; scene_sizes: problems per frame
+    (frame-major rows); seq_id / frame_idx: every problem's track and its position in the serial's frame list.  Returns
+    (params, report); the engine is left without mask set, mix, targets and obstacles."""
+    shares, kw = {}, {}
+    sil = cfg.get('silhouettes')
+    if 'scene_collision' in cfg:
+        sc = cfg['scene_collision']
+        shares['scene'] = float(sc['share'])
+        kw.update(scene_sizes=scene_sizes, grid_size=int(sc['grid_size']), scale_factor=float(sc['scale_factor']),
+                  robustifier=float(sc['robustifier']))
+    if 'temporal' in cfg:
+        shares['temporal'] = float(cfg['temporal']['share'])
+        kw.update(seq_id=seq_id, frame_idx=frame_idx)
+    found = masks = None
+    if sil is not None:
+        shares['silhouette'] = float(sil['share'])
+        kw.update(w_in=float(sil['w_in']), w_out=float(sil['w_out']), sigma=float(sil['sigma']))
+        masks, body, per_image, found = load_serial_masks(sil, serial, cams, frames, problems, rig, num_verts)
+        eng.set_silhouettes(masks, body, per_image, contour_stride=int(sil['contour_stride']))
+    try:
+        out, report = refine_joint(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), shares=shares,
+                                   sweeps=int(cfg['sweeps']), **kw)
+    finally:
+        if sil is not None:
+            eng.clear_silhouettes()
+    if found is not None:
+        report = dict(report, images=[(int(n), int(v)) for n, v, _ in found], mask_size=tuple(masks.shape[1:]))
+    return out, report
+
+
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
                save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
-               silhouettes=None, temporal=None):
+               silhouettes=None, temporal=None, joint=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -373,7 +461,18 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     persons=0, one per person id on the multi-person path, where a frame the person is absent from breaks the chain.  The
     serial's result gains ``temporal_report`` (smooth_sequences'), ``timing`` a 'temporal' entry, and ``final_loss`` is the
     report's loss (smoothing term included, neighbours frozen at the result).  ValueError for unknown keys, a missing or
-    non-positive weight, sweeps < 1, or together with scene_collision or silhouettes (one term slot)."""
+    non-positive weight, sweeps < 1, or together with scene_collision or silhouettes (one term slot).
+    joint: None, or dict(weight=..., sweeps=3, scene_collision=dict(share=..., grid_size=32, robustifier=0.05,
+    scale_factor=0.2), silhouettes=dict(share=..., mask_root=..., w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1,
+    downscale=1, max_mask_bytes=2**31), temporal=dict(share=...)) with at least two of the three parts - after the serial's
+    batched fit the problems are refined by joint_refine.refine_joint: ONE fit per sweep carries weight^2 * (the parts'
+    shares times the scene collision, silhouette and temporal terms) behind the last stage's weights (the term mix inside the
+    engine's fit), obstacles and neighbours frozen where the sweep starts; the problems linked by a frame (scene part) or a
+    track (temporal part) keep a sweep only if their joint energy fell.  Masks, scenes and tracks are those of the three
+    single options.  The serial's result gains ``joint_report`` (refine_joint's, plus images and mask_size with a silhouette
+    part), ``timing`` a 'joint' entry, and ``final_loss`` is the report's loss.  ValueError together with any of the three
+    single options, with is_seq=True, for a scene part without persons=, fewer than two parts, unknown keys and non-positive
+    numbers."""
     import time as _time
 
     def _tick(key, t0):
@@ -406,6 +505,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
     sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision) if silhouettes is not None else None
     tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
+    joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal) if joint is not None else None
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -603,6 +703,17 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             xf = xr.to(xf.dtype)
             final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
             _t = _tick('temporal', _t)
+        joint_report = None
+        if joint_cfg is not None:
+            # a frame is a scene (the problems are frame-major), a person id a track over the serial's frame list
+            if has.all():
+                eng.set_joints3d(ann[:, :, :3], c3)
+            sizes = [int((pf == f).sum()) for f in sorted(set(pf.tolist()))]
+            xr, joint_report = refine_serial_joint(eng, xf, stages_for(bool(has.all()))[-1], joint_cfg, serial, cams, frames,
+                                                   [(int(f), int(p)) for f, p in prob], rig, eng.nv, sizes, pp, pf)
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('joint', _t)
         full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
         xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
         res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
@@ -627,6 +738,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             out['silhouette_report'] = silhouette_report
         if temporal_report is not None:
             out['temporal_report'] = temporal_report
+        if joint_report is not None:
+            out['joint_report'] = joint_report
         if association is not None:
             out['association'] = association
         _t = _tick('write', _t)
@@ -741,6 +854,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 xf = xr.to(xf.dtype)
                 final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
                 _t = _tick('temporal', _t)
+            joint_report = None
+            if joint_cfg is not None:
+                if has.all():
+                    eng.set_joints3d(ann[:, :, :3], c3)
+                xr, joint_report = refine_serial_joint(eng, xf, stages_for(bool(has.all()))[-1], joint_cfg, serial, cams, frames,
+                                                       [(f, None) for f in range(F)], rig, eng.nv, None, np.zeros(F, np.int64),
+                                                       np.arange(F))
+                xf = xr.to(xf.dtype)
+                final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
+                _t = _tick('joint', _t)
             full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
             xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
             res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
@@ -765,6 +888,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 results[serial]['silhouette_report'] = silhouette_report
             if temporal_report is not None:
                 results[serial]['temporal_report'] = temporal_report
+            if joint_report is not None:
+                results[serial]['joint_report'] = joint_report
             _t = _tick('write', _t)
             if save_images:
                 results[serial]['images'] = render_serial_images(
@@ -779,4 +904,5 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
 
 
 __all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
-           'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes']
+           'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes',
+           'check_joint', 'load_serial_masks', 'refine_serial_joint']

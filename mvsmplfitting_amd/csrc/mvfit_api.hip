@@ -194,6 +194,11 @@ void mvfit::free_obstacles(mvfit_ctx* c) {
     c->obst = Obstacles{};
 }
 
+void mvfit::free_term_mix(mvfit_ctx* c) {
+    c->mix_mem.release();
+    c->mix = TermMix{};
+}
+
 void mvfit::free_vertex_targets(mvfit_ctx* c) {
     c->vtgt_mem.release();
     c->vtterm_mem.release();
@@ -215,6 +220,7 @@ static void free_problem_buffers(mvfit_ctx* c) {
     c->silterm_mem.release();           // the silhouette term goes with the batch it was enabled for
     c->silt = SilTerm{};
     free_vertex_targets(c);             // and so do the vertex targets and their term
+    free_term_mix(c);                   // and the term mix
 }
 
 extern "C" void mvfit_destroy(mvfit_ctx* c) {
@@ -315,6 +321,8 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the silhouette term uses the ctx's term slot: switch it off first");
     if (c->vt.term && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the vertex-target term uses the ctx's term slot: switch it off first");
+    if (c->mix.on && faces && num_faces != 0)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the term mix uses the ctx's term slot (the one-person term is not part of it): switch it off first");
     HIP_OK(c, hipSetDevice(c->device));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     drop_graph(c);
@@ -342,9 +350,13 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
 extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
     if (!c) return MVFIT_E_ARG;
     if (!c->pb.sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
-    if (samples && (c->obst.on || c->silt.on || c->vt.term))
+    if (samples && round_term(c))
         return fail(c, MVFIT_E_UNSUPPORTED, "mvfit_sdf_term_read: the %s term keeps no per-vertex samples (sums only)", term_name(c));
     HIP_OK(c, hipSetDevice(c->device));
+    if (c->mix.on) {                                               // the weighted sum of the parts: penalty = w^2 sums
+        if (sums) HIP_OK(c, hipMemcpyAsync(sums, c->mix.sums, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        return MVFIT_OK;
+    }
     if (c->silt.on || c->vt.term) {                                // L_j itself (the record holds its root)
         const float* L = c->vt.term ? c->vt.loss : c->silt.loss;
         if (sums) HIP_OK(c, hipMemcpyAsync(sums, L, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -395,13 +407,43 @@ int mvfit::ensure_sdf_buffers(mvfit_ctx* c) {
 // DevPose::box_part is set) when the split-fp16 basis exists and the launch is one 32-problem chunk per workgroup
 bool mvfit::pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
     const int chunks = (b_hi + 31) / 32 - b_lo / 32;
-    return !c->obst.on && !c->silt.on && !c->vt.term && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
+    return !round_term(c) && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
 }
 
 // the interpenetration term of a chained round behind its vertex pass: against the frozen obstacles when they are set,
 // the silhouette term when it is on (silhouette evaluation -> dense pull-back -> record), the vertex-target term when it is
-// (target kernel -> the same pull-back), else the one-person term of mvfit_set_sdf
+// (target kernel -> the same pull-back), else the one-person term of mvfit_set_sdf.  The term mix comes first: the live vertex
+// terms' evaluations, their mixed cotangent in front of ONE pull-back, and - with a scene share - the scene term into a record
+// of its own and the merge of the two records (term_mix.hip)
 hipError_t mvfit::launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
+    if (c->mix.on) {
+        const TermMix& X = c->mix;
+        const bool sil = X.silhouette > 0.f, vt = X.vertex_targets > 0.f, scene = X.scene > 0.f;
+        hipError_t e = hipSuccess;
+        if (sil && sil_round(c->sil, verts, c->B, X.w_in, X.w_out, X.sigma, gate, c->silt.loss, c->silt.g_verts, st, c->err))
+            return hipErrorLaunchFailure;
+        if (vt) {
+            const VtxTargets& T = c->vt;
+            e = launch_vertex_target(verts, c->nv, c->B, T.K, T.targets, T.weights, gate, T.partial, T.loss, T.g_verts, st);
+            if (e != hipSuccess) return e;
+        }
+        // one live vertex term with share 1: its own buffers go to the pull-back as they are
+        const float *g = X.g_verts, *L = X.loss;
+        if (sil && !vt && X.silhouette == 1.f) { g = c->silt.g_verts; L = c->silt.loss; }
+        else if (vt && !sil && X.vertex_targets == 1.f) { g = c->vt.g_verts; L = c->vt.loss; }
+        else {
+            e = launch_term_mix_cotangent(c->nv, c->B, X.silhouette, c->silt.g_verts, c->silt.loss, X.vertex_targets, c->vt.g_verts,
+                                          c->vt.loss, gate, X.g_verts, X.loss, scene ? nullptr : X.parts, X.sums, st);
+            if (e != hipSuccess) return e;
+        }
+        e = launch_silhouette_pullback(c->M, c->P, c->B, c->Bpad, gate, g, L, X.part, scene ? X.rec_verts : c->pb.sdf_adj, st);
+        if (e != hipSuccess || !scene) return e;
+        e = launch_scene_term(c->M, c->P, verts, c->B, c->obst.tab, c->obst.box, c->obst.phi, c->obst.grid, c->obst.rob, gate,
+                              c->pb.sdf_box, c->pb.sdf_entries, X.rec_scene, st);
+        if (e != hipSuccess) return e;
+        return launch_term_mix_record(c->B, X.scene, X.rec_scene, X.rec_verts, X.silhouette, sil ? c->silt.loss : nullptr,
+                                      X.vertex_targets, vt ? c->vt.loss : nullptr, gate, c->pb.sdf_adj, X.parts, X.sums, st);
+    }
     if (c->vt.term) {
         const VtxTargets& T = c->vt;
         const hipError_t e = launch_vertex_target(verts, c->nv, c->B, T.K, T.targets, T.weights, gate, T.partial, T.loss, T.g_verts, st);
@@ -543,7 +585,7 @@ extern "C" int mvfit_closure(mvfit_ctx* c, const mvfit_weights* w, const float* 
     int rc = check_flags(c, w->flags);
     if (rc) return rc;
     const bool sdf = w->coll_loss_weight > 0.f;
-    if (sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on && !c->vt.term)
+    if (sdf && !c->sdf_num_faces && !round_term(c))
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
     HIP_OK(c, hipSetDevice(c->device));
     if (c->opt.closure_vposer_helpers && (w->flags & MVFIT_F_VPOSER) && c->vps_mem && !sdf)

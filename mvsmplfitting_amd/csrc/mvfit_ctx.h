@@ -18,6 +18,7 @@
 #include "fit_plan.h"
 #include "launchers.h"
 #include "silhouette.h"
+#include "term_mix.h"
 #include "vertex_target.h"
 
 using namespace mvfit;          // (the three host files only: their bodies name the library's types unqualified)
@@ -69,6 +70,7 @@ struct mvfit_ctx {
     // is sized by Bpad) and the obstacles go whenever the problems go, and each may be replaced on its own before that
     DevPool problem_mem, ring_mem, obst_mem, silterm_mem;
     DevPool vtgt_mem, vtterm_mem;      // the vertex-target set (re-made when (B, K) change) and its term's round buffers
+    DevPool mix_mem;                   // the term mix's round buffers (mvfit_set_term_mix)
     // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
     DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
     DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
@@ -89,6 +91,8 @@ struct mvfit_ctx {
     SilTerm silt;
     // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
     VtxTargets vt;
+    // the weighted sum of the scene, silhouette and vertex-target terms (mvfit_set_term_mix, term_mix.hip)
+    TermMix mix;
     // ---- model ----
     DevModel M{};
     bool upload_failed = false, alloc_failed = false;
@@ -188,6 +192,11 @@ int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t 
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
 void free_vertex_targets(mvfit_ctx* c);
-inline const char* term_name(const mvfit_ctx* c) { return c->vt.term ? "vertex-target" : c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf"; }
+void free_term_mix(mvfit_ctx* c);
+inline const char* term_name(const mvfit_ctx* c) {
+    return c->mix.on ? "mix" : c->vt.term ? "vertex-target" : c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf";
+}
+// a term other than mvfit_set_sdf's is configured: it runs in chained rounds only and keeps no per-vertex samples
+inline bool round_term(const mvfit_ctx* c) { return c->mix.on || c->obst.on || c->silt.on || c->vt.term; }
 
 }  // namespace mvfit

@@ -69,7 +69,27 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         vtk.targets = c->vt.targets; vtk.weights = c->vt.weights; vtk.partial = c->vt.partial; vtk.g_verts = c->vt.g_verts;
         vtk.loss = c->vt.loss; vtk.part = c->vt.part; vtk.K = c->vt.K;
     }
-    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk) + sizeof(vtk));
+    // (the term mix: what its live components bake in - as above, so a re-freeze with the same shapes changes nothing - its own
+    // buffers, the three shares and the silhouette scalars)
+    struct { const void *g_verts, *loss, *part, *rec_scene, *rec_verts, *parts, *sums; float scene, silhouette, vertex_targets, w_in, w_out, sigma; } mixk;
+    memset(&mixk, 0, sizeof(mixk));
+    if (c->mix.on) {
+        const TermMix& X = c->mix;
+        if (X.scene <= 0.f) memset(&obst, 0, sizeof(obst));           // (obstacles may be set without taking part)
+        if (X.silhouette > 0.f) {
+            silk.ws = c->sil.ws.get(); silk.cs = c->sil.cs.get(); silk.g_verts = c->silt.g_verts; silk.loss = c->silt.loss;
+            silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
+        }
+        if (X.vertex_targets > 0.f) {
+            vtk.targets = c->vt.targets; vtk.weights = c->vt.weights; vtk.partial = c->vt.partial; vtk.g_verts = c->vt.g_verts;
+            vtk.loss = c->vt.loss; vtk.K = c->vt.K;
+        }
+        mixk.g_verts = X.g_verts; mixk.loss = X.loss; mixk.part = X.part; mixk.rec_scene = X.rec_scene; mixk.rec_verts = X.rec_verts;
+        mixk.parts = X.parts; mixk.sums = X.sums;
+        mixk.scene = X.scene; mixk.silhouette = X.silhouette; mixk.vertex_targets = X.vertex_targets;
+        mixk.w_in = X.w_in; mixk.w_out = X.w_out; mixk.sigma = X.sigma;
+    }
+    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk) + sizeof(vtk) + sizeof(mixk));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
     memcpy(k, &O, sizeof(O)); k += sizeof(O);
@@ -79,7 +99,8 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     memcpy(k, &c->opt.pass_kernel, sizeof(int)); k += sizeof(int);
     memcpy(k, &obst, sizeof(obst)); k += sizeof(obst);
     memcpy(k, &silk, sizeof(silk)); k += sizeof(silk);
-    memcpy(k, &vtk, sizeof(vtk));
+    memcpy(k, &vtk, sizeof(vtk)); k += sizeof(vtk);
+    memcpy(k, &mixk, sizeof(mixk));
     if (c->round_graph && key == c->graph_key) return MVFIT_OK;
     drop_graph(c);
     hipStream_t cs;
@@ -482,9 +503,9 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
         SW.w[s] = to_dev(sw[s]);
     }
     const bool any_sdf = in.sdf_stages != 0;
-    if (any_sdf && !c->sdf_num_faces && !c->obst.on && !c->silt.on && !c->vt.term)
+    if (any_sdf && !c->sdf_num_faces && !round_term(c))
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
-    if (c->obst.on || c->silt.on || c->vt.term) in.sdf_service = 0;      // the scene, silhouette and vertex-target terms run in chained rounds only (no service path for them)
+    if (round_term(c)) in.sdf_service = 0;      // the scene, silhouette and vertex-target terms and their mix run in chained rounds only (no service path for them)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;

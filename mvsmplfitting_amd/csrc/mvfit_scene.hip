@@ -174,6 +174,7 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     HIP_OK(c, hipSetDevice(c->device));
     if (!vertices) {                                         // remove: the buffers stay for the next freeze of this batch
         c->obst.on = false;
+        if (c->mix.scene > 0.f) c->mix.on = false;           // no obstacles, no mix that uses them
         return MVFIT_OK;
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
@@ -200,7 +201,9 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
         HIP_OK(c, c->obst_mem.alloc(&c->obst.phi, (size_t)c->B * nvox * 4));
         c->obst.grid = grid_size;
     }
-    c->obst.on = false;                                      // a failed freeze leaves no term behind
+    c->obst.on = false;                                      // a failed freeze leaves no term behind (and no mix that uses it)
+    const bool mix = c->mix.on;
+    if (c->mix.scene > 0.f) c->mix.on = false;
     rc = ensure_sdf_buffers(c);
     if (rc) return rc;
     hipError_t e = launch_scene_null_boxes(c->pb.sdf_box, c->B, c->stream);
@@ -210,6 +213,7 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (rc) return rc;
     c->obst.rob = robustifier;
     c->obst.on = true;
+    c->mix.on = mix;
     return MVFIT_OK;
 }
 
@@ -232,6 +236,7 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
     if (num_images == 0) {                                   // clear: the work areas stay for a next set of the same size
         c->sil.on = false;
         c->silt.on = false;                                  // no masks, no term
+        if (c->mix.silhouette > 0.f) c->mix.on = false;      // and no mix that uses them
         return MVFIT_OK;
     }
     if (num_images < 0 || num_images > 65535 || height < 2 || height > 8192 || width < 2 || width > 8192)
@@ -245,13 +250,43 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
                            c->stream, c->err);
     // a set that replaces the one of an enabled term must fit the batch like the first (the term's kernels index the
     // problems' buffers by image_body); a failed or unfit set leaves no term behind
-    if (c->silt.on && (rc || c->sil.body_min < 0 || c->sil.body_max >= c->B)) {
+    const bool in_mix = c->mix.on && c->mix.silhouette > 0.f;
+    if ((c->silt.on || in_mix) && (rc || c->sil.body_min < 0 || c->sil.body_max >= c->B)) {
         c->silt.on = false;
+        if (in_mix) c->mix.on = false;
         if (!rc)
             return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: image_body holds %d .. %d, outside the %d problems of the enabled "
                         "silhouette term (the term is switched off)", c->sil.body_min, c->sil.body_max, c->B);
     }
     return rc;
+}
+
+// the round buffers of the silhouette term (cotangent, loss, pull-back partials) for the current batch: allocated by the
+// first caller - the term's own setter or the term mix - and kept while B stays
+static int ensure_sil_round(mvfit_ctx* c) {
+    if (c->silt.part) return MVFIT_OK;
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    c->silterm_mem.release();                                // (what an earlier call that failed half-way left)
+    c->silt = SilTerm{};
+    float *g = nullptr, *l = nullptr;
+    HIP_OK(c, c->silterm_mem.alloc(&g, (size_t)c->B * c->nv * 3 * sizeof(float), true));
+    HIP_OK(c, c->silterm_mem.alloc(&l, (size_t)c->B * sizeof(float), true));
+    c->silt.g_verts = g; c->silt.loss = l;
+    HIP_OK(c, c->silterm_mem.alloc(&c->silt.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
+    return MVFIT_OK;
+}
+
+// the same for the vertex-target term
+static int ensure_vt_round(mvfit_ctx* c) {
+    VtxTargets& T = c->vt;
+    if (T.part) return MVFIT_OK;
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    c->vtterm_mem.release();                                 // (what an earlier call that failed half-way left)
+    T.g_verts = nullptr; T.loss = nullptr;
+    HIP_OK(c, c->vtterm_mem.alloc(&T.g_verts, (size_t)c->B * c->nv * 3 * sizeof(float), true));
+    HIP_OK(c, c->vtterm_mem.alloc(&T.loss, (size_t)c->B * sizeof(float), true));
+    HIP_OK(c, c->vtterm_mem.alloc(&T.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
+    return MVFIT_OK;
 }
 
 // The silhouette term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (mvfit_api.hip: launch_term).
@@ -264,6 +299,7 @@ extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, f
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: no mask set is present (mvfit_set_silhouettes)");
+    if (c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the term mix uses the ctx's term slot: switch it off first");
     if (c->vt.term)
         return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->sdf_num_faces || c->obst.on)
@@ -275,16 +311,7 @@ extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, f
     if (c->sil.body_min < 0 || c->sil.body_max >= c->B)
         return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_term: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min,
                     c->sil.body_max, c->B);
-    if (!c->silt.part) {
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        c->silterm_mem.release();                            // (what an earlier call that failed half-way left)
-        c->silt = SilTerm{};
-        float *g = nullptr, *l = nullptr;
-        HIP_OK(c, c->silterm_mem.alloc(&g, (size_t)c->B * c->nv * 3 * sizeof(float), true));
-        HIP_OK(c, c->silterm_mem.alloc(&l, (size_t)c->B * sizeof(float), true));
-        c->silt.g_verts = g; c->silt.loss = l;
-        HIP_OK(c, c->silterm_mem.alloc(&c->silt.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
-    }
+    if (const int rc = ensure_sil_round(c)) return rc;
     if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
     c->silt.w_in = w_in; c->silt.w_out = w_out; c->silt.sigma = sigma;
     c->silt.on = true;
@@ -321,6 +348,7 @@ extern "C" int mvfit_set_vertex_targets(mvfit_ctx* c, int K, const float* target
     if (K == 0 || !targets) {                                // clear: the buffers stay for a next set of the same shape
         c->vt.on = false;
         c->vt.term = false;                                  // no targets, no term
+        if (c->mix.vertex_targets > 0.f) c->mix.on = false;  // and no mix that uses them
         return MVFIT_OK;
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
@@ -335,15 +363,17 @@ extern "C" int mvfit_set_vertex_targets(mvfit_ctx* c, int K, const float* target
     VtxTargets& T = c->vt;
     if (!T.partial || T.K != K) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
-        const bool term = T.term;
+        const bool term = T.term, mix = c->mix.on;
         c->vtgt_mem.release();
         T.on = false; T.term = false;                        // (a failed allocation leaves no set and no term behind)
+        if (c->mix.vertex_targets > 0.f) c->mix.on = false;
         T.targets = nullptr; T.weights = nullptr; T.partial = nullptr; T.K = 0;
         HIP_OK(c, c->vtgt_mem.alloc(&T.targets, (size_t)c->B * K * row));
         HIP_OK(c, c->vtgt_mem.alloc(&T.weights, (size_t)c->B * K * sizeof(float)));
         HIP_OK(c, c->vtgt_mem.alloc(&T.partial, (size_t)c->B * vertex_target_blocks(c->nv) * sizeof(double), true));   // last: a set with partials is complete
         T.K = K;
         T.term = term;
+        c->mix.on = mix;
     }
     HIP_OK(c, hipMemcpyAsync(T.targets, targets, (size_t)c->B * K * row, hipMemcpyDefault, c->stream));
     HIP_OK(c, hipMemcpyAsync(T.weights, weights, (size_t)c->B * K * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -373,20 +403,110 @@ extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (!c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: no target set is present (mvfit_set_vertex_targets)");
+    if (c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: the term mix uses the ctx's term slot: switch it off first");
     if (c->sdf_num_faces || c->obst.on || c->silt.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: the %s term uses the ctx's term slot (one term per ctx): remove it first",
                     term_name(c));
-    VtxTargets& T = c->vt;
-    if (!T.part) {
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        c->vtterm_mem.release();                             // (what an earlier call that failed half-way left)
-        T.g_verts = nullptr; T.loss = nullptr;
-        HIP_OK(c, c->vtterm_mem.alloc(&T.g_verts, (size_t)c->B * c->nv * 3 * sizeof(float), true));
-        HIP_OK(c, c->vtterm_mem.alloc(&T.loss, (size_t)c->B * sizeof(float), true));
-        HIP_OK(c, c->vtterm_mem.alloc(&T.part, vjp_part_bytes(c->Bpad, c->nv)));      // last: a term with partials is complete
-    }
+    if (const int rc = ensure_vt_round(c)) return rc;
     if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
-    T.term = true;
+    c->vt.term = true;
+    return MVFIT_OK;
+}
+
+// The weighted sum of the scene, silhouette and vertex-target terms inside mvfit_fit / mvfit_closure (include/mvfit.h): state
+// and buffers only - the rounds launch it (mvfit_api.hip: launch_term).
+extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
+    if (!c) return MVFIT_E_ARG;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (!mix) {                                              // off: the buffers stay for the next enable of this batch
+        c->mix.on = false;
+        return MVFIT_OK;
+    }
+    if (mix->size < sizeof(mvfit_term_mix)) return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: size %u < %zu", mix->size, sizeof(mvfit_term_mix));
+    const float lam[3] = {mix->scene, mix->silhouette, mix->vertex_targets};
+    int live = 0;
+    for (float l : lam) {
+        if (!std::isfinite(l) || l < 0.f)
+            return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: the shares (%g, %g, %g) must be finite and >= 0", (double)lam[0], (double)lam[1], (double)lam[2]);
+        live += l > 0.f;
+    }
+    if (live < 2)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: at least two shares must be > 0 (a single term keeps its own setter)");
+    if (lam[1] > 0.f && (!std::isfinite(mix->sil_w_in) || !std::isfinite(mix->sil_w_out) || !std::isfinite(mix->sil_sigma) ||
+                         mix->sil_w_in < 0.f || mix->sil_w_out < 0.f))
+        return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: sil_w_in = %g and sil_w_out = %g must be finite and >= 0, sil_sigma = %g finite",
+                    (double)mix->sil_w_in, (double)mix->sil_w_out, (double)mix->sil_sigma);
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (c->sdf_num_faces)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: mvfit_set_sdf's term uses the ctx's term slot and is not part of the mix: remove it first");
+    if (c->silt.on || c->vt.term)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: the %s term is on through its own setter: switch it off first", term_name(c));
+    if (lam[0] > 0.f && !c->obst.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: scene > 0 needs obstacles (mvfit_set_scene_obstacles)");
+    if (lam[1] > 0.f && !c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: silhouette > 0 needs a mask set (mvfit_set_silhouettes)");
+    if (lam[2] > 0.f && !c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: vertex_targets > 0 needs a target set (mvfit_set_vertex_targets)");
+    if (lam[1] > 0.f && (c->sil.body_min < 0 || c->sil.body_max >= c->B))
+        return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min, c->sil.body_max, c->B);
+    TermMix& X = c->mix;
+    if (!X.sums) {
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        free_term_mix(c);                                    // (what an earlier call that failed half-way left)
+        HIP_OK(c, c->mix_mem.alloc(&X.g_verts, (size_t)c->B * c->nv * 3 * sizeof(float), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.loss, (size_t)c->B * sizeof(float), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.part, vjp_part_bytes(c->Bpad, c->nv)));
+        HIP_OK(c, c->mix_mem.alloc(&X.rec_scene, (size_t)c->B * sizeof(SdfAdj), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.rec_verts, (size_t)c->B * sizeof(SdfAdj), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.parts, (size_t)c->B * 3 * sizeof(float), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.sums, (size_t)c->B * sizeof(float), true));      // last: a mix with sums is complete
+    }
+    X.on = false;                                            // (a failed allocation below leaves no mix behind)
+    if (lam[1] > 0.f) { if (const int rc = ensure_sil_round(c)) return rc; }
+    if (lam[2] > 0.f) { if (const int rc = ensure_vt_round(c)) return rc; }
+    if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
+    X.scene = lam[0]; X.silhouette = lam[1]; X.vertex_targets = lam[2];
+    X.w_in = mix->sil_w_in; X.w_out = mix->sil_w_out; X.sigma = mix->sil_sigma;
+    X.on = true;
+    return MVFIT_OK;
+}
+
+// the mix's two kernels on the caller's buffers (include/mvfit.h): what the tests hold against the NumPy restatement
+extern "C" int mvfit_term_mix_cotangent(mvfit_ctx* c, float silhouette, const float* g_sil, const float* L_sil, float vertex_targets,
+                                        const float* g_vt, const float* L_vt, float* g, float* L_v) {
+    if (!c) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    const bool sil = silhouette > 0.f, vt = vertex_targets > 0.f;
+    if (!std::isfinite(silhouette) || !std::isfinite(vertex_targets) || silhouette < 0.f || vertex_targets < 0.f || (!sil && !vt))
+        return fail(c, MVFIT_E_ARG, "mvfit_term_mix_cotangent: the shares (%g, %g) must be finite and >= 0, one of them > 0",
+                    (double)silhouette, (double)vertex_targets);
+    if (!g || !L_v || (sil && (!g_sil || !L_sil)) || (vt && (!g_vt || !L_vt)))
+        return fail(c, MVFIT_E_ARG, "mvfit_term_mix_cotangent: null buffer of a live component or of the result");
+    HIP_OK(c, hipSetDevice(c->device));
+    const hipError_t e = launch_term_mix_cotangent(c->nv, c->B, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt, nullptr, g, L_v,
+                                                   nullptr, nullptr, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "term-mix cotangent launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_term_mix_merge(mvfit_ctx* c, float scene, const float* rec_scene, const float* rec_verts, float* rec) {
+    static_assert(sizeof(SdfAdj) == MVFIT_TERM_RECORD_FLOATS * sizeof(float), "include/mvfit.h states the record's size");
+    if (!c) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!std::isfinite(scene) || !(scene > 0.f)) return fail(c, MVFIT_E_ARG, "mvfit_term_mix_merge: scene = %g must be finite and > 0", (double)scene);
+    if (!rec_scene || !rec_verts || !rec) return fail(c, MVFIT_E_ARG, "mvfit_term_mix_merge: null record buffer");
+    if ((reinterpret_cast<uintptr_t>(rec_scene) | reinterpret_cast<uintptr_t>(rec_verts) | reinterpret_cast<uintptr_t>(rec)) & 3)
+        return fail(c, MVFIT_E_ARG, "mvfit_term_mix_merge: record buffers must be 4-byte aligned");
+    HIP_OK(c, hipSetDevice(c->device));
+    const hipError_t e = launch_term_mix_record(c->B, scene, reinterpret_cast<const SdfAdj*>(rec_scene), reinterpret_cast<const SdfAdj*>(rec_verts),
+                                                0.f, nullptr, 0.f, nullptr, nullptr, reinterpret_cast<SdfAdj*>(rec), nullptr, nullptr, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "term-mix record launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_term_mix_read(mvfit_ctx* c, float* parts) {
+    if (!c) return MVFIT_E_ARG;
+    if (!parts) return fail(c, MVFIT_E_ARG, "mvfit_term_mix_read: null parts");
+    if (!c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_term_mix_read: the term mix is off (mvfit_set_term_mix)");
+    HIP_OK(c, hipSetDevice(c->device));
+    HIP_OK(c, hipMemcpyAsync(parts, c->mix.parts, (size_t)c->B * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 

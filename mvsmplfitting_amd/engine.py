@@ -126,6 +126,7 @@ class MvFit:
         self._obstacles = False
         self._sil_term = False
         self._vt_term = False
+        self._mix = None                         # the shares of set_term_mix while it is on
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -227,6 +228,7 @@ class MvFit:
             self._obstacles = False              # (the C side drops them with the batch they were frozen for)
             self._sil_term = False               # (and switches the silhouette term off)
             self._vt_term = False                # (and clears the vertex targets with their term)
+            self._mix = None                     # (and switches the term mix off)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -423,6 +425,8 @@ class MvFit:
         """Remove the obstacles of set_scene_obstacles."""
         self._check(self._lib.mvfit_set_scene_obstacles(self._ctx, None, None, 0, 0, 0.0, 0.0))
         self._obstacles = False
+        if self._mix and self._mix[0] > 0:
+            self._mix = None                     # (no obstacles, no mix that uses them)
 
     # ------------------------------------------------------------------ silhouette term (include/mvfit.h:mvfit_set_silhouettes)
     def set_silhouettes(self, masks, image_body, cams, contour_stride=1):
@@ -455,6 +459,8 @@ class MvFit:
         """Remove the mask set of set_silhouettes."""
         self._check(self._lib.mvfit_set_silhouettes(self._ctx, 0, 0, 0, None, None, None, None, None, None, 1))
         self._sil_term = False                   # (no masks, no term: the C side switches it off)
+        if self._mix and self._mix[1] > 0:
+            self._mix = None
 
     def set_silhouette_term(self, w_in=1.0, w_out=1.0, sigma=0.0):
         """Make the silhouette loss of the current mask set a term of closure() and fit() (include/mvfit.h:
@@ -523,6 +529,8 @@ class MvFit:
         """Remove the targets of set_vertex_targets (and switch their term off)."""
         self._check(self._lib.mvfit_set_vertex_targets(self._ctx, 0, None, None))
         self._vt_term = False
+        if self._mix and self._mix[2] > 0:
+            self._mix = None                     # (no targets, no mix that uses them: the C side switches it off)
 
     def vertex_target_loss(self, vertices, need_grad=True):
         """The vertex-target loss at vertices[B,Nv,3] (include/mvfit.h:mvfit_vertex_target_loss): L_j = sum_k a_jk
@@ -548,6 +556,50 @@ class MvFit:
         """Switch the term of set_vertex_target_term off (the targets stay)."""
         self._check(self._lib.mvfit_set_vertex_target_term(self._ctx, 0))
         self._vt_term = False
+
+    # ------------------------------------------------------------------ term mix (include/mvfit.h:mvfit_set_term_mix)
+    def set_term_mix(self, scene=0.0, silhouette=0.0, vertex_targets=0.0, w_in=1.0, w_out=1.0, sigma=0.0):
+        """Make a weighted sum of the scene, silhouette and vertex-target terms the term of closure() and fit()
+        (include/mvfit.h:mvfit_set_term_mix): a stage with coll_loss_weight w > 0 adds w^2 * (scene * S_sc^2 + silhouette *
+        L_sil + vertex_targets * L_vt) to every problem.  At least two shares > 0, each with its data set in place
+        (set_scene_obstacles / set_silhouettes / set_vertex_targets); w_in, w_out, sigma are the silhouette term's."""
+        m = _lib.TermMix(C.sizeof(_lib.TermMix), float(scene), float(silhouette), float(w_in), float(w_out), float(sigma),
+                         float(vertex_targets))
+        rc = self._lib.mvfit_set_term_mix(self._ctx, C.byref(m))
+        if rc not in (0, -1, -3):                # (a failed allocation leaves no mix; a refusal keeps the one in place)
+            self._mix = None
+        self._check(rc)
+        self._mix = (float(scene), float(silhouette), float(vertex_targets))
+
+    def clear_term_mix(self):
+        """Switch the mix of set_term_mix off (the data sets stay)."""
+        self._check(self._lib.mvfit_set_term_mix(self._ctx, None))
+        self._mix = None
+
+    def term_mix_read(self):
+        """[B,3]: S_sc^2, L_sil, L_vt of the mix's last evaluation, unweighted (0 for a share of 0)."""
+        parts = torch.empty(self.B, 3, device=self.device)
+        self._check(self._lib.mvfit_term_mix_read(self._ctx, parts.data_ptr()))
+        return parts
+
+    def term_mix_cotangent(self, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt):
+        """The mix's cotangent kernel on the caller's buffers (include/mvfit.h:mvfit_term_mix_cotangent): (g [B,Nv,3], L_v [B]).
+        The buffers of a component with share 0 may be None."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        g = torch.empty(self.B, self.nv, 3, device=self.device)
+        L = torch.empty(self.B, device=self.device)
+        self._check(self._lib.mvfit_term_mix_cotangent(self._ctx, float(silhouette), ptr(g_sil), ptr(L_sil), float(vertex_targets),
+                                                       ptr(g_vt), ptr(L_vt), g.data_ptr(), L.data_ptr()))
+        return g, L
+
+    def term_mix_merge(self, scene, rec_scene, rec_verts):
+        """The mix's record kernel on the caller's records [B, TERM_RECORD_FLOATS] (include/mvfit.h:mvfit_term_mix_merge)."""
+        a, b = self._dev(rec_scene), self._dev(rec_verts)
+        if tuple(a.shape) != (self.B, _lib.TERM_RECORD_FLOATS) or a.shape != b.shape:
+            raise MvFitError('records must be [%d, %d]' % (self.B, _lib.TERM_RECORD_FLOATS))
+        out = torch.empty_like(a)
+        self._check(self._lib.mvfit_term_mix_merge(self._ctx, float(scene), a.data_ptr(), b.data_ptr(), out.data_ptr()))
+        return out
 
     def set_sdf(self, faces, num_faces=1, grid_size=128):
         """Configure the interpenetration term (include/mvfit.h:mvfit_set_sdf).  ``faces`` [F,3]; ``num_faces``
@@ -764,8 +816,9 @@ class MvFit:
     def sdf_term_read(self):
         """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
         (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set; so does the silhouette term
-        (set_silhouette_term) and the vertex-target term (set_vertex_target_term), whose S is the loss L_j itself."""
-        smp = None if (self._obstacles or self._sil_term or self._vt_term) else torch.empty(self.B, self.nv, 4, device=self.device)
+        (set_silhouette_term) and the vertex-target term (set_vertex_target_term), whose S is the loss L_j itself, and the
+        term mix (set_term_mix), whose S is the weighted sum of its parts."""
+        smp = None if (self._obstacles or self._sil_term or self._vt_term or self._mix) else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S

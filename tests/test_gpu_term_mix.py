@@ -1,0 +1,608 @@
+"""GPU: the term mix (mvfit_set_term_mix; term_mix.hip between the three terms' own kernels and vertex_backward.hip's gated
+pull-back) in closure() and in fit()'s chained rounds.
+
+The shapes are those of tests/test_gpu_vertex_target.py and tests/test_gpu_silhouette_term.py: the full body model, a 4-view
+ring scaled to 384 x 512, B = 34 problems (a second, ragged 32-problem chunk of the pull-back; 11 workgroups of the cotangent
+kernel per problem, the last one ragged), masks for bodies 0, 31, 32 and 33 only, K = 4 targets of which rows 1 and 3 have
+weight 0 and hold NaN, 17 scenes of two bodies.  Bodies 0 / 1 and 32 / 33 stand 15 cm apart (S_sc > 0), every other scene's
+first body 3 m away.  Problem 5 has every component zero; problem 1 has a scene part and nothing else.
+References: the same engine with one term on through that term's own setter, MvFit.silhouette_loss and
+MvFit.vertex_target_loss at the closure's vertices, and the NumPy restatement tests/term_mix_oracle.py.  Bounds: the project's
+own LOSS_RTOL / GRAD_TOL (tests/scene_sdf_cases.py) for sums of separately evaluated closures; chained rounds against the
+closure 1e-6 (tests/test_gpu_silhouette_term.py); everything else bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from mvsmplfitting_amd import _lib
+from mvsmplfitting_amd import synthetic as syn
+from mvsmplfitting_amd.engine import MvFitError, pack_params, stage_weights
+from tests import term_mix_oracle as tm
+from tests.gpu_helpers import make_engine
+from tests.helpers import body_model
+from tests.scene_sdf_cases import GRAD_TOL, LOSS_RTOL
+
+pytestmark = pytest.mark.gpu
+
+V, B = 4, 34
+SHARES = (0.5, 2.0, 0.25)                      # scene, silhouette, vertex targets
+SIZES = [2] * 17
+OFFSET = np.array([0.13, 0.02, 0.07], np.float32)
+KW = dict(grid_size=32, scale_factor=0.2, robustifier=0.05)
+SIL = dict(w_in=1.0, w_out=0.5, sigma=20.0)
+IMAGES = [(0, 0), (0, 1), (31, 2), (32, 0), (32, 1), (32, 2), (32, 3), (33, 3)]      # (body, view)
+WITH_IMAGES = (0, 31, 32, 33)
+VT_ZERO = (1, 5)
+ROWS3 = (32, 33, 5)                            # the fit's problems: a scene of two with every component, and problem 5
+SIZES3 = [2, 1]
+FIT_KW = dict(max_iter=6, maxiters=2)
+BETAS = np.array([3.0, -2.0, 1.5, -1.0, 2.5, 0.5, -3.0, 1.0, -0.5, 2.0], np.float32)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _stage(w, flags=0):
+    return dict(stage_weights(1536.0, flags=flags)[3], coll_loss_weight=float(w))
+
+
+def _cams():
+    R, t, f, c = syn.make_camera_ring(V, radius=4.0)
+    Wd, Hd = 512, 384
+    f = (f * np.float32(Wd / 2048.0)).astype(np.float32)
+    c = np.tile(np.array([Wd / 2.0, Hd / 2.0], np.float32), (V, 1))
+    return (R, t, f, c), Hd, Wd
+
+
+def _perturbed(x, seed):
+    rng = np.random.default_rng(seed)
+    y = x.copy()
+    y[:, 10:82] += rng.normal(0, 0.05, (x.shape[0], 72)).astype(np.float32)
+    y[:, 82:85] += rng.normal(0, 0.02, (x.shape[0], 3)).astype(np.float32)
+    return y
+
+
+def _k4(T2, a2):
+    n = T2.shape[0]
+    T4 = torch.full((n, 4) + tuple(T2.shape[2:]), float('nan'), device=T2.device)
+    T4[:, 0], T4[:, 2] = T2[:, 0], T2[:, 1]
+    a4 = np.zeros((n, 4), np.float32)
+    a4[:, 0], a4[:, 2] = a2[:, 0], a2[:, 1]
+    return T4, a4
+
+
+def _render(eng, x, images, H, W):
+    v, _ = eng.vertices(x)
+    prob, view = np.array([i[0] for i in images], np.int32), np.array([i[1] for i in images], np.int32)
+    _, fid = eng.render_overlay(v, None, np.zeros((len(images), H, W, 3), np.uint8), prob, view, face_id=True)
+    return (fid >= 0).to(torch.uint8)
+
+
+def _mask_set(world, rows):
+    """(masks, image_body, cams per image) of the images of ``rows``, the bodies renumbered by their place in rows."""
+    keep = [i for i, (b, _) in enumerate(IMAGES) if b in rows]
+    body = np.array([list(rows).index(IMAGES[i][0]) for i in keep], np.int32)
+    view = np.array([IMAGES[i][1] for i in keep])
+    return world['masks'][keep], body, tuple(a[view] for a in world['cams'])
+
+
+@pytest.fixture(scope='module')
+def world():
+    model = body_model()
+    vpw = syn.make_vposer_decoder()
+    eng = make_engine(model, vpw=vpw)
+    cams, H, W = _cams()
+    fr = syn.make_frames(B, seed0=5300, betas=BETAS)
+    fr['scale'][:] = 1.08
+    x_true = pack_params(B=B, **fr)
+    for a, b in ((0, 1), (32, 33)):
+        x_true[b, 82:85] = x_true[a, 82:85] + OFFSET
+    x_true[2:32:2, 82] += 3.0                                # every other scene: its first body 3 m away
+    eng.set_problems(cams, np.zeros((B, V, 17, 2), np.float32), np.zeros((B, V, 17), np.float32))
+    _, joints = eng.vertices(x_true)
+    gt, conf = syn.make_observations(_np(joints), cams, seed=3)
+    eng.set_problems(cams, gt, conf)
+    masks = _render(eng, x_true, IMAGES, H, W)
+    x = x_true.copy()
+    x[:, 0:10] = 0.0
+    x[:, 85] = 1.0
+    x[:, 82:85] += np.array([0.03, -0.02, 0.04], np.float32)
+    x[:, 86:118] = np.random.default_rng(2).normal(0, 0.3, (B, 32)).astype(np.float32)       # (the embedding, read with F_VPOSER only)
+    T2 = torch.stack([eng.vertices(_perturbed(x, 10))[0], eng.vertices(_perturbed(x, 11))[0]], dim=1)
+    a2 = np.random.default_rng(4).uniform(0.5, 1.5, (B, 2)).astype(np.float32)
+    a2[list(VT_ZERO)] = 0.0
+    a2[0, 0] = 0.0
+    T4, a4 = _k4(T2, a2)
+    w = dict(eng=eng, model=model, vpw=vpw, cams=cams, H=H, W=W, x=x, gt=gt, conf=conf, masks=masks, T=T4, a=a4)
+    eng.set_silhouettes(*_mask_set(w, range(B)))
+    eng.set_vertex_targets(T4, a4)
+    w['cache'] = {}
+    yield w
+    eng.close()
+
+
+def _closure(eng, x, w, flags):
+    o = eng.closure(x, _stage(w, flags), want_grad=True, want_verts=True)
+    return dict(loss=_np(o['loss']), grad=_np(o['grad']), verts=o['verts'])
+
+
+def _singles(world, flags):
+    """The closure at x without a term and with each single term on through its own setter (w = 1), once per flags."""
+    if flags in world['cache']:
+        return world['cache'][flags]
+    eng, x = world['eng'], world['x']
+    r = dict(none=_closure(eng, x, 0.0, flags))
+    v0 = r['none']['verts']
+    eng.set_scene_obstacles(v0, SIZES, **KW)
+    try:
+        r['scene'] = _closure(eng, x, 1.0, flags)
+        r['S_sc'] = _np(eng.sdf_term_read()[1])
+    finally:
+        eng.clear_scene_obstacles()
+    eng.set_silhouette_term(**SIL)
+    try:
+        r['sil'] = _closure(eng, x, 1.0, flags)
+    finally:
+        eng.clear_silhouette_term()
+    eng.set_vertex_target_term()
+    try:
+        r['vt'] = _closure(eng, x, 1.0, flags)
+    finally:
+        eng.clear_vertex_target_term()
+    world['cache'][flags] = r
+    return r
+
+
+def _mixed(world, flags, shares, w=1.0, eng=None, x=None, sizes=SIZES):
+    """The closure with the mix on (obstacles frozen at x's vertices), its parts and sums."""
+    eng, x = eng or world['eng'], world['x'] if x is None else x
+    v0, _ = eng.vertices(x, flags=flags)
+    eng.set_scene_obstacles(v0, sizes, **KW)
+    try:
+        eng.set_term_mix(scene=shares[0], silhouette=shares[1], vertex_targets=shares[2], **SIL)
+        r = _closure(eng, x, w, flags)
+        r['parts'] = _np(eng.term_mix_read())
+        smp, S = eng.sdf_term_read()
+        assert smp is None
+        r['sums'] = _np(S)
+    finally:
+        eng.clear_term_mix()
+        eng.clear_scene_obstacles()
+    return r
+
+
+# ------------------------------------------------------------------------------------------------ 1. additivity
+@pytest.mark.parametrize('flags', [0, _lib.F_VPOSER])
+@pytest.mark.parametrize('shares', [SHARES, (0.0, 2.0, 0.25), (0.5, 0.0, 0.25), (0.5, 2.0, 0.0)])
+def test_the_mix_is_the_weighted_sum_of_the_single_terms(world, flags, shares):
+    s = _singles(world, flags)
+    m = _mixed(world, flags, shares)
+    f64 = lambda a: a.astype(np.float64)
+    l0, g0 = f64(s['none']['loss']), f64(s['none']['grad'])
+    pen_ref = sum(lam * (f64(s[k]['loss']) - l0) for lam, k in zip(shares, ('scene', 'sil', 'vt')))
+    gp_ref = sum(lam * (f64(s[k]['grad']) - g0) for lam, k in zip(shares, ('scene', 'sil', 'vt')))
+    pen, gp = f64(m['loss']) - l0, f64(m['grad']) - g0
+    e_l = np.abs(pen - pen_ref) / f64(m['loss'])
+    gmax = np.abs(gp_ref).max(axis=1)
+    live = gmax > 0
+    e_g = np.abs(gp - gp_ref).max(axis=1)[live] / gmax[live]
+    print('flags %d shares %s: penalty error / loss worst %.2e (problem %d), gradient error / max worst %.2e (problem %d); '
+          'penalties of 0, 1, 31, 32, 33: %s' % (flags, shares, e_l.max(), e_l.argmax(), e_g.max(), np.flatnonzero(live)[e_g.argmax()],
+                                                pen[[0, 1, 31, 32, 33]]))
+    assert live[[0, 31, 32, 33]].all() and pen_ref[32] > 0
+    if shares[0] > 0:
+        assert (s['S_sc'][[0, 1, 32, 33]] > 0).all() and not s['S_sc'][2:32].any()
+    assert (e_l <= LOSS_RTOL).all()
+    assert (e_g <= GRAD_TOL).all()
+    assert np.array_equal(gp[~live], np.zeros_like(gp[~live]))
+
+
+# ------------------------------------------------------------------------------------------------ 2. components
+def test_parts_and_sums_are_the_terms_own_numbers(world):
+    eng = world['eng']
+    s = _singles(world, 0)
+    m = _mixed(world, 0, SHARES)
+    L_sil = _np(eng.silhouette_loss(m['verts'], need_grad=False, **SIL)[0])
+    L_vt = _np(eng.vertex_target_loss(m['verts'], need_grad=False)[0])
+    assert (L_sil[list(WITH_IMAGES)] > 0).all() and (L_vt[[0, 31, 32, 33]] > 0).all()
+    assert np.array_equal(_bits(m['parts'][:, 1]), _bits(L_sil))
+    assert np.array_equal(_bits(m['parts'][:, 2]), _bits(L_vt))
+    assert np.array_equal(_bits(m['parts'][:, 0]), _bits(tm.scene_part(s['S_sc'])))
+    assert np.array_equal(_bits(m['sums']), _bits(tm.mix_parts_sum(SHARES, m['parts'])))
+    assert not m['parts'][5].any() and m['sums'][5] == 0
+    # a share of 0 is reported as 0, with or without a record merge behind the cotangent kernel
+    m2 = _mixed(world, 0, (0.0, 2.0, 0.25))
+    assert not m2['parts'][:, 0].any() and np.array_equal(m2['parts'][:, 1:], m['parts'][:, 1:])
+    assert np.array_equal(_bits(m2['sums']), _bits(tm.mix_parts_sum((0.0, 2.0, 0.25), m2['parts'])))
+    m3 = _mixed(world, 0, (0.5, 0.0, 0.25))
+    assert not m3['parts'][:, 1].any() and np.array_equal(m3['parts'][:, [0, 2]], m['parts'][:, [0, 2]])
+
+
+# ------------------------------------------------------------------------------------------------ 3. kernel arithmetic
+def test_the_cotangent_kernel_against_the_oracle(world):
+    eng, verts = world['eng'], _singles(world, 0)['none']['verts']
+    Ls, gs = eng.silhouette_loss(verts, **SIL)
+    Lv, gv = eng.vertex_target_loss(verts)
+    for lam_s, lam_v in ((2.0, 0.25), (0.3, 0.0), (0.0, 1.7), (1.0, 1.0)):
+        nan_g, nan_L = torch.full_like(gs, float('nan')), torch.full_like(Ls, float('nan'))
+        g, L = eng.term_mix_cotangent(lam_s, gs if lam_s else nan_g, Ls if lam_s else nan_L, lam_v, gv if lam_v else nan_g,
+                                      Lv if lam_v else nan_L)
+        g_ref, L_ref = tm.mix_cotangent(lam_s, _np(gs), _np(Ls), lam_v, _np(gv), _np(Lv))
+        assert np.isfinite(_np(g)).all()
+        assert np.array_equal(_bits(_np(g)), _bits(g_ref)), (lam_s, lam_v)
+        assert np.array_equal(_bits(_np(L)), _bits(L_ref)), (lam_s, lam_v)
+    g, L = eng.term_mix_cotangent(0.5, gs, Ls, 0.0, None, None)                # a skipped component's buffers may be absent
+    assert np.array_equal(_np(g), np.float32(0.5) * _np(gs))
+
+
+def test_the_record_kernel_against_the_oracle(world):
+    eng = world['eng']
+    rng = np.random.default_rng(9)
+    R = _lib.TERM_RECORD_FLOATS
+    sc = rng.normal(0, 1, (B, R)).astype(np.float32)
+    rv = rng.normal(0, 1, (B, R)).astype(np.float32)
+    sc[:, 0], rv[:, 0] = np.abs(sc[:, 0]) * 30, np.abs(rv[:, 0]) * 5
+    rv[1] = 0.0                                              # the vertex terms pay nothing: the scene record passes through
+    sc[5], rv[5] = 0.0, 0.0                                  # nothing at all
+    sc[7, 0], rv[7, 0] = 1e-20, 0.0                          # Q below FLT_MIN
+    sc[9, 0] = 0.0                                           # only the vertex terms
+    for lam in (1.0, 0.5, 3.0):
+        out = _np(eng.term_mix_merge(lam, sc, rv))
+        ref = tm.mix_record(lam, sc, rv)
+        assert np.array_equal(_bits(out), _bits(ref)), (lam, np.count_nonzero(_bits(out) != _bits(ref)))
+        assert not out[5].any() and not out[7].any()
+    out = _np(eng.term_mix_merge(1.0, sc, rv))
+    assert np.array_equal(_bits(out[1]), _bits(sc[1])) and np.array_equal(_bits(out[9]), _bits(rv[9]))
+
+
+def test_pass_through_and_the_problem_without_any_component(world):
+    s = _singles(world, 0)
+    m = _mixed(world, 0, (1.0, 0.0, 0.5))
+    # problem 1: S_sc > 0, no image, all target weights zero - the single scene term's bits
+    assert s['S_sc'][1] > 0 and m['parts'][1, 2] == 0
+    assert np.array_equal(_bits(m['loss'][1]), _bits(s['scene']['loss'][1]))
+    assert np.array_equal(_bits(m['grad'][1]), _bits(s['scene']['grad'][1]))
+    assert not np.array_equal(m['loss'][32], s['scene']['loss'][32])
+    for shares in (SHARES, (0.0, 2.0, 0.25)):
+        m = _mixed(world, 0, shares)
+        assert np.array_equal(_bits(m['loss'][5]), _bits(s['none']['loss'][5]))
+        assert np.array_equal(_bits(m['grad'][5]), _bits(s['none']['grad'][5]))
+        assert not np.array_equal(m['loss'][32], s['none']['loss'][32])
+
+
+# ------------------------------------------------------------------------------------------------ 4. independence
+def _sub_engine(world, rows, **options):
+    """A fresh engine with the problems ``rows``, their masks and their targets."""
+    rows = list(rows)
+    eng = make_engine(world['model'], vpw=world['vpw'], **options)
+    eng.set_problems(world['cams'], world['gt'][rows], world['conf'][rows])
+    eng.set_silhouettes(*_mask_set(world, rows))
+    eng.set_vertex_targets(world['T'][rows], world['a'][rows])
+    return eng, world['x'][rows].copy()
+
+
+def test_a_problems_numbers_do_not_depend_on_the_batch_or_the_run(world):
+    m = _mixed(world, 0, SHARES)
+    again = _mixed(world, 0, SHARES)
+    for k in ('loss', 'grad', 'parts', 'sums'):
+        assert np.array_equal(_bits(m[k]), _bits(again[k])), k
+    two, x2 = _sub_engine(world, (32, 33))
+    try:
+        m2 = _mixed(world, 0, SHARES, eng=two, x=x2, sizes=[2])
+    finally:
+        two.close()
+    for k in ('loss', 'grad', 'parts', 'sums'):
+        assert np.array_equal(_bits(m2[k]), _bits(m[k][32:34])), k
+    # without the scene term a problem stands alone
+    sv = _mixed(world, 0, (0.0, 2.0, 0.25))
+    one, x1 = _sub_engine(world, (32,))
+    try:
+        m1 = _mixed(world, 0, (0.0, 2.0, 0.25), eng=one, x=x1, sizes=[1])
+    finally:
+        one.close()
+    for k in ('loss', 'grad', 'parts', 'sums'):
+        assert np.array_equal(_bits(m1[k][0]), _bits(sv[k][32])), k
+
+
+def test_cotangent_buffers_at_addresses_4_mod_8(world):
+    eng, verts = world['eng'], _singles(world, 0)['none']['verts']
+    Ls, gs = eng.silhouette_loss(verts, **SIL)
+    Lv, gv = eng.vertex_target_loss(verts)
+    g, L = eng.term_mix_cotangent(2.0, gs, Ls, 0.25, gv, Lv)
+    n = gs.numel()
+
+    def off(t=None):
+        flat = torch.empty(n + 1, device=eng.device)
+        if t is not None:
+            flat[1:] = t.reshape(-1)
+        o = flat[1:].view(B, eng.nv, 3)
+        assert o.data_ptr() % 8 == 4 and o.is_contiguous()
+        return o
+
+    for src_off, dst_off in ((True, False), (False, True), (True, True)):
+        a, b = (off(gs), off(gv)) if src_off else (gs, gv)
+        out = off() if dst_off else torch.empty_like(gs)
+        L_out = torch.empty(B, device=eng.device)
+        eng._check(eng._lib.mvfit_term_mix_cotangent(eng._ctx, 2.0, a.data_ptr(), Ls.data_ptr(), 0.25, b.data_ptr(), Lv.data_ptr(),
+                                                     out.data_ptr(), L_out.data_ptr()))
+        assert torch.equal(out, g) and torch.equal(L_out, L), (src_off, dst_off)
+
+
+def test_a_share_of_zero_is_never_read(world):
+    eng = world['eng']
+    ref = _mixed(world, 0, (0.5, 2.0, 0.0))
+    eng.set_vertex_targets(torch.full_like(world['T'], float('nan')), np.ones((B, 4), np.float32))
+    try:
+        got = _mixed(world, 0, (0.5, 2.0, 0.0))
+    finally:
+        eng.set_vertex_targets(world['T'], world['a'])
+    for k in ('loss', 'grad', 'parts', 'sums'):
+        assert np.array_equal(_bits(got[k]), _bits(ref[k])), k
+    assert np.isfinite(got['grad']).all()
+
+
+# ------------------------------------------------------------------------------------------------ 5. in the fit
+def _three(world, shares=SHARES, seed=None, **options):
+    """A fresh engine with the fit's three problems, obstacles frozen at x (or at x perturbed by ``seed``) and the mix on."""
+    eng, x = _sub_engine(world, ROWS3, **options)
+    _freeze(eng, x, seed)
+    if shares is not None:
+        eng.set_term_mix(scene=shares[0], silhouette=shares[1], vertex_targets=shares[2], **SIL)
+    return eng, x
+
+
+def _freeze(eng, x, seed=None):
+    eng.set_scene_obstacles(eng.vertices(x if seed is None else _perturbed(x, seed))[0], SIZES3, **KW)
+
+
+def _w3(eng, x):
+    """w with w^2 = data term / the mix's sum of problem 0: neither drowns the other."""
+    data = float(eng.closure(x, _stage(0.0), want_grad=False)['loss'][0])
+    eng.closure(x, _stage(1.0), want_grad=False)
+    return float(np.sqrt(data / float(eng.sdf_term_read()[1][0])))
+
+
+def _fit(eng, x, stages):
+    xf, st = eng.fit(x, stages, **FIT_KW)
+    return xf.cpu(), st['final_loss'].cpu(), st['n_closure'].cpu()
+
+
+def _same(a, b):
+    return all(torch.equal(p, q) for p, q in zip(a, b))
+
+
+def test_chained_rounds_evaluate_the_closures_function(world):
+    eng, x = _three(world)
+    try:
+        w = _w3(eng, x)
+        tr = eng.fit_trace(12)
+        xf, st = eng.fit(x, [_stage(w)], **FIT_KW)
+        tr = _np(tr).astype(np.float64)
+        eng.fit_trace(0)
+        assert st['passes']['run'] == 0                       # chained rounds from the first stage on
+        ncl = _np(st['n_closure'])
+        checked = 0
+        for k in range(12):
+            rows = [b for b in range(3) if k < ncl[b] and np.isfinite(tr[b, k]).all()]
+            if not rows:
+                continue
+            xk = x.copy()
+            xk[rows] = tr[rows, k, :118].astype(np.float32)
+            L = _np(eng.closure(xk, _stage(w), want_grad=False)['loss']).astype(np.float64)
+            for b in rows:
+                print('closure %d problem %d: round %.9g closure %.9g' % (k, b, tr[b, k, 118], L[b]))
+                assert abs(L[b] - tr[b, k, 118]) <= 1e-6 * abs(L[b]), (k, b)
+                checked += 1
+        assert checked >= 9
+        # two stages, the first without the term: a single-launch lead phase, then chained rounds
+        xf2, st2 = eng.fit(x, [_stage(0.0), _stage(w)], **FIT_KW)
+        print('two-stage fit: passes %s, closures %s' % (st2['passes'], _np(st2['n_closure'])))
+        assert st2['passes']['run'] > 0
+        assert st2['passes']['missed'] == 0 and st2['passes']['timed_out'] == 0
+        assert torch.isfinite(xf2).all() and torch.isfinite(st2['final_loss']).all()
+        # the problem without any component against the same stages with no term, through the same kernels
+        eng.set_options(round_mode=1)
+        a = _fit(eng, x, [_stage(0.0), _stage(w)])
+        eng.clear_term_mix()
+        eng.clear_scene_obstacles()
+        b = _fit(eng, x, [_stage(0.0), _stage(0.0)])
+        assert _same([t[2] for t in a], [t[2] for t in b])
+        assert not torch.equal(a[0][0], b[0][0])
+    finally:
+        eng.close()
+
+
+def test_the_round_graph_follows_the_frozen_data_and_the_shares(world):
+    eng, x = _three(world)
+    try:
+        w = _w3(eng, x)
+        first = _fit(eng, x, [_stage(w)])
+        # a re-freeze with unchanged shapes: other obstacles, other targets and a re-set mask set in the same buffers
+        _freeze(eng, x, 30)
+        T = torch.roll(world['T'][list(ROWS3)], 1, dims=1)
+        a = np.roll(world['a'][list(ROWS3)], 1, axis=1) * np.float32(1.5)
+        eng.set_vertex_targets(T, a)
+        eng.set_silhouettes(*_mask_set(world, ROWS3))
+        second = _fit(eng, x, [_stage(w)])
+        # another share
+        other = (0.25, 1.0, 0.75)
+        eng.set_term_mix(scene=other[0], silhouette=other[1], vertex_targets=other[2], **SIL)
+        third = _fit(eng, x, [_stage(w)])
+        # after the mix: each single term as on an engine that never saw it
+        eng.clear_term_mix()
+        singles = [_fit(eng, x, [_stage(w)])]                                  # the obstacles alone are the scene term
+        eng.clear_scene_obstacles()
+        eng.set_silhouette_term(**SIL)
+        singles.append(_fit(eng, x, [_stage(w)]))
+        eng.clear_silhouette_term()
+        eng.set_vertex_target_term()
+        singles.append(_fit(eng, x, [_stage(w)]))
+    finally:
+        eng.close()
+    assert not _same(first, second) and not _same(second, third)
+    for shares, got in ((SHARES, second), (other, third)):
+        fresh, xs = _three(world, shares=None)
+        try:
+            _freeze(fresh, xs, 30)
+            fresh.set_vertex_targets(T, a)
+            fresh.set_term_mix(scene=shares[0], silhouette=shares[1], vertex_targets=shares[2], **SIL)
+            assert _same(got, _fit(fresh, xs, [_stage(w)])), shares
+        finally:
+            fresh.close()
+    fresh, xs = _three(world, shares=None)
+    try:
+        _freeze(fresh, xs, 30)
+        fresh.set_vertex_targets(T, a)
+        ref = [_fit(fresh, xs, [_stage(w)])]
+        fresh.clear_scene_obstacles()
+        fresh.set_silhouette_term(**SIL)
+        ref.append(_fit(fresh, xs, [_stage(w)]))
+        fresh.clear_silhouette_term()
+        fresh.set_vertex_target_term()
+        ref.append(_fit(fresh, xs, [_stage(w)]))
+    finally:
+        fresh.close()
+    for name, got, want in zip(('scene', 'silhouette', 'vertex-target'), singles, ref):
+        assert _same(got, want), name
+
+
+# ------------------------------------------------------------------------------------------------ 6. the contract
+def _set(eng, **kw):
+    eng.set_term_mix(**dict(SIL, **kw))
+
+
+def test_contract(world):
+    eng, x, cams = world['eng'], world['x'], world['cams']
+    faces = world['model']['faces']
+    verts = _singles(world, 0)['none']['verts']
+    parts = torch.empty(B, 3, device=eng.device)
+    try:
+        # the shares: at least two > 0, finite, >= 0; the silhouette scalars as in the term's own setter; the struct's size
+        for kw in (dict(), dict(silhouette=1.0), dict(scene=2.0), dict(silhouette=1.0, vertex_targets=-1.0),
+                   dict(silhouette=float('nan'), vertex_targets=1.0), dict(silhouette=1.0, vertex_targets=float('inf')),
+                   dict(silhouette=1.0, vertex_targets=1.0, w_in=-1.0), dict(silhouette=1.0, vertex_targets=1.0, sigma=float('nan'))):
+            with pytest.raises(MvFitError, match='error -1: mvfit_set_term_mix'):
+                _set(eng, **kw)
+        short = _lib.TermMix(C.sizeof(_lib.TermMix) - 4, 0.0, 1.0, 1.0, 1.0, 0.0, 1.0)
+        assert eng._lib.mvfit_set_term_mix(eng._ctx, C.byref(short)) == -1
+        # off: reading refuses, a weight > 0 has no term
+        with pytest.raises(MvFitError, match='error -3: mvfit_term_mix_read'):
+            eng.term_mix_read()
+        assert eng._lib.mvfit_term_mix_read(eng._ctx, None) == -1
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.closure(x, _stage(1.0))
+        # a share > 0 without its data set
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_term_mix: scene > 0 needs obstacles'):
+            _set(eng, scene=1.0, silhouette=1.0)
+        eng.clear_vertex_targets()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_term_mix: vertex_targets > 0 needs a target set'):
+            _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.set_vertex_targets(world['T'], world['a'])
+        eng.clear_silhouettes()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_term_mix: silhouette > 0 needs a mask set'):
+            _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.set_silhouettes(*_mask_set(world, range(B)))
+        # a single term's own setter or mvfit_set_sdf's term in the slot
+        eng.set_silhouette_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_term_mix: the silhouette term'):
+            _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.clear_silhouette_term()
+        eng.set_vertex_target_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_term_mix: the vertex-target term'):
+            _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.clear_vertex_target_term()
+        eng.set_sdf(faces, num_faces=1, grid_size=32)
+        with pytest.raises(MvFitError, match="error -3: mvfit_set_term_mix: mvfit_set_sdf's term"):
+            _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.set_sdf(None)
+        # on: the single setters and mvfit_set_sdf refuse, samples are unsupported, the data sets may be replaced
+        _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.closure(x, _stage(1.0))
+        eng._check(eng._lib.mvfit_term_mix_read(eng._ctx, parts.data_ptr()))
+        with pytest.raises(MvFitError, match='error -4'):
+            eng._check(eng._lib.mvfit_sdf_term_read(eng._ctx, torch.empty(B, eng.nv, 4, device=eng.device).data_ptr(), None))
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_silhouette_term'):
+            eng.set_silhouette_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_vertex_target_term'):
+            eng.set_vertex_target_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_sdf'):
+            eng.set_sdf(faces, num_faces=1, grid_size=32)
+        eng.set_vertex_targets(world['T'], world['a'])
+        eng.set_silhouettes(*_mask_set(world, range(B)))
+        eng.set_scene_obstacles(verts, SIZES, **KW)           # obstacles alone do not make the scene term run
+        a = eng.closure(x, _stage(1.0))
+        assert not _np(eng.term_mix_read())[:, 0].any()
+        eng.clear_scene_obstacles()                           # ... and removing them leaves a mix that does not use them on
+        b = eng.closure(x, _stage(1.0))
+        assert torch.equal(a['loss'], b['loss']) and torch.equal(a['grad'], b['grad'])
+        # removing a data set the mix uses switches it off
+        eng.clear_vertex_targets()
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.closure(x, _stage(1.0))
+        with pytest.raises(MvFitError, match='error -3: mvfit_term_mix_read'):
+            eng.term_mix_read()
+        eng.set_vertex_targets(world['T'], world['a'])
+        _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.clear_silhouettes()
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.closure(x, _stage(1.0))
+        eng.set_silhouettes(*_mask_set(world, range(B)))
+        eng.set_scene_obstacles(verts, SIZES, **KW)
+        _set(eng, scene=1.0, vertex_targets=1.0)
+        eng.closure(x, _stage(1.0))
+        eng.clear_scene_obstacles()
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.closure(x, _stage(1.0))
+        # mix off: the single setters' own refusals are what they were
+        eng.set_scene_obstacles(verts, SIZES, **KW)
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_silhouette_term'):
+            eng.set_silhouette_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_vertex_target_term'):
+            eng.set_vertex_target_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_sdf'):
+            eng.set_sdf(faces, num_faces=1, grid_size=32)
+        eng.clear_scene_obstacles()
+        eng.set_silhouette_term()
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_scene_obstacles'):
+            eng.set_scene_obstacles(verts, SIZES, **KW)
+        with pytest.raises(MvFitError, match='error -3: mvfit_set_vertex_target_term'):
+            eng.set_vertex_target_term()
+        eng.clear_silhouette_term()
+        # another B switches the mix off
+        _set(eng, silhouette=1.0, vertex_targets=1.0)
+        eng.set_problems(cams, world['gt'][:2], world['conf'][:2])
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.closure(x[:2], _stage(1.0))
+        with pytest.raises(MvFitError, match='error -3'):
+            eng.fit(x[:2], [_stage(1.0)])
+        with pytest.raises(MvFitError, match='error -3: mvfit_term_mix_read'):
+            eng.term_mix_read()
+        # the two op entries
+        with pytest.raises(MvFitError, match='error -1: mvfit_term_mix_cotangent'):
+            eng.term_mix_cotangent(0.0, None, None, 0.0, None, None)
+        with pytest.raises(MvFitError, match='error -1: mvfit_term_mix_cotangent'):
+            eng.term_mix_cotangent(1.0, None, None, 0.0, None, None)
+        with pytest.raises(MvFitError, match='error -1: mvfit_term_mix_merge'):
+            eng.term_mix_merge(0.0, np.zeros((2, _lib.TERM_RECORD_FLOATS), np.float32), np.zeros((2, _lib.TERM_RECORD_FLOATS), np.float32))
+        bare = make_engine(world['model'])
+        try:
+            with pytest.raises(MvFitError, match='error -3'):
+                _set(bare, silhouette=1.0, vertex_targets=1.0)
+        finally:
+            bare.close()
+    finally:
+        eng.set_sdf(None)
+        eng.clear_term_mix()
+        eng.clear_scene_obstacles()
+        eng.clear_silhouette_term()
+        eng.set_problems(cams, world['gt'], world['conf'])
+        eng.set_silhouettes(*_mask_set(world, range(B)))
+        eng.set_vertex_targets(world['T'], world['a'])
+        world['cache'].clear()
