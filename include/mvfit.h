@@ -174,8 +174,9 @@ typedef struct mvfit_options {
     int32_t closure_vposer_helpers;  /* 1: mvfit_closure (MVFIT_F_VPOSER, no SDF term, B <= 160) decodes on helper workgroups
                                       * of its own launch - the decoder arithmetic of the fits, for parity tests (0) */
     int32_t pass_kernel;             /* per-round launch kernels at more than 32 problems: 0 automatic (two-role pipeline; dense
-                                      * skinning rows: the lock-step chunk loop), 1 one workgroup per (tile, chunk); 2 = 0 (the
-                                      * lock-step loop for <= 4 weights per vertex was dropped in round 6) */
+                                      * skinning rows: the lock-step chunk loop; <= 4 weights per vertex and an odd num_verts: as
+                                      * 1), 1 one workgroup per (tile, chunk); 2 = 0 (the lock-step loop for <= 4 weights per
+                                      * vertex was dropped in round 6).  The vertices do not depend on it, bit for bit */
     int32_t sdf_service;             /* 1 (default): in a two-phase fit (sdf_two_phase) the stages WITH the SDF term also run in the
                                       * single-launch optimiser kernel, which asks for the term every closure round - gate ->
                                       * vertex pass -> term kernels per round on the pass stream, the pull-back answers through

@@ -139,4 +139,13 @@ PersistentVariant plan_persistent_variant(bool sdf_service, bool queue, bool hel
     return lean ? PV_LEAN : PV_PLAIN;
 }
 
+PassLaunch plan_pass_launch(bool split_basis, bool sparse_skinning, bool nv_even, int chunks, int pass_kernel) {
+    if (!split_basis) return {PASS_EXACT, sparse_skinning, chunks};
+    // more than one 32-problem chunk: one workgroup per vertex tile walks ALL chunks with the tile's basis held in registers
+    if (chunks == 1 || pass_kernel == 1) return {PASS_SPLIT, sparse_skinning, chunks};
+    if (!sparse_skinning) return {PASS_SPLIT_LOOP, false, 1};
+    if (nv_even) return {PASS_PIPE, true, 1};
+    return {PASS_SPLIT, true, chunks};
+}
+
 }  // namespace mvfit

@@ -103,4 +103,22 @@ enum PersistentVariant {
 // has an instantiation for them
 PersistentVariant plan_persistent_variant(bool sdf_service, bool queue, bool helpers, bool reuse_outer, bool lean);
 
+// The kernels of a per-round vertex pass (vertex_pass.hip: launch_vertex_pass switches on the result)
+enum PassKernel {
+    PASS_EXACT = 0,        // lbs_vertex_pass_kernel<sparse>             exact fp32 MFMA chain, one workgroup per (tile, chunk)
+    PASS_SPLIT,            // lbs_vertex_pass_split_kernel<sparse>       split-fp16, one workgroup per (tile, chunk)
+    PASS_SPLIT_LOOP,       // lbs_vertex_pass_split_loop_kernel<false>   split-fp16, one workgroup per tile walks the chunks in lock-step
+    PASS_PIPE,             // lbs_vertex_pass_pipe_kernel                split-fp16, the same walk as a two-role pipeline
+    PASS_KERNEL_COUNT
+};
+struct PassLaunch {
+    int kernel;            // PassKernel
+    bool sparse;           // the 4-pair skinning blend (the SPARSE_W instantiation; the pipeline has no other)
+    int grid_y;            // workgroups per vertex tile: the chunks, or 1 for the kernels that walk them
+};
+// split_basis: the model has the split-fp16 basis (full or half width); chunks = ceil(B / 32) - first chunk of the launch;
+// pass_kernel: mvfit_options::pass_kernel (1: one workgroup per (tile, chunk) at any number of chunks; 2 = 0).
+// The pipeline stores vertex pairs: an odd vertex count with sparse skinning rows takes one workgroup per (tile, chunk).
+PassLaunch plan_pass_launch(bool split_basis, bool sparse_skinning, bool nv_even, int chunks, int pass_kernel);
+
 }  // namespace mvfit

@@ -28,6 +28,7 @@
 #include <hip/hip_ext.h>
 #include "mvfit_device.h"
 #include "launchers.h"
+#include "fit_plan.h"
 
 namespace mvfit {
 
@@ -117,6 +118,7 @@ __device__ __forceinline__ bool pass_chunk_live(const DevPose& P, int b0, int B,
 // ---------------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef f32x2 f32x2_a4 __attribute__((aligned(4)));      // a pair of floats at any float address
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void vp_blend_zero(float (&tr)[3][2][4]) {
@@ -221,8 +223,13 @@ __device__ __forceinline__ void vp_apply(const float* part, const float (&tr)[3]
     }
 }
 
-// coalesced store of x + transl: 32 rows of 96 floats (8-byte aligned: 12 * 6890 % 8 == 0); nvalid = floats of the
-// tile row that exist (last tile); store_nt: non-temporal (asynchronous fit, see the split kernel)
+// coalesced store of x + transl: 32 rows of 96 floats; nvalid = floats of the tile row that exist (last tile); store_nt:
+// non-temporal (asynchronous fit, see the split kernel).  Row b0 + b of the output starts at float 3 nv (b0 + b) and a tile
+// at an even float of its row: the pairs are 8-byte aligned for an even vertex count (12 * 6890 % 8 == 0) and, with an odd
+// count, in the even rows only - in its odd rows they start at 4 mod 8.  So a pair is stored through f32x2_a4, which promises
+// the 4 bytes every row has: one global_store_dwordx2 either way (gfx9 under HSA takes multi-dword global accesses at any
+// dword address - the compiler itself fuses two adjacent 4-byte stores into this instruction), the code of an even count
+// unchanged.  (A float2 store here told the compiler 8 bytes: undefined for an odd count.)
 __device__ __forceinline__ void vp_store_rows(float* __restrict__ verts, const float* out_l, const float* tau, int nv, int vbase,
                                               int nvalid, int b0, int B, int tid, bool store_nt) {
 #pragma unroll
@@ -236,8 +243,8 @@ __device__ __forceinline__ void vp_store_rows(float* __restrict__ verts, const f
             o.x += tau[b * 4 + k0];
             o.y += tau[b * 4 + k1];
             if (2 * q + 1 < nvalid) {
-                if (store_nt) __builtin_nontemporal_store(__builtin_bit_cast(f32x2, o), reinterpret_cast<f32x2*>(dst));
-                else *reinterpret_cast<float2*>(dst) = o;
+                if (store_nt) __builtin_nontemporal_store(__builtin_bit_cast(f32x2, o), reinterpret_cast<f32x2_a4*>(dst));
+                else *reinterpret_cast<f32x2_a4*>(dst) = __builtin_bit_cast(f32x2, o);
             } else if (2 * q < nvalid) dst[0] = o.x;
         }
     }
@@ -1953,33 +1960,34 @@ static void vp_launch(K kernel, dim3 grid, size_t lds, hipStream_t stream, hipEv
     else hipLaunchKernelGGL(kernel, grid, dim3(VP_NT), lds, stream, M, P, B, verts);
 }
 
-// pass_kernel (mvfit_options): kernel choice at more than 32 problems: 0 automatic, 1 one workgroup per (tile, chunk),
-// 2 lock-step chunk loop
+// Which kernel serves chunks [P.chunk0, ceil(B / 32)) is plan_pass_launch's decision (fit_plan.cpp; the table: DESIGN.md §4.4):
+// the exact-fp32 chain without the split-fp16 basis; with it one workgroup per (tile, chunk) for a single chunk or
+// pass_kernel 1, else one workgroup per vertex tile that walks ALL chunks with the tile's basis held in registers - the
+// two-role pipeline for <= 4 weights per vertex and an even vertex count, the lock-step loop for dense skinning rows.
+// pass_kernel 2 is 0: the lock-step loop's <= 4-weights instantiation, which it used to select, is gone (round 6), and an odd
+// vertex count with <= 4 weights takes one workgroup per (tile, chunk).
 hipError_t launch_vertex_pass(const DevModel& M, const DevPose& P, int B, float* verts, int pass_kernel,
                               hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    dim3 grid(M.ntiles, (B + 31) / 32 - P.chunk0);       // chunks [P.chunk0, ceil(B / 32))
-    if (M.bs_h2) {        // split-fp16 contraction (default); MVFIT_CONTRACTION_EXACT_FP32 keeps the fp32 MFMA chain
-        // more than one 32-problem chunk: one workgroup per vertex tile walks ALL chunks with the tile's basis held in
-        // registers - the basis is read once per launch whatever the number of problems (pass_kernel 1: one
-        // workgroup per (tile, chunk) as for a single chunk)
-        if (grid.y == 1 || pass_kernel == 1) {
-            if (M.wsp_w) vp_launch(lbs_vertex_pass_split_kernel<true>, grid, vertex_pass_split_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-            else vp_launch(lbs_vertex_pass_split_kernel<false>, grid, vertex_pass_split_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-        } else {
-            const dim3 g1(M.ntiles, 1);
-            // models with <= 4 weights per vertex and an even vertex count: the two-role pipeline (pass_kernel 2 keeps
-            // the lock-step chunk loop, which also serves dense skinning rows)
-            // (round 6: the lock-step loop's <= 4-weights instantiation is gone - pass_kernel 2 was its only selector; an odd
-            // vertex count with <= 4 weights takes one workgroup per (tile, chunk))
-            if (M.wsp_w && (M.nv & 1) == 0)
-                vp_launch(lbs_vertex_pass_pipe_kernel, g1, vertex_pass_pipe_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-            else if (M.wsp_w) vp_launch(lbs_vertex_pass_split_kernel<true>, grid, vertex_pass_split_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-            else vp_launch(lbs_vertex_pass_split_loop_kernel<false>, g1, vertex_pass_split_loop_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-        }
-        return hipGetLastError();
+    const PassLaunch L = plan_pass_launch(M.bs_h2 != nullptr, M.wsp_w != nullptr, (M.nv & 1) == 0, (B + 31) / 32 - P.chunk0, pass_kernel);
+    const dim3 grid(M.ntiles, L.grid_y);
+    switch (L.kernel) {
+    case PASS_EXACT:
+        if (L.sparse) vp_launch(lbs_vertex_pass_kernel<true>, grid, vertex_pass_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        else vp_launch(lbs_vertex_pass_kernel<false>, grid, vertex_pass_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        break;
+    case PASS_SPLIT:
+        if (L.sparse) vp_launch(lbs_vertex_pass_split_kernel<true>, grid, vertex_pass_split_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        else vp_launch(lbs_vertex_pass_split_kernel<false>, grid, vertex_pass_split_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        break;
+    case PASS_SPLIT_LOOP:
+        vp_launch(lbs_vertex_pass_split_loop_kernel<false>, grid, vertex_pass_split_loop_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        break;
+    case PASS_PIPE:
+        vp_launch(lbs_vertex_pass_pipe_kernel, grid, vertex_pass_pipe_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
+        break;
+    default:
+        return hipErrorInvalidValue;
     }
-    if (M.wsp_w) vp_launch(lbs_vertex_pass_kernel<true>, grid, vertex_pass_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
-    else vp_launch(lbs_vertex_pass_kernel<false>, grid, vertex_pass_lds_bytes(), stream, ev_start, ev_stop, M, P, B, verts);
     return hipGetLastError();
 }
 

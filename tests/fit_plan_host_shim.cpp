@@ -47,6 +47,13 @@ extern "C" int fit_plan_persistent_variant(int sdf_service, int queue, int helpe
 }
 extern "C" int fit_plan_persistent_variant_count() { return PV_COUNT; }
 
+// the kernel of a per-round vertex pass: out3 = kernel (PassKernel), sparse, grid_y
+extern "C" void fit_plan_pass_launch(int split_basis, int sparse_skinning, int nv_even, int chunks, int pass_kernel, int32_t* out3) {
+    const PassLaunch L = plan_pass_launch(split_basis != 0, sparse_skinning != 0, nv_even != 0, chunks, pass_kernel);
+    out3[0] = L.kernel; out3[1] = L.sparse; out3[2] = L.grid_y;
+}
+extern "C" int fit_plan_pass_kernel_count() { return PASS_KERNEL_COUNT; }
+
 // kAsyncMaxB, kResidentMaxB, kPassWords, kVpsSets, kVpsMaxSparse, kVpsMaxAsync, VPS_PMAX, VPS_MAX_SETS, VPS_SLICES, MVFIT_MAX_STAGES
 extern "C" void fit_plan_constants(int32_t* out10) {
     const int v[10] = {kAsyncMaxB, kResidentMaxB, kPassWords, kVpsSets, kVpsMaxSparse, kVpsMaxAsync, VPS_PMAX, VPS_MAX_SETS, VPS_SLICES,

@@ -42,6 +42,8 @@ def shim():
     lib.fit_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int]
     lib.fit_plan_nsets.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.fit_plan_constants.argtypes = [C.c_void_p]
+    lib.fit_plan_pass_launch.argtypes = [C.c_int] * 5 + [C.c_void_p]
+    lib.fit_plan_pass_launch.restype = None
     return lib
 
 
@@ -409,3 +411,51 @@ def test_persistent_variant(shim, case):
 def test_persistent_variant_count(shim):
     assert len(VARIANTS) == 32
     assert shim.fit_plan_persistent_variant_count() == 10 == len(set(VARIANTS.values()))
+
+
+# ---- which kernel a per-round vertex pass runs (fit_plan.h: plan_pass_launch) ----
+EXACT, SPLIT, LOOP, PIPE = range(4)
+# (split-fp16 basis, sparse skinning rows, even vertex count) -> (kernel, workgroups per tile) for chunks 1, 2, 5 (rows) x
+# pass_kernel 0, 1, 2 (columns).  All 72 cells, written out; the SPARSE_W instantiation is the model's sparse_skinning everywhere
+# but in the lock-step loop, which has none, and in the pipeline, which has no other.
+PASS_TABLE = {
+    (0, 0, 0): [[(EXACT, 1)] * 3, [(EXACT, 2)] * 3, [(EXACT, 5)] * 3],
+    (0, 0, 1): [[(EXACT, 1)] * 3, [(EXACT, 2)] * 3, [(EXACT, 5)] * 3],
+    (0, 1, 0): [[(EXACT, 1)] * 3, [(EXACT, 2)] * 3, [(EXACT, 5)] * 3],
+    (0, 1, 1): [[(EXACT, 1)] * 3, [(EXACT, 2)] * 3, [(EXACT, 5)] * 3],
+    (1, 0, 0): [[(SPLIT, 1)] * 3, [(LOOP, 1), (SPLIT, 2), (LOOP, 1)], [(LOOP, 1), (SPLIT, 5), (LOOP, 1)]],
+    (1, 0, 1): [[(SPLIT, 1)] * 3, [(LOOP, 1), (SPLIT, 2), (LOOP, 1)], [(LOOP, 1), (SPLIT, 5), (LOOP, 1)]],
+    (1, 1, 0): [[(SPLIT, 1)] * 3, [(SPLIT, 2), (SPLIT, 2), (SPLIT, 2)], [(SPLIT, 5), (SPLIT, 5), (SPLIT, 5)]],
+    (1, 1, 1): [[(SPLIT, 1)] * 3, [(PIPE, 1), (SPLIT, 2), (PIPE, 1)], [(PIPE, 1), (SPLIT, 5), (PIPE, 1)]],
+}
+PASS_CELLS = [(key, ci, pk) for key in sorted(PASS_TABLE) for ci in range(3) for pk in range(3)]
+
+
+@pytest.mark.parametrize('key, ci, pk', PASS_CELLS, ids=lambda v: ''.join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_pass_launch(shim, key, ci, pk):
+    split, sparse, even = key
+    chunks = (1, 2, 5)[ci]
+    out = np.zeros(3, np.int32)
+    shim.fit_plan_pass_launch(split, sparse, even, chunks, pk, out.ctypes.data)
+    kernel, grid_y = PASS_TABLE[key][ci][pk]
+    want_sparse = {LOOP: 0, PIPE: 1}.get(kernel, sparse)
+    assert tuple(out) == (kernel, want_sparse, grid_y)
+
+
+def test_pass_launch_table_is_whole(shim):
+    assert len(PASS_CELLS) == 72 and shim.fit_plan_pass_kernel_count() == 4
+    # pass_kernel 2 is pass_kernel 0 in every cell
+    assert all(row[0] == row[2] for rows_ in PASS_TABLE.values() for row in rows_)
+
+
+def test_pass_plan_helper_reads_the_same_table():
+    """tests/pass_plan.py (the ids of the GPU matrix) against the table above"""
+    from tests import pass_plan
+    for key, ci, pk in PASS_CELLS:
+        kernel, grid_y = PASS_TABLE[key][ci][pk]
+        got = pass_plan.pass_launch(*key, (1, 2, 5)[ci], pk)
+        assert (got[0], got[2]) == (kernel, grid_y)
+    assert pass_plan.kernel_name(SPLIT, 1) == 'lbs_vertex_pass_split_kernel<true>'
+    assert pass_plan.kernel_name(PIPE, 1) == 'lbs_vertex_pass_pipe_kernel'
+    assert pass_plan.short_name(1, 1, 1, 129, 0) == 'pipe' and pass_plan.short_name(1, 0, 0, 97, 0) == 'loop_dense'
+    assert pass_plan.short_name(1, 1, 0, 65, 0) == 'split_sparse' and pass_plan.short_name(0, 0, 0, 65, 0) == 'exact_dense'
