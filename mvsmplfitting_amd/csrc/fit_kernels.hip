@@ -274,7 +274,7 @@ __device__ __forceinline__ bool fit_round(const DevModel& M, ClosureLds& L, int 
         PH_T(10);
         // the single-launch fit takes the direction in compact form (history and R^-1 in LDS, every phase on all waves);
         // the chained step kernel keeps the two-loop form over its Gram matrices in global memory
-        if constexpr (COMPACT) lb_direction_compact<float, STEP_NT>(H, L.lbW, tid, lb_dir_general(O));
+        if constexpr (COMPACT) lb_direction_compact<float, STEP_NT>(H, L.lbW, tid, lb_dir_forms(O));
         else lb_direction_block<float, STEP_NT>(H, L.lbW, tid, GL);
         PH_T(11); PH_ADD(15, 1);
     });
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(64) void lbfgs_kat_kernel(int kind, int D, LbOpts O
         for (int e = 0; e < LB_EPL; ++e) gnew[e] = (LB_EPL * lane + e < D) ? gs[LB_EPL * lane + e] : 0.0;
         __syncthreads();
         lbfgs_round<double, 64, false>(&S, &Vm[0], H, W, O, f, gnew, xt, lane, final_loss, [&]() {   // the production round
-            if (compact) lb_direction_compact<double, 64>(H, W, lane, lb_dir_general(O));
+            if (compact) lb_direction_compact<double, 64>(H, W, lane, lb_dir_forms(O));
             else lb_direction_block<double, 64>(H, W, lane);
         });
         __syncthreads();

@@ -59,16 +59,18 @@ struct LbOpts {
     // optimiser still holds - the accepted line-search point (:393-399).  With the flag the device feeds those back
     // instead of evaluating again: same iterates, same eval accounting, 8-10 % fewer closure evaluations.
     int reuse_outer;
-    int dir_general;     // -DMVFIT_DEBUG_HOOKS builds only: every compact direction takes the general (ring) form of its
-                         // triangular products.  Always 0 otherwise, and no other build reads it.
+    int dir_forms;       // -DMVFIT_DEBUG_HOOKS builds only, LB_DIR_* bits: every compact direction takes the general (ring) form of
+                         // its triangular products / the LDS form of its mat-vecs.  Always 0 otherwise, and no other build reads it.
 };
+constexpr int LB_DIR_GENERAL = 1;      // MVFIT_DIR_GENERAL=1
+constexpr int LB_DIR_MATVEC_LDS = 2;   // MVFIT_DIR_MATVEC_LDS=1
 
-// hooks build: the environment switch the host read (uniform); every other build: false at compile time
-__device__ __forceinline__ bool lb_dir_general(const LbOpts& O) {
+// hooks build: the environment switches the host read (uniform); every other build: 0 at compile time
+__device__ __forceinline__ int lb_dir_forms(const LbOpts& O) {
 #ifdef MVFIT_DEBUG_HOOKS
-    return __builtin_amdgcn_readfirstlane(O.dir_general) != 0;
+    return __builtin_amdgcn_readfirstlane(O.dir_forms);
 #else
-    return false;
+    return 0;
 #endif
 }
 
@@ -681,13 +683,105 @@ __device__ __forceinline__ void lb_cmp_matvec(const T* rows, int ld, const T* co
     }
 }
 
+// The same mat-vec with its sums met in registers (8 waves of float): the sixteen row classes c = 0..15 (rows c, c + 16, ...)
+// of ONE chunk sit in the sixteen lanes of one DPP row, a wave carries four chunks.  Lane map (restated and checked in
+// tests/test_matvec_lanes.py): class = lane & 15; chunk = 2 wave + (row & 1) + 16 (row >> 1) - the two DPP rows that share
+// the lane groups of a 16-byte LDS read hold neighbouring chunks, and at ld = 88 (22 sixteen-byte units per history row:
+// class c starts 6 c units further, mod 16) the eight classes a group takes from one row cover the even units and those of
+// the other row the odd ones: no bank conflict.  Per lane the same loads and the same FMA chain as lb_cmp_matvec, then
+//   P_w = A_2w + A_2w+1                       one add with the neighbouring lane (the two operands of the half-wave swap)
+//   total = ((P_0 + P_1) + ... ) + P_7        seven dependent adds, P_w broadcast from lane 2 w of the row
+// in every lane of the row - the order in which the caller of lb_cmp_matvec adds the eight per-wave partials - and lane 0
+// of the row finishes the chunk: out = LAST ? fma(-Hdiag, tv, total) -> W.dv : total - qv -> W.tv, zeros from ld up to LB_D.
+// No partial sums in LDS, no combine loop: ONE barrier behind it.
+__host__ __device__ constexpr int lb_mv_chunk(int tid) { return 2 * (tid >> 6) + ((tid >> 4) & 1) + 16 * ((tid >> 5) & 1); }
+template <int W2>
+__device__ __forceinline__ float lb_row_bcast(float v) { return dpp_mov<0x150 + W2>(v); }       // row_newbcast: lane W2 of the row, in every lane
+
+template <typename T, int NT, bool LAST>
+__device__ __forceinline__ void lb_cmp_matvec_row(const T* rows, int ld, const T* coef, LbWork<T>& W, int tid) {
+    static_assert(NT == 512 && sizeof(T) == 4, "16 row classes x 32 chunk places");
+    const int n = W.n, head = W.head;
+    const int cl = lb_mv_chunk(tid), k = tid & 15;
+    const bool cok = 4 * cl < ld;
+    const int c = 4 * (cok ? cl : (cl & 1));               // a dead chunk's lanes read chunk 0 / 1 with zero coefficients (the parity keeps the banks apart)
+    constexpr int RP = 16, NIT = (LB_HIST + RP - 1) / RP;
+    T sub[4];
+    lb_load4((LAST ? W.tv : W.qv) + 4 * min(cl, LB_D / 4 - 1), sub);
+    const T nh = -W.Hdiag;
+    T acc[4] = {(T)0, (T)0, (T)0, (T)0};
+    {
+        T cf[8], rv[8][4];                                  // (eight steps as in lb_cmp_matvec: the last one has a zero coefficient and stays an FMA)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int r0 = k + i * RP, r = min(r0, LB_HIST - 1);
+            const bool ok = i < NIT && r0 < LB_HIST && lb_age(r, head) < n && cok;
+            const T cv = coef[r];
+            cf[i] = ok ? cv : (T)0;
+            lb_load4(rows + r * ld + c, rv[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = fma(cf[i], rv[i][j], acc[j]);
+    }
+    T out[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const T p = acc[j] + dpp_mov<DPP_XOR1>(acc[j]);
+        T s = lb_row_bcast<0>(p) + lb_row_bcast<2>(p);
+        s = s + lb_row_bcast<4>(p);
+        s = s + lb_row_bcast<6>(p);
+        s = s + lb_row_bcast<8>(p);
+        s = s + lb_row_bcast<10>(p);
+        s = s + lb_row_bcast<12>(p);
+        s = s + lb_row_bcast<14>(p);
+        out[j] = cok ? (LAST ? fma(nh, sub[j], s) : s - sub[j]) : (T)0;
+    }
+    if (k == 0 && cl < LB_D / 4) *reinterpret_cast<float4*>((LAST ? W.dv : W.tv) + 4 * cl) = make_float4(out[0], out[1], out[2], out[3]);
+}
+
+// one mat-vec phase of the compact direction up to and including its last barrier: t = Y w - q (LAST = false) or
+// d = S a - gamma t.  lds: per-wave partials in W.part, a combine loop, two barriers - the form of the 64-thread float64
+// instantiation and, in the hooks build, of MVFIT_DIR_MATVEC_LDS=1; else lb_cmp_matvec_row and one barrier.
+template <typename T, int NT, bool LAST>
+__device__ __forceinline__ void lb_cmp_matvec_phase(const LbHist<T>& Hh, LbWork<T>& W, int tid, int forms) {
+    const T* rows = LAST ? Hh.stps : Hh.dirs;
+    const T* coef = LAST ? W.cvec : W.alpha;
+    constexpr bool ROWS = NT == 512 && sizeof(T) == 4;
+#ifdef MVFIT_DEBUG_HOOKS
+    const bool lds = !ROWS || (forms & LB_DIR_MATVEC_LDS) != 0;
+#else
+    constexpr bool lds = !ROWS;
+    (void)forms;
+#endif
+    if constexpr (ROWS) {
+        if (!lds) {
+            lb_cmp_matvec_row<T, NT, LAST>(rows, Hh.ld, coef, W, tid);
+            __syncthreads();
+            return;
+        }
+    }
+    lb_cmp_matvec<T, NT>(rows, Hh.ld, coef, W, tid);
+    __syncthreads();
+    for (int e = tid; e < LB_D; e += NT) {
+        T sacc = W.part[0][e];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) sacc += W.part[k][e];
+        if (LAST) W.dv[e] = e < Hh.ld ? fma(-W.Hdiag, W.tv[e], sacc) : (T)0;
+        else W.tv[e] = e < Hh.ld ? sacc - W.qv[e] : (T)0;
+    }
+    __syncthreads();
+}
+
 // In: W.qv = -g, W.n / head / ins_slot / Hdiag, history rows, ys, ro incl. the freshly inserted pair.  Out: W.dv.
-// general: take the general form of the triangular products whatever the window (a switch of the hooks build).
+// forms: LB_DIR_* bits, switches of the hooks build (0 in every other): the general form of the triangular products
+// whatever the window, the LDS form of the mat-vecs.
 template <typename T, int NT>
-__device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork<T>& W, int tid, bool general = false) {
+__device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork<T>& W, int tid, int forms = 0) {
     // the window does not wrap round the ring: the triangular products take their no-wrap form (workgroup-uniform; a fit may
     // change form from one call to the next - both read and write the same packed R^-1 and the same work vectors)
-    const bool nowrap = !general && __builtin_amdgcn_readfirstlane(W.head + W.n) <= LB_HIST;
+    const bool nowrap = !(forms & LB_DIR_GENERAL) && __builtin_amdgcn_readfirstlane(W.head + W.n) <= LB_HIST;
     // ---- p = S^T q (+ u = S^T y_new) ----
     lb_cmp_rowdots<T, NT, true>(Hh, W, tid);
     __syncthreads();
@@ -698,15 +792,7 @@ __device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork
     __syncthreads();
     PH_T(17);
     // ---- t = Y w - q ----
-    lb_cmp_matvec<T, NT>(Hh.dirs, Hh.ld, W.alpha, W, tid);
-    __syncthreads();
-    for (int e = tid; e < LB_D; e += NT) {
-        T sacc = W.part[0][e];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) sacc += W.part[k][e];
-        W.tv[e] = e < Hh.ld ? sacc - W.qv[e] : (T)0;
-    }
-    __syncthreads();
+    lb_cmp_matvec_phase<T, NT, false>(Hh, W, tid, forms);
     PH_T(18);
     // ---- z = D w + gamma Y^T t ----
     lb_cmp_rowdots<T, NT, false>(Hh, W, tid);
@@ -718,15 +804,7 @@ __device__ __forceinline__ void lb_direction_compact(const LbHist<T>& Hh, LbWork
     __syncthreads();
     PH_T(20);
     // ---- d = S a - gamma t ----
-    lb_cmp_matvec<T, NT>(Hh.stps, Hh.ld, W.cvec, W, tid);
-    __syncthreads();
-    for (int e = tid; e < LB_D; e += NT) {
-        T sacc = W.part[0][e];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) sacc += W.part[k][e];
-        W.dv[e] = e < Hh.ld ? fma(-W.Hdiag, W.tv[e], sacc) : (T)0;
-    }
-    __syncthreads();
+    lb_cmp_matvec_phase<T, NT, true>(Hh, W, tid, forms);
     PH_T(21);
 }
 

@@ -10,7 +10,8 @@ static LbOpts lb_opts(const mvfit_lbfgs_opts& o, int num_stages) {
     O.lr = o.lr; O.tol_grad = o.tolerance_grad; O.tol_change = o.tolerance_change; O.ftol = o.ftol; O.gtol = o.gtol;
     O.max_iter = o.max_iter; O.max_eval = o.max_iter * 5 / 4; O.history = o.history; O.maxiters = o.maxiters;
     O.num_stages = num_stages;
-    O.dir_general = debug_hook("MVFIT_DIR_GENERAL") != 0;      // (hooks build only) the general form of the direction's triangular products
+    // (hooks build only) the general form of the direction's triangular products; the LDS form of its mat-vecs
+    O.dir_forms = (debug_hook("MVFIT_DIR_GENERAL") != 0 ? LB_DIR_GENERAL : 0) | (debug_hook("MVFIT_DIR_MATVEC_LDS") != 0 ? LB_DIR_MATVEC_LDS : 0);
     return O;
 }
 
