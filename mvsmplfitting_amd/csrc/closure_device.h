@@ -170,9 +170,21 @@ __device__ __forceinline__ void prologue(ClosureLds& L, const DevModel& M, const
     constexpr int nvp = sizeof(VpBlock) / 16;
     static_assert(nvp <= STEP_NT, "one word per thread");
     if (vp_g && tid < nvp) vvp = reinterpret_cast<const float4*>(vp_g)[tid];
+    // E6's lane cells (model_layout.h: e6_cells) lie behind the image; where the model has them they replace the head of each
+    // row of wT on the way into LDS (both words are loaded, the flag picks one: no load waits for it)
+    constexpr int row16 = NS_STRIDE * 4 / 16, cell16 = E6_ROW_BYTES / 16;
+    static_assert(offsetof(ModelLds, wT) == 0 && NS_STRIDE * 4 % 16 == 0 && (cell16 & (cell16 - 1)) == 0 && NJ * row16 <= 2 * STEP_NT,
+                  "the rows of wT are whole 16-byte words inside the first two words of a thread");
+    const int i1 = tid + STEP_NT;
+    const int4* cells = src + n16;
+    const int4 c0 = cells[min(tid / row16, NJ - 1) * cell16 + (tid % row16 & (cell16 - 1))];
+    const int4 c1 = cells[min(i1 / row16, NJ - 1) * cell16 + (i1 % row16 & (cell16 - 1))];
+    const bool e6 = M.mlds->e6_cells != 0;
     int4* dst = reinterpret_cast<int4*>(&L.M);
-    if (tid < n16) dst[tid] = m0;
-    if (tid + STEP_NT < n16) dst[tid + STEP_NT] = m1;
+    // (picked component by component: a select between two 16-byte objects is a select between their addresses - on the stack)
+    auto pick = [](bool c, const int4& a, const int4& b) { return make_int4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w); };
+    if (tid < n16) dst[tid] = pick(e6 && tid % row16 < cell16, c0, m0);
+    if (i1 < n16) dst[i1] = pick(e6 && i1 < NJ * row16 && i1 % row16 < cell16, c1, m1);
     if (tid + 2 * STEP_NT < n16) dst[tid + 2 * STEP_NT] = m2;
     if (tid + 3 * STEP_NT < n16) dst[tid + 3 * STEP_NT] = m3;
     if (obs_g && tid < nobs) reinterpret_cast<float4*>(&L.obs)[tid] = vobs;
@@ -1195,6 +1207,11 @@ template <bool REMOTE = false, bool DEFER = false, bool SDFW = false, bool SDFT 
 __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& L, int V, const DevWeights& W, int tid) {
     const bool use_vp = (W.flags & MVFIT_F_VPOSER) != 0;
     const int ns = L.M.ns, nc = L.M.nc, nc_pad = L.M.nc_pad;
+    // E6's cell of this thread (model constants, read ahead of the barriers: E6 then starts with its data loads); every
+    // thread reads - rows 24..31 lie inside the image - and only E6's threads use the word
+    static_assert(32 * NS_STRIDE * 4 <= sizeof(ModelLds), "a 16-lane row of every thread reads inside the image");
+    const bool e6_cells = L.M.e6_cells != 0, n_skel = L.M.n_skel != 0;
+    const uint2 e6_cw = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(&L.M) + (tid >> 4) * (NS_STRIDE * 4))[tid & 15];
     __syncthreads();                  // L.gkp (view sums) and L.gtau are written after E4's last barrier
     // ---- E5: g_x = Ksel^T g_kp ; g_vposed = Tr^T g_x ----
     if constexpr (DEFER) {
@@ -1241,36 +1258,62 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
     // ---- E6: g_A = sum_s W[s][j] [g_x v_posed^T | g_x]: 16-lane row per joint, lanes stride s ----
     if (tid < NJ * 16) {
         const int j = tid >> 4, g = tid & 15;
+        // operands of the phase's tail, row min(g, 2): read here, with the sums' own loads, not behind the row totals (every
+        // lane reads - a conditional LDS read is a branch; g_M holds E5's seed only for a model without a regressor)
+        const int ta = min(g, 2);
+        const float J0 = L.pose.J[j][0], J1 = L.pose.J[j][1], J2 = L.pose.J[j][2];
+        const float G0 = L.pose.G[j][0 + ta], G4 = L.pose.G[j][4 + ta], G8 = L.pose.G[j][8 + ta];
+        const float gm = L.gM[j][ta];
         float acc[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) acc[e] = 0.f;
-        for (int s = g; s < ns; s += 16) {
-            const float w = L.M.wT[j][s];
-            const float g0 = w * L.gx[3 * s], g1 = w * L.gx[3 * s + 1], g2 = w * L.gx[3 * s + 2];
-            const float v0 = L.vposed[3 * s], v1 = L.vposed[3 * s + 1], v2 = L.vposed[3 * s + 2];
+        // Every product and sum of this phase is stated, in the form the compiler had chosen for the plain expressions: the
+        // weighted g_x is a rounded product where it multiplies v_posed, and fused into the sum where it is added alone
+        auto add_vertex = [&acc](float w, float gx0, float gx1, float gx2, float v0, float v1, float v2) {
+            const float g0 = w * gx0, g1 = w * gx1, g2 = w * gx2;
             acc[0] = fmaf(g0, v0, acc[0]); acc[1] = fmaf(g0, v1, acc[1]); acc[2] = fmaf(g0, v2, acc[2]);
             acc[3] = fmaf(g1, v0, acc[3]); acc[4] = fmaf(g1, v1, acc[4]); acc[5] = fmaf(g1, v2, acc[5]);
             acc[6] = fmaf(g2, v0, acc[6]); acc[7] = fmaf(g2, v1, acc[7]); acc[8] = fmaf(g2, v2, acc[8]);
-            acc[9] += g0; acc[10] += g1; acc[11] += g2;
+            acc[9] = fmaf(w, gx0, acc[9]); acc[10] = fmaf(w, gx1, acc[10]); acc[11] = fmaf(w, gx2, acc[11]);
+        };
+        if (e6_cells) {                                    // uniform
+            // the lane's non-zero weights only (the prologue laid the cells over the head of wT's rows): the vertices the
+            // dense loop below would add a non-zero product for, in its order - a skipped product is fma(+-0, v, acc).  All
+            // loads of the E6_NZ entries in one batch; a padding entry reads word 0 and its weight becomes 0 afterwards
+            float w[E6_NZ], gx[E6_NZ][3], vp[E6_NZ][3];
+#pragma unroll
+            for (int t = 0; t < E6_NZ; ++t) {
+                const unsigned e = ((t & 2) ? e6_cw.y : e6_cw.x) >> (16 * (t & 1)) & 0xffffu;
+                const int i = (int)(e & (E6_INVALID - 1)), s = i >> 2;
+                const float wl = (&L.M.selw[0][0])[i];
+                w[t] = (e & E6_INVALID) ? 0.f : wl;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { gx[t][a] = L.gx[3 * s + a]; vp[t][a] = L.vposed[3 * s + a]; }
+            }
+#pragma unroll
+            for (int t = 0; t < E6_NZ; ++t) add_vertex(w[t], gx[t][0], gx[t][1], gx[t][2], vp[t][0], vp[t][1], vp[t][2]);
+        } else {
+            for (int s = g; s < ns; s += 16)
+                add_vertex(L.M.wT[j][s], L.gx[3 * s], L.gx[3 * s + 1], L.gx[3 * s + 2], L.vposed[3 * s], L.vposed[3 * s + 1], L.vposed[3 * s + 2]);
         }
 #pragma unroll
         for (int e = 0; e < 12; ++e) acc[e] = row16_sum(acc[e]);
-        if (g == 0) {
+        if (g < 3) {
+            // the row totals are in every lane: lane a finishes row a of g_G and g_J[a] (its operands were loaded above)
             if (sdf_fac != 0.f) {                          // + the SDF term's dense-vertex part of g_A
 #pragma unroll
                 for (int e = 0; e < 12; ++e) acc[e] = fmaf(sdf_fac, sdf_ld(&L.sdf_adj->gA[j * 12 + e]), acc[e]);
             }
             // A_j = [Gr_j | Gt_j - Gr_j J_j]:  g_Gt = g_At ; g_Gr = g_Ar - g_At J^T ; g_J = -Gr^T g_At
-            const float J0 = L.pose.J[j][0], J1 = L.pose.J[j][1], J2 = L.pose.J[j][2];
             // + the keypoints that ARE this joint's posed position (model without a regressor): their g_kp goes to g_Gt alone,
             // not through A (staged by E5 in L.gM)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                *reinterpret_cast<float4*>(&L.gG[j][4 * a]) =
-                    make_float4(acc[3 * a + 0] - acc[9 + a] * J0, acc[3 * a + 1] - acc[9 + a] * J1,
-                                acc[3 * a + 2] - acc[9 + a] * J2, L.M.n_skel ? acc[9 + a] + L.gM[j][a] : acc[9 + a]);
-                L.gJ[j][a] = -(L.pose.G[j][0 + a] * acc[9] + L.pose.G[j][4 + a] * acc[10] + L.pose.G[j][8 + a] * acc[11]);
-            }
+            auto row = [g](float r0, float r1, float r2) { return g == 0 ? r0 : (g == 1 ? r1 : r2); };
+            const float ar0 = row(acc[0], acc[3], acc[6]), ar1 = row(acc[1], acc[4], acc[7]), ar2 = row(acc[2], acc[5], acc[8]);
+            const float at = row(acc[9], acc[10], acc[11]);
+            // (g_Gr: one fused step per element; g_J: the middle product rounded, the outer two fused onto it, then the sign)
+            *reinterpret_cast<float4*>(&L.gG[j][4 * g]) =
+                make_float4(fmaf(-at, J0, ar0), fmaf(-at, J1, ar1), fmaf(-at, J2, ar2), n_skel ? at + gm : at);
+            L.gJ[j][g] = -fmaf(acc[11], G8, fmaf(acc[9], G0, acc[10] * G4));
         }
     }
     __syncthreads();

@@ -67,8 +67,15 @@ struct ModelLds {
     // non-zero products of the dense row in the same order: the same bits); sel_sparse = 0 when a row has more than 4
     float selw[NS_MAX][4];
     unsigned selj[NS_MAX];            // four joint indices, one per byte
-    int sel_sparse, spad0, spad1, spad2;
+    // e6_cells = 1: every cell of the adjoint's E6 (joint j, lane g = s mod 16) has <= E6_NZ non-zero weights and sel_sparse
+    // is 1 - the kernels' prologue then lays HostModel::e6_cells over the first E6_ROW_BYTES of each row of wT, which nothing
+    // else reads in that case (the image itself always holds the dense wT)
+    int sel_sparse, e6_cells, spad1, spad2;
 };
+constexpr int E6_NZ = 4;                                // padded entries per E6 cell
+constexpr unsigned E6_INVALID = 0x8000u;                // entry = 4 s + t (the word selw[s][t]) | E6_INVALID for padding
+constexpr int E6_ROW_BYTES = 16 * E6_NZ * 2;            // one joint's sixteen cells of 16-bit entries
+static_assert(E6_ROW_BYTES % 16 == 0 && E6_ROW_BYTES <= NS_STRIDE * 4 && NS_MAX * 4 <= (int)E6_INVALID, "E6 cells fit a row of wT");
 static_assert(sizeof(ModelLds) % 16 == 0, "ModelLds is bulk-copied as 16-byte words");
 static_assert(NKP <= 18 && NJ < 31, "kp_joint packs six 5-bit entries per word");
 

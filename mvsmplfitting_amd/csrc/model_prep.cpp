@@ -190,6 +190,22 @@ int build_selection(const mvfit_model& m, HostModel& h, std::string& err) {
         if (np > 4) sel_sparse = 0;
     }
     G.sel_sparse = sel_sparse;
+    // E6's lane cells: lane g of joint j's 16-lane row adds the vertices s = g, g + 16, ... - their non-zero weights in that
+    // order, each as the word of selw that holds it; a cell with more than E6_NZ of them (or a dense model) keeps the dense row
+    h.e6_cells.assign((size_t)NJ * 16 * E6_NZ, (uint16_t)E6_INVALID);
+    G.e6_cells = sel_sparse;
+    for (int j = 0; j < NJ && sel_sparse; ++j)
+        for (int g = 0; g < 16; ++g) {
+            int n = 0;
+            for (int s = g; s < ns; s += 16) {
+                if (G.wT[j][s] == 0.f) continue;
+                int t = 0;
+                while (t < 3 && (((G.selj[s] >> (8 * t)) & 0xffu) != (unsigned)j || G.selw[s][t] == 0.f)) ++t;   // (byte 0 also names padding)
+                if (n < E6_NZ) h.e6_cells[((size_t)j * 16 + g) * E6_NZ + n] = (uint16_t)(4 * s + t);
+                ++n;
+            }
+            if (n > E6_NZ) G.e6_cells = 0;
+        }
     // selection in CSR form, both ways
     int nnz = 0;
     for (int k = 0; k < NKP; ++k) {

@@ -44,6 +44,10 @@ struct HostModel {
     std::vector<int32_t> tile_sel_slot;  // [max(ns, 1)] selected-vertex slot s
     // ---- the LDS image of the per-problem kernels (model_layout.h) ----
     ModelLds lds;
+    // E6's lane cells [NJ][16 lanes][E6_NZ]: the non-zero entries of wT[j][s], s = g, g + 16, ... in ascending s, each as
+    // 4 s + t (the word of lds.selw that holds the weight), padded with E6_INVALID.  Uploaded behind the LDS image; used
+    // when lds.e6_cells is 1 (no cell longer than E6_NZ, lds.sel_sparse set)
+    std::vector<uint16_t> e6_cells;
     // ---- VPoser decoder (empty when the model has none) ----
     bool has_vposer = false;
     std::vector<float> vp_w1, vp_b1, vp_w2, vp_b2, vp_w3, vp_b3;   // [512][32], [512], [512][512], [512], [138][512], [138]

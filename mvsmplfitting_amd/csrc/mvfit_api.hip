@@ -46,7 +46,14 @@ static void upload_model(mvfit_ctx* c, const HostModel& h) {
     M.tile_sel_start = dev_upload(c, h.tile_sel_start);
     M.tile_sel_local = dev_upload(c, h.tile_sel_local);
     M.tile_sel_slot = dev_upload(c, h.tile_sel_slot);
-    M.mlds = dev_upload(c, &h.lds, 1);
+    {   // the LDS image and, behind it in the same allocation, E6's lane cells (closure_device.h: prologue)
+        std::vector<unsigned char> img(sizeof(ModelLds) + NJ * E6_ROW_BYTES, 0);
+        ModelLds lds = h.lds;
+        if (debug_hook("MVFIT_E6_DENSE") != 0) lds.e6_cells = 0;          // (hooks build only) E6 on the dense rows of wT
+        memcpy(img.data(), &lds, sizeof(ModelLds));
+        memcpy(img.data() + sizeof(ModelLds), h.e6_cells.data(), std::min<size_t>(h.e6_cells.size() * 2, NJ * E6_ROW_BYTES));
+        M.mlds = reinterpret_cast<const ModelLds*>(dev_upload(c, img));
+    }
     M.vp_w1 = dev_upload(c, h.vp_w1); M.vp_b1 = dev_upload(c, h.vp_b1);
     M.vp_w2 = dev_upload(c, h.vp_w2); M.vp_b2 = dev_upload(c, h.vp_b2);
     M.vp_w3 = dev_upload(c, h.vp_w3); M.vp_b3 = dev_upload(c, h.vp_b3);
