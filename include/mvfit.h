@@ -781,10 +781,12 @@ int mvfit_pass_profile(mvfit_ctx* ctx, int* tiles_per_wg, int* workgroups, int* 
 
 /* Known-answer test entry for the device L-BFGS state machine (same template as production,
  * instantiated in float64) on the analytic objectives of oracle/lbfgs_np.py:kat_objective.
- *   kind: 0 quad, 1 rosen, 2 gmof ; D <= 96 ; x_inout[D] host ; trace[max_trace,(D+1)] host
+ *   kind: 0 quad, 1 rosen, 2 gmof, 3 linear, 4 wavy, 5 wavy2, 6 steep, 7 steep2 (| 0x100: the direction in compact form) - any
+ *   other kind is MVFIT_E_ARG ; D <= 96 ; x_inout[D] host ; trace[max_trace,(D+1)] host
  *   (x_trial, loss per closure) ; segs[nseg+1] parameter-tensor boundaries for the gtol test ;
  *   opts as for mvfit_fit (num_stages and max_rounds are not read): max_iter, maxiters > 0 and
  *   1 <= history <= MVFIT_HISTORY, else MVFIT_E_ARG before anything is launched. */
+#define MVFIT_KAT_KINDS 8
 int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs, int nseg,
                     const mvfit_lbfgs_opts* opts, double* x_inout, double* trace, int max_trace,
                     int* n_closure, double* final_loss);

@@ -546,6 +546,27 @@ __device__ double kat_eval(int kind, int D, const double* x, double* g) {
             g[i] += -400.0 * a * x[i] - 2.0 * bb;
             g[i + 1] += 200.0 * a;
         }
+    } else if (kind == 3) {                                    // 'linear': c . x, unbounded below
+        for (int i = 0; i < D; ++i) {
+            const double c = 1.0 + (double)i / D;
+            f += c * x[i]; g[i] = c;
+        }
+    } else if (kind == 4 || kind == 5) {                       // 'wavy' / 'wavy2': sum 0.5 x^2 + a sin(b x)
+        const double a = kind == 4 ? 5.0 : 0.5, b = kind == 4 ? 7.0 : 3.0;
+        for (int i = 0; i < D; ++i) {
+            f += 0.5 * x[i] * x[i] + a * sin(b * x[i]);
+            g[i] = x[i] + (a * b) * cos(b * x[i]);
+        }
+    } else if (kind == 6) {                                    // 'steep': -sum c x^4, unbounded below and ever steeper
+        for (int i = 0; i < D; ++i) {
+            const double c = 1.0 + (double)i / D, x2 = x[i] * x[i];
+            f += -c * (x2 * x2); g[i] = -4.0 * c * (x2 * x[i]);
+        }
+    } else if (kind == 7) {                                    // 'steep2': -sum c |x|^(31/16), unbounded below, its slope growing ever slower
+        for (int i = 0; i < D; ++i) {
+            const double c = 1.0 + (double)i / D, r = sqrt(sqrt(sqrt(sqrt(fabs(x[i])))));
+            f += -c * (x[i] * x[i] / r); g[i] = -1.9375 * c * (x[i] / r);
+        }
     } else {
         const double rho2 = 1e4;
         for (int i = 0; i < D; ++i) g[i] = x[i];

@@ -155,12 +155,17 @@ __device__ __forceinline__ T vdot(const T* a, const T* b) {
     for (int e = 0; e < LB_EPL; ++e) s = fma(a[e], b[e], s);
     return wave64_sum(s);
 }
+// max |a_i| like the reference's abs().max(): NaN if any element is NaN (fmax alone drops NaNs: a NaN gradient or
+// direction would give 0, and the tolerance_grad, step-size and bracket-width tests would fire where the reference's
+// comparisons with NaN are false)
 template <typename VT>
 __device__ __forceinline__ double vmaxabs(const VT* a) {
     VT s = (VT)0;
+    bool nan = false;
 #pragma unroll
-    for (int e = 0; e < LB_EPL; ++e) s = fmax(s, fabs(a[e]));
-    return (double)wave64_max(s);
+    for (int e = 0; e < LB_EPL; ++e) { s = fmax(s, fabs(a[e])); nan = nan || a[e] != a[e]; }
+    const double m = (double)wave64_max(s);
+    return __builtin_amdgcn_ballot_w64(nan) != 0 ? (double)NAN : m;
 }
 
 // lbfgs_ls.py:11-36

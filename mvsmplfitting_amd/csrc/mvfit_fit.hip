@@ -570,6 +570,7 @@ extern "C" int mvfit_lbfgs_kat(int device, int kind, int D, const int32_t* segs,
                                double* x_inout, double* trace, int max_trace, int* n_closure, double* final_loss) {
     if (!o || !x_inout || D <= 1 || D > LB_D || nseg < 1 || nseg > 8 || !segs) return MVFIT_E_ARG;
     if (!lb_opts_ok(*o)) return MVFIT_E_ARG;
+    if ((kind & ~0x100) < 0 || (kind & ~0x100) >= MVFIT_KAT_KINDS) return MVFIT_E_ARG;      // (an unknown kind used to run 'gmof')
     if (hipSetDevice(device) != hipSuccess) return MVFIT_E_HIP;
     LbOpts O = lb_opts(*o, 1);
     O.nseg = nseg;

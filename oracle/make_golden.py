@@ -11,6 +11,7 @@ Files
   closure_<case>.npz      x[B,D], cams, gt_xy, conf, weights -> reference loss / grad /
                           joints / vertices in float64 and float32
   lbfgs_kat.npz           reference LBFGS+run_fitting closure traces on analytic objectives
+  lbfgs_kat_branches.npz  the same for the runs of tests/lbfgs_branch_cases.py, with the oracle's branch tags
   fit_<case>.npz          reference 4-stage fits (final params / loss / closure counts)
 """
 from __future__ import annotations
@@ -143,17 +144,20 @@ def gen_closure_goldens(lsp, only=None):
         print('%-18s loss64 %s  fp32-vs-fp64 rel %.1e' % (name, res['float64'][0], e_l.max()))
 
 
-def run_ref_lbfgs(fn, x0, segments, dtype_name='float64', maxiters=30, tolerances=None):
+def run_ref_lbfgs(fn, x0, segments, dtype_name='float64', maxiters=30, tolerances=None, lr=1.0, max_iter=30, history=100,
+                  ftol=1e-9, gtol=1e-9):
     """tolerances = (tolerance_grad, tolerance_change): construct the reference's LBFGS class directly (the factory
-    does not forward them, optim_factory.py:50-52)."""
+    does not forward them, optim_factory.py:50-52) - and so with any lr / max_iter / history other than what gen_lbfgs_kat
+    has always asked the factory for.  maxiters / ftol / gtol are run_fitting's."""
     import torch
     ref = ri.load()
     dt = torch.float64 if dtype_name == 'float64' else torch.float32
     ps = [torch.nn.Parameter(torch.tensor(x0[a:b], dtype=dt)) for a, b in segments]
-    if tolerances is None:
+    if tolerances is None and (lr, max_iter, history) == (1.0, 30, 100):
         opt, _ = ref.optim_factory.create_optimizer(ps, optim_type='lbfgsls', lr=1.0, maxiters=30)
     else:
-        opt = ref.lbfgs_ls.LBFGS(ps, lr=1.0, max_iter=30, tolerance_grad=tolerances[0], tolerance_change=tolerances[1],
+        tg, tc = tolerances if tolerances is not None else (1e-5, 1e-9)
+        opt = ref.lbfgs_ls.LBFGS(ps, lr=lr, max_iter=max_iter, tolerance_grad=tg, tolerance_change=tc, history_size=history,
                                  line_search_fn='strong_Wolfe')
     trace = []
 
@@ -164,7 +168,7 @@ def run_ref_lbfgs(fn, x0, segments, dtype_name='float64', maxiters=30, tolerance
             p.grad = torch.tensor(g[a:b], dtype=dt)
         trace.append(np.concatenate([x, [f]]))
         return torch.tensor(f, dtype=dt)
-    mon = ref.fitting.FittingMonitor(maxiters=maxiters, ftol=1e-9, gtol=1e-9)
+    mon = ref.fitting.FittingMonitor(maxiters=maxiters, ftol=ftol, gtol=gtol)
     with contextlib.redirect_stdout(io.StringIO()):
         final = mon.run_fitting(opt, closure, ps, None, use_vposer=False)
     xf = torch.cat([p.detach() for p in ps]).numpy().astype(np.float64)
@@ -201,6 +205,38 @@ def gen_lbfgs_kat():
         out[key + '_tc'] = np.array(tc)
         print('kat', key, 'tolerance_change', tc, 'closures', len(trace), 'final', final)
     np.savez_compressed(os.path.join(GOLD, 'lbfgs_kat.npz'), **out)
+    gen_lbfgs_kat_branches()
+
+
+def gen_lbfgs_kat_branches():
+    """tests/golden/lbfgs_kat_branches.npz: per case of tests/lbfgs_branch_cases.py the start, the reference's whole trace,
+    closure count, final loss (NaN where run_fitting returns None) and final point - and the branch tags of the oracle
+    replaying that trace (tests/lbfgs_follow.py), which tests/test_lbfgs_oracle.py holds to the trace closure for closure."""
+    import warnings
+    from tests import lbfgs_branch_cases as bc
+    from tests import lbfgs_follow as lf
+    out = {}
+    for c in bc.CASES:
+        name, D = c['name'], c['D']
+        fn, _ = ln.kat_objective(c['kind'], D)
+        x0 = bc.make_x0(c)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)           # the non-finite case overflows on purpose
+            final, trace, xf = run_ref_lbfgs(fn, x0, bc.SEGMENTS(D), maxiters=c['maxiters'],
+                                             tolerances=(c['tolerance_grad'], c['tolerance_change']), lr=c['lr'],
+                                             max_iter=c['max_iter'], history=c['history'], ftol=c['ftol'], gtol=c['gtol'])
+            assert len(trace) <= bc.MAX_CLOSURES, (name, len(trace))
+            fo = lf.replay(trace, D, kind=c['kind'], case=c)
+        assert not fo.exhausted and len(fo.trace) == len(trace), (name, len(fo.trace), len(trace))
+        out[name + '_x0'] = x0
+        out[name + '_trace'] = trace
+        out[name + '_n'] = np.array(len(trace))
+        out[name + '_final'] = np.array(np.nan if final is None else final)
+        out[name + '_xf'] = xf
+        out[name + '_tag_at'] = np.array([i for i, _ in fo.branches], np.int32)
+        out[name + '_tags'] = np.array([t for _, t in fo.branches])
+        print('kat branches', name, 'closures', len(trace), 'final', final, 'replay deviation %.2g' % np.nanmax(fo.dev))
+    np.savez_compressed(os.path.join(GOLD, 'lbfgs_kat_branches.npz'), **out)
 
 
 def run_reference_fit(rp, x0, stages):

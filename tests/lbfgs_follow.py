@@ -9,7 +9,11 @@ one - one round's direction and line-search arithmetic on the recorded run's own
 set of pairs than the oracle's (stale pair, mis-ordered ring) proposes another direction at the first such round.
 
 Shared by tests/test_lbfgs_follow_cpu.py (which pins the method: what it measures on a clean run and on mutants) and
-tests/test_gpu_lbfgs_history.py (which judges the device with it).
+tests/test_gpu_lbfgs_history.py (which judges the device with it); with the objective and options of a case of
+tests/lbfgs_branch_cases.py also by tests/test_lbfgs_branch_cases_cpu.py and tests/test_gpu_lbfgs_branches.py, which compare
+the branch sequence of the replay (LbfgsOracle.branches) as well.  Limit of the method: inside ONE line search the oracle keeps
+its own step lengths, so a search of many interior cubic extrapolations amplifies rounding closure by closure (27 x per
+closure on -sum |x|^1.5: such a run is no case).
 """
 import numpy as np
 
@@ -45,7 +49,13 @@ class FollowOracle(ln.LbfgsOracle):
         if i >= len(self.rows):
             raise TraceExhausted('the recorded trace ends after %d closures' % len(self.rows))
         row = self.rows[i]
-        self.dev.append(float(np.abs(x - row).max() / max(1.0, np.abs(row).max())))
+        ok = np.isfinite(row)
+        if ok.all():
+            self.dev.append(float(np.abs(x - row).max() / max(1.0, np.abs(row).max())))
+        else:       # a non-finite recorded point: the proposal has to be non-finite in the same places (NaN for NaN, inf for inf)
+            same = np.array_equal(x[~ok], row[~ok], equal_nan=True)
+            self.dev.append(float(np.abs(x[ok] - row[ok]).max(initial=0.0) / max(1.0, np.abs(row[ok]).max(initial=0.0))) if same
+                            else float('inf'))
         self._proposed.append((i, x))
         return super()._eval(row)
 
@@ -58,8 +68,14 @@ class FollowOracle(ln.LbfgsOracle):
         self._continue()
         self._proposed = []
         x = self.x
+        nb = len(self.branches)
         out = super()._strong_wolfe(t, d, f, g, gtd, **kw)
-        hit = [i for i, p in self._proposed if np.array_equal(p, x + out[2] * d)]
+        hit = [i for i, p in self._proposed if np.array_equal(p, x + out[2] * d, equal_nan=True)]
+        tags = [tag for _, tag in self.branches[nb:]]
+        from_zero = 'max_ls' in tags or ('extrapolate' not in tags and ('bracket_fail_it0' in tags or 'bracket_gtd_pos' in tags))
+        if not hit and out[2] == 0 and from_zero:      # a bracket [0, t] whose low end is still the point the search started from
+            self._resume = x.copy()
+            return out
         assert hit, 'the accepted step is none of the proposals of its line search'
         self._resume = self.rows[hit[-1]].copy()
         return out
@@ -71,14 +87,21 @@ class FollowOracle(ln.LbfgsOracle):
         return out
 
 
-def replay(rows, D, history, dtype=np.float64):
-    """Replays ``rows`` with the clean oracle.  Returns the FollowOracle (``exhausted`` set when the oracle wanted more closures
-    than were recorded)."""
-    fn, _ = ln.kat_objective('rosen', D)
-    fo = FollowOracle(rows, fn, history=history, dtype=dtype)
+def replay(rows, D, history=100, dtype=np.float64, kind='rosen', case=None, cls=FollowOracle):
+    """Replays ``rows`` with the clean oracle on objective ``kind``.  case: an entry of tests/lbfgs_branch_cases.py, whose
+    optimiser and run_fitting options then apply (else the production ones at ``history``); cls: the oracle to replay with
+    (FollowOracle or a mutant of it).  Returns the oracle (``exhausted`` set when it wanted more closures than were recorded;
+    ``final`` = what run_fitting returned, None then)."""
+    fn, _ = ln.kat_objective(kind, D)
+    okw, fkw = dict(history=history), dict(segments=SEGMENTS + [(13, D)])
+    if case is not None:
+        from tests import lbfgs_branch_cases as bc
+        okw, fkw = bc.oracle_opts(case)
+    fo = cls(rows, fn, dtype=dtype, **okw)
     fo.exhausted = False
+    fo.final = None
     try:
-        ln.run_fitting(fo, segments=SEGMENTS + [(13, D)])
+        fo.final, _ = ln.run_fitting(fo, **fkw)
     except TraceExhausted:
         fo.exhausted = True
     return fo
