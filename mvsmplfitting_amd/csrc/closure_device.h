@@ -19,7 +19,7 @@
 //   E4  thread per (view, keypoint): keypoint, projection, GMoF, d/d keypoint; priors on wave 4;
 //       DPP wave reductions -> LDS
 //   E5  g_x, g_vposed                                                            (thread per coordinate)
-//   E6  g_A = W^T [g_x v_posed^T | g_x]: 16-lane row per joint, DPP butterfly
+//   E6  g_A = W^T [g_x v_posed^T | g_x]: 16-lane row per joint, DPP butterfly (waves 0-5); waves 6-7 issue their E7 loads
 //   E7  wave 0: chain adjoint; waves 1-7: stream pd_subT (g_coef partials)      [overlapped]
 //   E8  g_R assembly, g_J, g_beta; E9 Rodrigues adjoint + pose priors; flat gradient
 #pragma once
@@ -1152,6 +1152,7 @@ __device__ __forceinline__ void chain_backward_wave(ClosureLds& L, int lane) {
 // g_coef partials = pd_subT . g_vposed: 8 column slices x 56 float4 row groups = 448 items, one per
 // thread of waves 1-7; partials in L.scratch[cs][KROWS].  Loads first, as in the forward stream.
 constexpr int BWD_SLICES = 8, BWD_CPS = NC_MAX / BWD_SLICES;     // up to 36 columns per slice
+constexpr int BWD_SMPL_CPS = 28;                                 // the SMPL keypoint set's columns per slice
 __device__ __forceinline__ int bwd_slices(int) { return BWD_SLICES; }
 
 // CPS = compile-time bound of the columns per slice (the SMPL keypoint set: 28 of the array's 36 - the loop over the array's
@@ -1190,9 +1191,47 @@ __device__ __forceinline__ void contraction_backward_t(const DevModel& M, Closur
 }
 
 __device__ __forceinline__ void contraction_backward(const DevModel& M, ClosureLds& L, int t, int nthreads) {
-    constexpr int SMPL_CPS = 28;
-    if (((L.M.nc_pad >> 2) + BWD_SLICES - 1) / BWD_SLICES * 4 <= SMPL_CPS) contraction_backward_t<SMPL_CPS>(M, L, t, nthreads);      // uniform
+    if (((L.M.nc_pad >> 2) + BWD_SLICES - 1) / BWD_SLICES * 4 <= BWD_SMPL_CPS) contraction_backward_t<BWD_SMPL_CPS>(M, L, t, nthreads);      // uniform
     else contraction_backward_t<BWD_CPS>(M, L, t, nthreads);
+}
+
+// The same item in two halves, for the waves that idle in E6 (closure_backward): an item's loads depend on nothing the round
+// computes - pd_subT is a model constant, only the FMAs need g_vposed -, so those waves issue them in E6, one barrier ahead of
+// E7, and E7 finds the data on its way.  One form for every model: the first BWD_SMPL_CPS loads unconditional, the rest by cps
+// - what contraction_backward_t loads in either instantiation; the same addresses (slice rotation, column clamp), the same
+// FMAs in the same order on the same two accumulators and the same store.
+static_assert((KROWS >> 2) * BWD_SLICES == STEP_NT - 64, "one transposed item per thread of waves 1-7");
+__device__ __forceinline__ void bwd_item_load(const DevModel& M, int nc_pad, int item, float4 (&v)[BWD_CPS]) {
+    constexpr int npq = KROWS >> 2;
+    const int cps = ((nc_pad >> 2) + BWD_SLICES - 1) / BWD_SLICES * 4;
+    const int pq = item % npq, cs = (item / npq + (int)blockIdx.x) & (BWD_SLICES - 1);
+    const int c0 = cs * cps;
+    const float4* src = reinterpret_cast<const float4*>(M.pd_subT) + pq;
+#pragma unroll
+    for (int r = 0; r < BWD_CPS; ++r) {
+        const int c = min(c0 + r, nc_pad - 1);
+        if (r < BWD_SMPL_CPS || r < cps) v[r] = src[(size_t)c * npq];
+    }
+}
+
+__device__ __forceinline__ void bwd_item_fma(ClosureLds& L, int nc_pad, int item, const float4 (&v)[BWD_CPS]) {
+    constexpr int npq = KROWS >> 2;
+    const int cps = ((nc_pad >> 2) + BWD_SLICES - 1) / BWD_SLICES * 4;
+    const int pq = item % npq, cs = (item / npq + (int)blockIdx.x) & (BWD_SLICES - 1);
+    const int c0 = cs * cps;
+    float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+#pragma unroll
+    for (int r = 0; r < BWD_CPS; r += 2) {
+        if (r < cps) {
+            const float g0 = L.gvp[c0 + r], g1 = L.gvp[c0 + r + 1];
+            acc0.x = fmaf(g0, v[r].x, acc0.x); acc0.y = fmaf(g0, v[r].y, acc0.y);
+            acc0.z = fmaf(g0, v[r].z, acc0.z); acc0.w = fmaf(g0, v[r].w, acc0.w);
+            acc1.x = fmaf(g1, v[r + 1].x, acc1.x); acc1.y = fmaf(g1, v[r + 1].y, acc1.y);
+            acc1.z = fmaf(g1, v[r + 1].z, acc1.z); acc1.w = fmaf(g1, v[r + 1].w, acc1.w);
+        }
+    }
+    float4* dst = reinterpret_cast<float4*>(L.scratch + cs * KROWS + 4 * pq);
+    *dst = make_float4(acc0.x + acc1.x, acc0.y + acc1.y, acc0.z + acc1.z, acc0.w + acc1.w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1255,8 +1294,22 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
     __syncthreads();
     PH_T(4);
     const float sdf_fac = SDFT ? L.sdf_fac : 0.f;       // (side results of the loss's combine: complete behind this barrier in either mode)
+    // E7's transposed stream, thread 64 + t owns item t.  Waves 6-7 have nothing to do in E6 and the CU's L2 path is idle
+    // there: they issue their item's loads behind E6's branch and E7 finds 128 of the 448 items on their way.  The values
+    // are live across E6's closing barrier only.  The roles are whole waves and their branches scalar (wave_t0), and each
+    // role is an `if` of its own, the early FMAs ahead of the other waves' stream: as the two sides of an if / else the
+    // compiler lays one side behind the other and keeps e7v allocated across the in-slot stream's 144 registers.
+    static_assert(NJ * 16 % 64 == 0 && NJ * 16 < STEP_NT, "E6 leaves whole waves free");
+#ifdef MVFIT_DEBUG_HOOKS
+    const bool bwd_late = (__builtin_amdgcn_readfirstlane(L.M.stream_late) & 1) != 0;      // the test's switch: every wave loads in E7
+#else
+    constexpr bool bwd_late = false;
+#endif
+    const int wave_t0 = __builtin_amdgcn_readfirstlane(tid);                               // this wave's first thread
+    const bool e7_early = !bwd_late && wave_t0 >= NJ * 16;
+    float4 e7v[BWD_CPS];
     // ---- E6: g_A = sum_s W[s][j] [g_x v_posed^T | g_x]: 16-lane row per joint, lanes stride s ----
-    if (tid < NJ * 16) {
+    if (wave_t0 < NJ * 16) {
         const int j = tid >> 4, g = tid & 15;
         // operands of the phase's tail, row min(g, 2): read here, with the sums' own loads, not behind the row totals (every
         // lane reads - a conditional LDS read is a branch; g_M holds E5's seed only for a model without a regressor)
@@ -1316,14 +1369,21 @@ __device__ __forceinline__ void closure_backward(const DevModel& M, ClosureLds& 
             L.gJ[j][g] = -fmaf(acc[11], G8, fmaf(acc[9], G0, acc[10] * G4));
         }
     }
+    if (e7_early) bwd_item_load(M, nc_pad, tid - 64, e7v);
     __syncthreads();
     PH_T(5);
     // ---- E7: chain adjoint on wave 0 || transposed contraction on waves 1-7 ----
     // (measured: the two overlap - the one-wave walk up the tree, 5 k cycles, hides the 186 KB stream; the whole-workgroup
     // form of the adjoint, chain_backward_block, is shorter alone but runs behind the stream: +0.7-1.1 us per round)
     const long long t_e7 = PH_CLK();
-    if (tid < 64) { chain_backward_wave(L, tid); PH_T(23); }
-    else { contraction_backward(M, L, tid - 64, STEP_NT - 64); PH_W(59, 64, t_e7); PH_W(61, 448, t_e7); }
+    if (e7_early) bwd_item_fma(L, nc_pad, tid - 64, e7v);                  // waves 6-7: the loads are on their way since E6
+    if (wave_t0 == 0) {
+        chain_backward_wave(L, tid); PH_T(23);
+    } else if (!e7_early) {
+        __builtin_assume(tid >= 64);                                       // (one item per thread: no loop)
+        contraction_backward(M, L, tid - 64, STEP_NT - 64);
+    }
+    PH_W(59, 64, t_e7); PH_W(61, 448, t_e7);
     const int ncs = bwd_slices(STEP_NT - 64);
     __syncthreads();
     PH_T(6);

@@ -70,7 +70,9 @@ struct ModelLds {
     // e6_cells = 1: every cell of the adjoint's E6 (joint j, lane g = s mod 16) has <= E6_NZ non-zero weights and sel_sparse
     // is 1 - the kernels' prologue then lays HostModel::e6_cells over the first E6_ROW_BYTES of each row of wT, which nothing
     // else reads in that case (the image itself always holds the dense wT)
-    int sel_sparse, e6_cells, spad1, spad2;
+    // stream_late: always 0 in the image the host builds; the -DMVFIT_DEBUG_HOOKS build sets bit 0 on request (MVFIT_BWD_STREAM_LATE)
+    // and only that build's kernels read it: every wave of the adjoint's transposed stream then loads inside E7
+    int sel_sparse, e6_cells, stream_late, spad2;
 };
 constexpr int E6_NZ = 4;                                // padded entries per E6 cell
 constexpr unsigned E6_INVALID = 0x8000u;                // entry = 4 s + t (the word selw[s][t]) | E6_INVALID for padding
