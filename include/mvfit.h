@@ -475,6 +475,63 @@ int mvfit_silhouette_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies,
  * non-finite or negative w_in / w_out, a non-finite sigma, a mask set whose image_body lies outside [0, B). */
 int mvfit_set_silhouette_term(mvfit_ctx* ctx, int enable, float w_in, float w_out, float sigma);
 
+/* ---- Occlusion between the bodies of a scene (csrc/silhouette_occlusion.hip).  A person mask from a segmenter is modal: it
+ * shows the visible part of the person only.  Where another body of the scene stands in front, an off pixel says nothing
+ * about this body: term A would push the body out from behind the other one, term B would pull it onto the line where the
+ * other one cuts its mask.  mvfit_set_silhouette_occluders freezes the other bodies as depth maps per mask image; while
+ * they are set, mvfit_silhouette_loss, mvfit_closure, the term in mvfit_fit and the term mix ignore what the maps hide.
+ * With no occluders set every entry returns the bits it returns without this section.
+ *
+ * Freeze, at vertices[N,Nv,3] dev with body_scene[N] host (N = num_bodies): image i shows body n = image_body[i].
+ *   body_scene[n] < 0: the image has no occluders.  Otherwise its occluders are all bodies m != n with body_scene[m] ==
+ *   body_scene[n], at vertices[m]; a body without images still occludes.
+ *   Depth maps at the mask set's H x W through the image's own camera: Z_occ,i[y,x] = the smallest fp32 depth of any
+ *     occluder face covering the pixel sample, Z_own,i the same from vertices[n] itself (every image has it), both +inf
+ *     where nothing covers the sample.  Transform, coverage, depth formula, [znear, zfar] and guard band are exactly those
+ *     of mvfit_render_overlay below (fp32 transform, 1/256-pixel integer edge functions with inclusive edges, float64
+ *     perspective depth rounded to fp32, [0.05, 8000], 16384 px).  The minimum is taken over the fp32 bits (positive floats
+ *     order like their bits): order-independent, deterministic, independent of any grouping of images or bodies.
+ *   Point flags, one byte per kept contour point (contour list, CSR, chunk table and every buffer of the mask set stay as
+ *     they are).  For point p of image i and a 4-neighbour q of p that lies inside the image and is off in the mask: q is
+ *     explained iff Z_occ,i(q) < +inf and not (Z_own,i(p) <= Z_occ,i(q)) - an own depth of +inf counts as "not known to be
+ *     in front".  The point is flagged iff all its off in-image 4-neighbours are explained.
+ * Evaluation while occluders are set:
+ *   A valid vertex (pz > 0.05) projected to (u, v) is hidden in image i iff 0 <= u < W and 0 <= v < H (fp32 compares) and
+ *     Z_occ,i[(int)v][(int)u] + margin < pz, the add rounded to fp32, nothing fused.  A hidden vertex contributes to neither
+ *     term, exactly like an invalid one: nothing to term A, no candidate in term B's search.
+ *   A flagged contour point contributes 0: winner -2 in the diagnostic output, no gradient; B_i stays contour_stride * sum
+ *     over the unflagged kept points.
+ *   Everything else - rho forms, summation orders, fixed-point accumulators, determinism, independence of N, of the body's
+ *     position and of other scenes - is the contract above.
+ * mvfit_silhouette_occluders_read: z_occ[M,H,W], z_own[M,H,W] float32 and point_flag[C] uint8, dev out or NULL.
+ * mvfit_silhouette_hidden: hidden[M,Nv] uint8 dev out, the hidden byte per (image, vertex) at vertices[num_bodies,Nv,3]; 0
+ * for invalid vertices and 0 everywhere without occluders.
+ * Lifetime.  The occluders belong to the mask set: every mvfit_set_silhouettes call clears them (a failing one and
+ * num_images = 0 included).  num_bodies = 0 or vertices = NULL clears them; a failed freeze leaves none set.  A re-freeze
+ * with unchanged (M, H, W, C) keeps every buffer address; the captured round graph's key holds the maps' buffer, whether
+ * occluders are set and margin, so a re-freeze alone does not rebuild the graph.  The freeze waits for the stream.
+ * Workspace, kept in the ctx: 8 M H W + C bytes (two maps and the flags, each part rounded up to 256 bytes), plus for the
+ * raster 16 bytes per instance (an image's own body and each of its occluders) and, per instance of a group of at most
+ * 512, 16 Nv + 4 Nf bytes of vertex records and large-face list, grown to the largest freeze seen like the renderer's.
+ * A face whose pixel box exceeds 1024 pixels is rasterised by a whole workgroup, as in the renderer.
+ * MVFIT_E_STATE: no mask set; a model without (valid) faces; mvfit_silhouette_occluders_read without occluders.
+ * MVFIT_E_ARG: NULL body_scene, num_bodies outside [1, 65535] or not above the mask set's largest image_body, margin
+ * negative or not finite; for mvfit_silhouette_hidden a NULL pointer or num_bodies as above.
+ * Not built: a body's self-occlusion (its own mask covers it), label images shared between persons. */
+int mvfit_set_silhouette_occluders(mvfit_ctx* ctx, const float* vertices, int num_bodies, const int32_t* body_scene, float margin);
+int mvfit_silhouette_occluders_read(mvfit_ctx* ctx, float* z_occ, float* z_own, uint8_t* point_flag);
+int mvfit_silhouette_hidden(mvfit_ctx* ctx, const float* vertices, int num_bodies, uint8_t* hidden);
+
+/* The captured round graph of the chained rounds (mvfit_fit with a term other than mvfit_set_sdf's, or round_mode = 1) and the
+ * buffers a re-freeze must keep.  out4 (host, or NULL): [0] round graphs captured on this ctx so far - a fit whose key
+ * (buffers, sizes, weights, options; see the terms above) equals the last capture's replays that graph and does not count;
+ * [1..3] the device addresses of the occluders' z_occ, z_own and point_flag (0 before the first freeze).  drop != 0 waits
+ * for the stream and drops the captured graph: the next such fit captures a fresh one (about 1 ms).
+ * silhouette.refine_fit_occluded does so before every sweep after the first: a default-length fit that replays a graph
+ * captured before the frozen data changed has been measured not to be reproducible from ctx to ctx,
+ * a fit on a graph of its own is. */
+int mvfit_round_graph_info(mvfit_ctx* ctx, int drop, uint64_t* out4);
+
 /* ---- Vertex-target term: squared distance of a problem's vertices to weighted target vertex sets ----
  * The frozen form of every "stay close to these bodies" energy (temporal smoothing against the neighbouring frames, a
  * registered mesh of another method): problem j has K target vertex sets T_jk [Nv,3] with weights a_jk >= 0.

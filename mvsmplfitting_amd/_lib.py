@@ -79,7 +79,8 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_options_default', 'mvfit_create_ex', 'mvfit_set_options', 'mvfit_get_options', 'mvfit_sdf_info',
            'mvfit_lbfgs_kat', 'mvfit_render_overlay', 'mvfit_render_scene', 'mvfit_scene_sdf_loss', 'mvfit_set_scene_obstacles', 'mvfit_scene_obstacles_read',
            'mvfit_associate_views', 'mvfit_set_silhouettes', 'mvfit_silhouettes_read', 'mvfit_silhouette_loss',
-           'mvfit_set_silhouette_term', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
+           'mvfit_set_silhouette_term', 'mvfit_set_silhouette_occluders', 'mvfit_silhouette_occluders_read',
+           'mvfit_silhouette_hidden', 'mvfit_round_graph_info', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
            'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge']
 
 
@@ -166,6 +167,14 @@ def load(path=None):
     lib.mvfit_silhouette_loss.restype = C.c_int
     lib.mvfit_set_silhouette_term.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
     lib.mvfit_set_silhouette_term.restype = C.c_int
+    lib.mvfit_set_silhouette_occluders.argtypes = [vp, vp, C.c_int, _ip, C.c_float]
+    lib.mvfit_set_silhouette_occluders.restype = C.c_int
+    lib.mvfit_silhouette_occluders_read.argtypes = [vp, vp, vp, vp]
+    lib.mvfit_silhouette_occluders_read.restype = C.c_int
+    lib.mvfit_silhouette_hidden.argtypes = [vp, vp, C.c_int, vp]
+    lib.mvfit_silhouette_hidden.restype = C.c_int
+    lib.mvfit_round_graph_info.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
+    lib.mvfit_round_graph_info.restype = C.c_int
     lib.mvfit_set_vertex_targets.argtypes = [vp, C.c_int, vp, vp]
     lib.mvfit_set_vertex_targets.restype = C.c_int
     lib.mvfit_vertex_target_loss.argtypes = [vp, vp, vp, vp]

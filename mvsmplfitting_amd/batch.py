@@ -40,7 +40,7 @@ from .engine import MvFit, SCENE_PALETTE, stage_weights
 from .init_guess import init_guess_batch, initial_params
 from .scene_fit import refine_scenes
 from .sequence import fit_sequences
-from .silhouette import refine_fit
+from .silhouette import refine_fit, refine_fit_occluded
 from .joint_refine import refine_joint
 from .temporal import smooth_sequences
 
@@ -212,11 +212,13 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scen
     return paths
 
 
-SILHOUETTE_DEFAULTS = dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31)
+SILHOUETTE_DEFAULTS = dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31, occlusion=None)
+OCCLUSION_DEFAULTS = dict(margin=0.02, sweeps=2)
 
 
-def check_silhouettes(silhouettes, is_seq=False, scene_collision=None):
-    """fit_folder's ``silhouettes`` option with the defaults filled in, or ValueError."""
+def check_silhouettes(silhouettes, is_seq=False, scene_collision=None, multi=True):
+    """fit_folder's ``silhouettes`` option with the defaults filled in, or ValueError.  ``occlusion`` (None, or a dict with
+    margin and sweeps; the multi-person path only) comes back with its own defaults filled in."""
     if not isinstance(silhouettes, dict) or 'mask_root' not in silhouettes or 'weight' not in silhouettes:
         raise ValueError("silhouettes: a dict with at least 'mask_root' and 'weight' (the term's coll_loss_weight)")
     unknown = set(silhouettes) - set(SILHOUETTE_DEFAULTS) - {'mask_root', 'weight'}
@@ -231,6 +233,16 @@ def check_silhouettes(silhouettes, is_seq=False, scene_collision=None):
         raise ValueError('silhouettes: downscale and contour_stride must be >= 1')
     if not float(cfg['weight']) > 0.0:
         raise ValueError('silhouettes: weight must be > 0')
+    if cfg['occlusion'] is not None:
+        occ = cfg['occlusion']
+        if not isinstance(occ, dict) or set(occ) - set(OCCLUSION_DEFAULTS):
+            raise ValueError('silhouettes: occlusion: a dict with the keys %s, got %r' % (sorted(OCCLUSION_DEFAULTS), occ))
+        if not multi:
+            raise ValueError('silhouettes: occlusion is between the persons of a frame: it needs persons= a list of ids or \'all\'')
+        occ = dict(OCCLUSION_DEFAULTS, **occ)
+        if not (np.isfinite(float(occ['margin'])) and float(occ['margin']) >= 0.0) or int(occ['sweeps']) < 1:
+            raise ValueError('silhouettes: occlusion: margin must be finite and >= 0, sweeps >= 1')
+        cfg['occlusion'] = occ
     return cfg
 
 
@@ -358,12 +370,19 @@ def load_serial_masks(cfg, serial, cams, frames, problems, rig, num_verts):
 
 def refine_serial_silhouettes(eng, xf, stage, cfg, serial, cams, frames, problems, rig, num_verts):
     """The silhouette refinement of one serial's fitted problems (silhouette.refine_fit, the term inside the engine's fit)
-    against the mask set of load_serial_masks.  Returns (params, report); the engine is left without mask set and term."""
+    against the mask set of load_serial_masks.  With cfg['occlusion'] the persons of a frame are a scene and occlude one
+    another (silhouette.refine_fit_occluded; the report gains its per-sweep counts).  Returns (params, report); the engine is
+    left without mask set, occluders and term."""
     masks, body, per_image, found = load_serial_masks(cfg, serial, cams, frames, problems, rig, num_verts)
     eng.set_silhouettes(masks, body, per_image, contour_stride=int(cfg['contour_stride']))
     try:
-        out, report = refine_fit(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), w_in=float(cfg['w_in']),
-                                 w_out=float(cfg['w_out']), sigma=float(cfg['sigma']))
+        st, kw = dict(stage, coll_loss_weight=float(cfg['weight'])), dict(w_in=float(cfg['w_in']), w_out=float(cfg['w_out']),
+                                                                          sigma=float(cfg['sigma']))
+        if cfg.get('occlusion') is not None:
+            out, report = refine_fit_occluded(eng, xf, st, [int(f) for f, _ in problems], margin=float(cfg['occlusion']['margin']),
+                                              sweeps=int(cfg['occlusion']['sweeps']), **kw)
+        else:
+            out, report = refine_fit(eng, xf, st, **kw)
     finally:
         eng.clear_silhouettes()
     report = dict(report, images=[(int(n), int(v)) for n, v, _ in found], mask_size=tuple(masks.shape[1:]))
@@ -453,7 +472,11 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     missing mask_root / weight, is_seq=True, together with scene_collision (one term slot), or when the mask workspace of
     include/mvfit.h exceeds max_mask_bytes (the message names the smallest downscale that fits).  The serial's result gains
     ``silhouette_report`` (refine_fit's, plus images = [(problem, view)] and mask_size), ``timing`` a 'silhouette' entry, and
-    ``final_loss`` is the refined objective.
+    ``final_loss`` is the refined objective.  ``occlusion=dict(margin=0.02, sweeps=2)`` (the multi-person path only;
+    ValueError with persons=0 or an unknown key) makes the persons of a frame a scene whose bodies occlude one another:
+    the masks are modal, so silhouette.refine_fit_occluded freezes the other persons as occluder depth maps per sweep and the
+    term ignores what they hide; ``silhouette_report`` then carries ``sweeps`` (per sweep the accepted rows and the
+    hidden-vertex and flagged-point counts per image).  Not built: occlusion under ``joint=``.
     temporal: None, or dict(weight=..., sweeps=3) - after the serial's batched fit (or its is_seq chain) every person's track
     over the serial's sorted frame list is smoothed by temporal.smooth_sequences (the vertex-target term inside the engine's
     fit: first-order smoothness of the vertices over consecutive frames) with the last stage's weights plus
@@ -503,7 +526,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         unknown = set(scene_collision) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
         if unknown:
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
-    sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision) if silhouettes is not None else None
+    sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision, multi) if silhouettes is not None else None
     tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
     joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal) if joint is not None else None
     if associate is not None and associate is not False:

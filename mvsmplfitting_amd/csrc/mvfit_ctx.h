@@ -133,6 +133,7 @@ struct mvfit_ctx {
     hipGraphExec_t round_graph = nullptr;
     std::vector<unsigned char> graph_key;
     int graph_rounds = 0;
+    unsigned graph_builds = 0;         // round graphs captured on this ctx so far (mvfit_round_graph_info)
     // SDF interpenetration term (mvfit_set_sdf)
     int sdf_num_faces = 0, sdf_grid = 0;
     int sdf_op_B = 0, sdf_op_F = 0;

@@ -55,8 +55,12 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     if (c->obst.on) { obst.tab = c->obst.tab; obst.box = c->obst.box; obst.phi = c->obst.phi; obst.grid = c->obst.grid; obst.rob = c->obst.rob; }
     // (the silhouette term: mask workspace and contour buffers, the sizes their offsets and grids derive from, the round's
     // buffers and the weights; a re-set of a mask set of the same sizes and contour changes none of them)
-    struct { const void *ws, *cs, *g_verts, *loss, *part; int M, H, W, C, nchunks, stride; float w_in, w_out, sigma; } silk;
+    // (its occluders: the maps' buffer, whether they are set, and the margin; a re-freeze at the same sizes changes none)
+    struct { const void *ws, *cs, *g_verts, *loss, *part, *occ; int M, H, W, C, nchunks, stride, occ_on; float w_in, w_out, sigma, margin; } silk;
     memset(&silk, 0, sizeof(silk));
+    if ((c->silt.on || (c->mix.on && c->mix.silhouette > 0.f)) && c->sil.occ_on) {
+        silk.occ = c->sil.occ.get(); silk.occ_on = 1; silk.margin = c->sil.occ_margin;
+    }
     if (c->silt.on) {
         silk.ws = c->sil.ws.get(); silk.cs = c->sil.cs.get(); silk.g_verts = c->silt.g_verts; silk.loss = c->silt.loss; silk.part = c->silt.part;
         silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
@@ -128,6 +132,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     if (e != hipSuccess) { c->round_graph = nullptr; return fail(c, MVFIT_E_HIP, "round graph: %s", hipGetErrorString(e)); }
     c->graph_key = key;
     c->graph_rounds = kGraphRounds;
+    ++c->graph_builds;
     return MVFIT_OK;
 }
 
@@ -465,6 +470,23 @@ extern "C" int mvfit_debug_capture_pass(mvfit_ctx* c, int round, float* verts) {
     if (!c) return MVFIT_E_ARG;
     c->capture_round = verts ? round : -1;
     c->capture_verts = verts;
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_round_graph_info(mvfit_ctx* c, int drop, uint64_t* out4) {
+    if (!c) return MVFIT_E_ARG;
+    if (drop) {
+        HIP_OK(c, hipSetDevice(c->device));
+        HIP_OK(c, hipStreamSynchronize(c->stream));          // (a replay may still run)
+        drop_graph(c);
+    }
+    if (out4) {
+        const unsigned char* oc = c->sil.occ.as<unsigned char>();
+        out4[0] = c->graph_builds;
+        out4[1] = oc ? reinterpret_cast<uintptr_t>(oc + c->sil.o_zocc) : 0;
+        out4[2] = oc ? reinterpret_cast<uintptr_t>(oc + c->sil.o_zown) : 0;
+        out4[3] = oc ? reinterpret_cast<uintptr_t>(oc + c->sil.o_pflag) : 0;
+    }
     return MVFIT_OK;
 }
 

@@ -232,6 +232,7 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
                                      const int32_t* image_body, const float* cam_R, const float* cam_t, const float* cam_f,
                                      const float* cam_c, int contour_stride) {
     if (!c) return MVFIT_E_ARG;
+    c->sil.occ_on = false;                                   // the occluders belong to the mask set: every call clears them
     HIP_OK(c, hipSetDevice(c->device));
     if (num_images == 0) {                                   // clear: the work areas stay for a next set of the same size
         c->sil.on = false;
@@ -338,6 +339,47 @@ extern "C" int mvfit_silhouette_loss(mvfit_ctx* c, const float* vertices, int nu
                     c->sil.body_max, num_bodies);
     HIP_OK(c, hipSetDevice(c->device));
     return sil_loss(c->sil, vertices, num_bodies, w_in, w_out, sigma, loss, g_vertices, winner, c->stream, c->err);
+}
+
+// Occlusion between the bodies of a scene (include/mvfit.h; silhouette_occlusion.hip): the other bodies frozen as depth maps per
+// mask image.  State of the mask set: the evaluation entries and the rounds read it (silhouette.hip: sil_loss / sil_round).
+extern "C" int mvfit_set_silhouette_occluders(mvfit_ctx* c, const float* vertices, int num_bodies, const int32_t* body_scene,
+                                              float margin) {
+    if (!c) return MVFIT_E_ARG;
+    c->sil.occ_on = false;                                   // a failed freeze leaves none set
+    if (num_bodies == 0 || !vertices) return MVFIT_OK;       // clear: the buffers stay for the next freeze
+    if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_occluders: no mask set is present (mvfit_set_silhouettes)");
+    if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_occluders: the model was created without (valid) faces");
+    if (!body_scene) return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_occluders: null body_scene");
+    if (num_bodies < 1 || num_bodies > 65535)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_occluders: num_bodies %d outside [1, 65535]", num_bodies);
+    if (c->sil.body_min < 0 || c->sil.body_max >= num_bodies)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_occluders: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min,
+                    c->sil.body_max, num_bodies);
+    if (!std::isfinite(margin) || margin < 0.f)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_silhouette_occluders: margin = %g must be finite and >= 0", (double)margin);
+    HIP_OK(c, hipSetDevice(c->device));
+    return sil_occ_set(c->sil, vertices, num_bodies, body_scene, margin, c->d_faces, c->num_faces, c->stream, c->err);
+}
+
+extern "C" int mvfit_silhouette_occluders_read(mvfit_ctx* c, float* z_occ, float* z_own, uint8_t* point_flag) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->sil.on || !c->sil.occ_on) return fail(c, MVFIT_E_STATE, "mvfit_silhouette_occluders_read: no occluders are set");
+    HIP_OK(c, hipSetDevice(c->device));
+    return sil_occ_read(c->sil, z_occ, z_own, point_flag, c->stream, c->err);
+}
+
+extern "C" int mvfit_silhouette_hidden(mvfit_ctx* c, const float* vertices, int num_bodies, uint8_t* hidden) {
+    if (!c) return MVFIT_E_ARG;
+    if (!c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_silhouette_hidden: no mask set is present (mvfit_set_silhouettes)");
+    if (!vertices || !hidden) return fail(c, MVFIT_E_ARG, "mvfit_silhouette_hidden: null %s", !vertices ? "vertices" : "hidden");
+    if (num_bodies < 1 || num_bodies > 65535)
+        return fail(c, MVFIT_E_ARG, "mvfit_silhouette_hidden: num_bodies %d outside [1, 65535]", num_bodies);
+    if (c->sil.body_min < 0 || c->sil.body_max >= num_bodies)
+        return fail(c, MVFIT_E_ARG, "mvfit_silhouette_hidden: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min,
+                    c->sil.body_max, num_bodies);
+    HIP_OK(c, hipSetDevice(c->device));
+    return sil_occ_hidden(c->sil, vertices, hidden, c->stream, c->err);
 }
 
 // The vertex-target set (include/mvfit.h; vertex_target.hip).  The set's three buffers are re-made only when K changes (B

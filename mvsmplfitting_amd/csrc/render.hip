@@ -27,20 +27,12 @@
 
 #pragma clang fp contract(off)
 
+#include "render_raster.h"      // vertex records, edge functions, face setup, the depth of a sample: shared with the silhouette term's occluder maps
+
 namespace mvfit {
 
 constexpr int RD_NT = 256;
-constexpr float RD_ZNEAR = 0.05f, RD_ZFAR = 8000.f;
-constexpr float RD_GUARD = 16384.f;                // a vertex further than this outside the image drops its triangle
 constexpr unsigned long long RD_EMPTY = ~0ull;
-constexpr long long RD_BIG_BOX = 1024;             // pixel boxes larger than this are walked by a whole workgroup
-constexpr int RD_BIG_BLOCKS = 256;                 // workgroups per image of render_raster_big_kernel
-
-struct RenderVert {            // per (image, vertex)
-    int X, Y;                  // rintf(u * 256), rintf(v * 256)
-    float pz;
-    int ok;                    // pz > znear and inside the guard band
-};
 
 struct RenderImage {           // per image: the nine lights (camera space)
     double L[9][3];
@@ -139,7 +131,7 @@ __device__ inline void transform_body(const RenderCam& c, const float* __restric
         cam_point(c, P[i * 3 + 0], P[i * 3 + 1], P[i * 3 + 2], px, py, pz);
         const float u = c.f * (px / pz) + c.cx;
         const float w = c.f * (py / pz) + c.cy;
-        RenderVert rv;
+        RenderVert rv;                                          // (render_raster.h: snap_vertex states the same record)
         rv.ok = (pz > RD_ZNEAR) && (u >= -RD_GUARD) && (u <= (float)W + RD_GUARD) && (w >= -RD_GUARD) && (w <= (float)H + RD_GUARD);
         rv.X = rv.ok ? (int)rintf(u * 256.f) : 0;
         rv.Y = rv.ok ? (int)rintf(w * 256.f) : 0;
@@ -180,41 +172,10 @@ __global__ __launch_bounds__(RD_NT) void render_transform_kernel(DevProblems Q, 
     }
 }
 
-__device__ inline long long edge_fn(int xa, int ya, int xb, int yb, long long sx, long long sy) {
-    return (long long)(xb - xa) * (sy - ya) - (long long)(yb - ya) * (sx - xa);
-}
-
-struct FaceSetup {             // a face's snapped vertices, orientation, pixel box and 1/z
-    RenderVert v0, v1, v2;
-    long long sgn, area;
-    int x0, x1, y0, y1;
-    double iz0, iz1, iz2;
-};
-
-// false: the face draws nothing (a vertex dropped, zero area, or its box misses the image)
-__device__ inline bool face_setup(const RenderVert* V, const int32_t* faces, int f, int H, int W, FaceSetup& s) {
-    s.v0 = V[faces[f * 3 + 0]]; s.v1 = V[faces[f * 3 + 1]]; s.v2 = V[faces[f * 3 + 2]];
-    if (!(s.v0.ok && s.v1.ok && s.v2.ok)) return false;
-    const long long area = edge_fn(s.v0.X, s.v0.Y, s.v1.X, s.v1.Y, s.v2.X, s.v2.Y);
-    if (area == 0) return false;
-    s.sgn = area > 0 ? 1 : -1;
-    s.area = area * s.sgn;
-    const int minX = min(s.v0.X, min(s.v1.X, s.v2.X)), maxX = max(s.v0.X, max(s.v1.X, s.v2.X));
-    const int minY = min(s.v0.Y, min(s.v1.Y, s.v2.Y)), maxY = max(s.v0.Y, max(s.v1.Y, s.v2.Y));
-    // pixel x is sampled at 256 x + 128: the columns whose centre lies in [minX, maxX] (arithmetic shifts = floor division)
-    s.x0 = max(0, (minX - 128 + 255) >> 8); s.x1 = min(W - 1, (maxX - 128) >> 8);
-    s.y0 = max(0, (minY - 128 + 255) >> 8); s.y1 = min(H - 1, (maxY - 128) >> 8);
-    if (s.x0 > s.x1 || s.y0 > s.y1) return false;
-    s.iz0 = 1.0 / (double)s.v0.pz; s.iz1 = 1.0 / (double)s.v1.pz; s.iz2 = 1.0 / (double)s.v2.pz;
-    return true;
-}
-
 // one covered-or-not sample: e0 = edge v1->v2 (opposite v0), e1 = v2->v0, e2 = v0->v1, already oriented
 __device__ inline void raster_sample(const FaceSetup& s, int f, long long e0, long long e1, long long e2, unsigned long long* px) {
-    if ((e0 | e1 | e2) < 0) return;
-    const double w = ((double)e0 * s.iz0 + (double)e1 * s.iz1) + (double)e2 * s.iz2;
-    const float z = (float)((double)s.area / w);
-    if (!(z >= RD_ZNEAR && z <= RD_ZFAR)) return;
+    float z;
+    if (!raster_depth(s, e0, e1, e2, z)) return;
     atomicMin(px, ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)f);
 }
 

@@ -22,6 +22,8 @@
 // No float atomics; nothing a body gets depends on the other bodies of the call or on its position in it.
 // Inside the fit (mvfit_set_silhouette_term): sil_round launches the <GATED = true> instantiations of the three evaluation
 // kernels on the stream a chained round is captured on; they skip the bodies whose gate word is 0.
+// With occluders set (mvfit_set_silhouette_occluders, silhouette_occlusion.hip) the <., OCC = true> instantiations of the search
+// and the vertex kernel run: hidden vertices and flagged contour points drop out of both terms.
 #include "silhouette.h"
 
 #include <algorithm>
@@ -29,39 +31,22 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "mvfit.h"
+#include "silhouette_device.h"
 #include "wave_ops.h"
 
 namespace mvfit {
 
-constexpr int SIL_NT = 256;
 constexpr int SIL_PPT = 2;                       // contour points per thread of the search
 constexpr int SIL_CHUNK = SIL_NT * SIL_PPT;      // contour points per workgroup
 constexpr int SIL_VT = 3456;                     // vertices per LDS tile: 27 KB, five workgroups per CU
 constexpr int SIL_INF = 0x3fffffff;              // "no on pixel in this column": above every real d2 (< 2^28), sums stay in int32
 constexpr int SIL_FAR = 1 << 20;
-constexpr float SIL_ZNEAR = 0.05f;
 constexpr double SIL_FIX = 268435456.0;          // 2^28: fixed-point unit of term B's gradient accumulators (pixels)
 
-struct SilCam { float R[9], t[3], f, cx, cy, pad; };
-static_assert(sizeof(SilCam) == 64, "table row");
-struct SilChunk { int image, first, count, pad; };
-static_assert(sizeof(SilChunk) == 16, "table row");
-
 #pragma clang fp contract(off)
-
-// the rasteriser's fp32 sequence (render.hip: cam_point), no contraction
-__device__ __forceinline__ bool sil_project(const SilCam& c, const float* __restrict__ p, float& px, float& py, float& pz,
-                                            float& u, float& w) {
-    const float X = p[0], Y = p[1], Z = p[2];
-    px = ((c.R[0] * X + c.R[1] * Y) + c.R[2] * Z) + c.t[0];
-    py = ((c.R[3] * X + c.R[4] * Y) + c.R[5] * Z) + c.t[1];
-    pz = ((c.R[6] * X + c.R[7] * Y) + c.R[8] * Z) + c.t[2];
-    u = c.f * (px / pz) + c.cx;
-    w = c.f * (py / pz) + c.cy;
-    return pz > SIL_ZNEAR;
-}
 
 // ------------------------------------------------------------------------------------------------ distance transform
 // grid (ceil(W / SIL_NT), M): a thread per column.  g2 = squared distance to the nearest on pixel of the column (SIL_INF:
@@ -176,22 +161,28 @@ template <> struct SilGate<true> {
     __device__ __forceinline__ bool off(int body) const { return gate && !gate[body]; }
 };
 
+// What the search and the vertex kernel take beside their data: the gate and the occluders in one argument, so that the
+// instantiations without occluders have the argument list - and with it the code - they had before occluders existed.
+template <bool GATED, bool OCC> struct SilPolicy : SilGate<GATED>, SilOcc<OCC> {};
+
 // ------------------------------------------------------------------------------------------------ term B: the search
 // grid (chunks): SIL_CHUNK contour points of one image against all vertices of its body.
 // acc[(image * nv + j) * 2 + {0, 1}] += round(2^28 * stride * rho_B'(m) * 2 (dx, dy)); partB[chunk] = sum of rho_B.
-template <bool GATED>
+// OCC (occluders are set, silhouette_device.h: SilOcc): a hidden vertex is NaN in the tile like an invalid one, a flagged
+// point contributes nothing and reports winner -2.
+template <bool GATED, bool OCC>
 __global__ __launch_bounds__(SIL_NT) void sil_search_kernel(const float* __restrict__ verts, int nv, const SilCam* __restrict__ cams,
                                                             const int* __restrict__ image_body,
                                                             const SilChunk* __restrict__ chunks, const int2* __restrict__ xy,
                                                             float sigma, int stride, unsigned long long* __restrict__ acc,
                                                             double* __restrict__ partB, int* __restrict__ winner,
-                                                            SilGate<GATED> gate) {
+                                                            SilPolicy<GATED, OCC> pol) {
     __shared__ __attribute__((aligned(16))) float2 sh_uv[SIL_VT];
     __shared__ double sh_d[SIL_NT / 64];
     static_assert(SIL_VT % 2 == 0, "two vertices per read");
     const int tid = threadIdx.x;
     const SilChunk ch = chunks[blockIdx.x];
-    if (GATED && gate.off(image_body[ch.image])) return;          // (uniform)
+    if (GATED && pol.off(image_body[ch.image])) return;           // (uniform)
     const SilCam cam = cams[ch.image];
     const float* vb = verts + (size_t)image_body[ch.image] * nv * 3;
     float cx[SIL_PPT], cy[SIL_PPT];
@@ -211,7 +202,8 @@ __global__ __launch_bounds__(SIL_NT) void sil_search_kernel(const float* __restr
         __syncthreads();
         for (int j = tid; j < n; j += SIL_NT) {
             float px, py, pz, u, w;
-            const bool ok = sil_project(cam, vb + (size_t)(v0 + j) * 3, px, py, pz, u, w);
+            bool ok = sil_project(cam, vb + (size_t)(v0 + j) * 3, px, py, pz, u, w);
+            if (OCC && ok && pol.hidden(ch.image, u, w, pz)) ok = false;
             sh_uv[j] = ok ? make_float2(u, w) : make_float2(qnan, qnan);
         }
         if (tid == 0 && (n & 1)) sh_uv[n] = make_float2(qnan, qnan);       // n odd => n < SIL_VT
@@ -235,6 +227,10 @@ __global__ __launch_bounds__(SIL_NT) void sil_search_kernel(const float* __restr
     for (int p = 0; p < SIL_PPT; ++p) {
         const int k = tid + p * SIL_NT;
         if (k >= ch.count) continue;
+        if (OCC && pol.flagged((size_t)ch.first + k)) {
+            if (winner) winner[(size_t)ch.first + k] = -2;
+            continue;
+        }
         if (winner) winner[(size_t)ch.first + k] = bj[p];
         if (bj[p] < 0) continue;
         float px, py, pz, u, w;
@@ -278,17 +274,18 @@ __device__ __forceinline__ int sil_lower_bound(const int* __restrict__ sbody, in
 }
 
 // grid (ceil(nv / SIL_NT), N): thread = (body n, vertex j).  sbody / simg: the images sorted by (body, image).
-// partA[i * gridDim.x + blockIdx.x] = the workgroup's sum of rho_A in image i.
-template <bool GATED>
+// partA[i * gridDim.x + blockIdx.x] = the workgroup's sum of rho_A in image i.  OCC: a vertex hidden in image i gets
+// nothing from it, like an invalid one.
+template <bool GATED, bool OCC>
 __global__ __launch_bounds__(SIL_NT) void sil_vertex_kernel(const float* __restrict__ verts, int nv, const SilCam* __restrict__ cams,
                                                             const int* __restrict__ sbody, const int* __restrict__ simg, int M,
                                                             const float* __restrict__ field, int H, int W,
                                                             const int* __restrict__ flags, float w_in, float w_out, float sigma,
                                                             const long long* __restrict__ acc, float* __restrict__ g_verts,
-                                                            double* __restrict__ partA, SilGate<GATED> gate) {
+                                                            double* __restrict__ partA, SilPolicy<GATED, OCC> pol) {
     __shared__ double sh_d[SIL_NT / 64];
     const int n = blockIdx.y, tid = threadIdx.x, j = blockIdx.x * SIL_NT + tid;
-    if (GATED && gate.off(n)) return;                               // (uniform)
+    if (GATED && pol.off(n)) return;                                // (uniform)
     const bool live = j < nv;
     const float* pv = verts + ((size_t)n * nv + (live ? j : 0)) * 3;
     double g[3] = {0.0, 0.0, 0.0};
@@ -299,7 +296,7 @@ __global__ __launch_bounds__(SIL_NT) void sil_vertex_kernel(const float* __restr
         if (live && flags[i]) {
             const SilCam cam = cams[i];
             float px, py, pz, u, w;
-            if (sil_project(cam, pv, px, py, pz, u, w)) {
+            if (sil_project(cam, pv, px, py, pz, u, w) && !(OCC && pol.hidden(i, u, w, pz))) {
                 const float x = u - 0.5f, y = w - 0.5f;
                 const float xc = fminf(fmaxf(x, 0.f), (float)(W - 1)), yc = fminf(fmaxf(y, 0.f), (float)(H - 1));
                 const int x0 = min((int)floorf(xc), W - 2), y0 = min((int)floorf(yc), H - 2);
@@ -395,6 +392,7 @@ static size_t sil_al(size_t x) { return (x + 255) & ~(size_t)255; }
 int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, const int32_t* image_body, const float* cam_R,
             const float* cam_t, const float* cam_f, const float* cam_c, int stride, hipStream_t stream, std::string& err) {
     S.on = false;                                // a failed set leaves no mask set behind
+    S.occ_on = false;                            // the occluders belong to the mask set: every set clears them
     const int nblk = (nv + SIL_NT - 1) / SIL_NT;
     const size_t npix = (size_t)M * H * W;
     size_t o = 0;
@@ -418,6 +416,7 @@ int sil_set(SilState& S, int nv, int M, int H, int W, const uint8_t* masks, cons
     for (int i = 0; i < M; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return image_body[a] < image_body[b]; });
     S.body_min = INT_MAX; S.body_max = INT_MIN;
+    S.h_body.assign(image_body, image_body + M);
     for (int i = 0; i < M; ++i) { S.body_min = std::min(S.body_min, image_body[i]); S.body_max = std::max(S.body_max, image_body[i]); }
     const size_t tab_bytes = o_first - o_cam;
     S.h_tab.assign(tab_bytes / 4, 0);
@@ -494,29 +493,48 @@ int sil_read(const SilState& S, float* field, int32_t* contour_first, int32_t* c
     return MVFIT_OK;
 }
 
-int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, float* loss,
-             float* g_vertices, int32_t* winner, hipStream_t stream, std::string& err) {
+static SilGate<false> sil_gate(std::false_type, const int*) { return {}; }
+static SilGate<true> sil_gate(std::true_type, const int* gate) { return SilGate<true>{gate}; }
+static SilOcc<false> sil_occ(std::false_type, const SilState&) { return {}; }
+static SilOcc<true> sil_occ(std::true_type, const SilState& S) {
+    const unsigned char* oc = S.occ.as<unsigned char>();
+    return SilOcc<true>{reinterpret_cast<const float*>(oc + S.o_zocc), oc + S.o_pflag, S.H, S.W, S.occ_margin};
+}
+
+// search -> vertex kernel -> loss kernel of one evaluation; acc: the zeroed fixed-point accumulators, or null (loss only)
+template <bool GATED, bool OCC>
+static void sil_launch(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, const int* gate,
+                       unsigned long long* acc, float* loss, float* g_vertices, int32_t* winner, hipStream_t stream) {
     const int nv = S.nv, nblk = (nv + SIL_NT - 1) / SIL_NT;
     unsigned char *ws = S.ws.as<unsigned char>(), *cs = S.cs.as<unsigned char>();
     const SilCam* cams = reinterpret_cast<const SilCam*>(ws + S.o_cam);
     const int* sbody = reinterpret_cast<const int*>(ws + S.o_sbody);
     const int* simg = reinterpret_cast<const int*>(ws + S.o_simg);
-    const bool accumulate = g_vertices && S.nchunks;
-    unsigned long long* acc = accumulate ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
-    if (accumulate) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * nv * 16, stream));
+    const SilGate<GATED> g = sil_gate(std::integral_constant<bool, GATED>{}, gate);
+    const SilPolicy<GATED, OCC> pol{g, sil_occ(std::integral_constant<bool, OCC>{}, S)};
     if (S.nchunks)
-        hipLaunchKernelGGL(sil_search_kernel<false>, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
+        hipLaunchKernelGGL((sil_search_kernel<GATED, OCC>), dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
                            reinterpret_cast<const int*>(ws + S.o_body), reinterpret_cast<const SilChunk*>(cs + S.o_chunk),
                            reinterpret_cast<const int2*>(cs + S.o_xy), sigma, S.stride, acc,
-                           reinterpret_cast<double*>(cs + S.o_partB), winner, SilGate<false>{});
-    hipLaunchKernelGGL(sil_vertex_kernel<false>, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg, S.M,
-                       reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(ws + S.o_flags),
-                       w_in, w_out, sigma, reinterpret_cast<const long long*>(acc), g_vertices,
-                       reinterpret_cast<double*>(ws + S.o_partA), SilGate<false>{});
-    hipLaunchKernelGGL(sil_loss_kernel<false>, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
+                           reinterpret_cast<double*>(cs + S.o_partB), winner, pol);
+    hipLaunchKernelGGL((sil_vertex_kernel<GATED, OCC>), dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody,
+                       simg, S.M, reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W,
+                       reinterpret_cast<const int*>(ws + S.o_flags), w_in, w_out, sigma, reinterpret_cast<const long long*>(acc),
+                       g_vertices, reinterpret_cast<double*>(ws + S.o_partA), pol);
+    hipLaunchKernelGGL(sil_loss_kernel<GATED>, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
                        reinterpret_cast<const double*>(ws + S.o_partA), nblk,
                        reinterpret_cast<const double*>(cs + S.o_partB), reinterpret_cast<const int*>(ws + S.o_cfirst), w_in,
-                       w_out, S.stride, loss, SilGate<false>{});
+                       w_out, S.stride, loss, g);
+}
+
+// with occluders set (mvfit_set_silhouette_occluders) the <., OCC = true> instantiations run, otherwise the kernels as they were
+int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, float* loss,
+             float* g_vertices, int32_t* winner, hipStream_t stream, std::string& err) {
+    const bool accumulate = g_vertices && S.nchunks;
+    unsigned long long* acc = accumulate ? reinterpret_cast<unsigned long long*>(S.ws.as<unsigned char>() + S.o_acc) : nullptr;
+    if (accumulate) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * S.nv * 16, stream));
+    if (S.occ_on) sil_launch<false, true>(S, vertices, num_bodies, w_in, w_out, sigma, nullptr, acc, loss, g_vertices, winner, stream);
+    else sil_launch<false, false>(S, vertices, num_bodies, w_in, w_out, sigma, nullptr, acc, loss, g_vertices, winner, stream);
     SIL_HIP(hipGetLastError());
     return MVFIT_OK;
 }
@@ -525,26 +543,10 @@ int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, flo
 // gradient; no host work, so a stream capture records it as it is (one memset node and three kernel nodes).
 int sil_round(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, const int* gate,
               float* loss, float* g_vertices, hipStream_t stream, std::string& err) {
-    const int nv = S.nv, nblk = (nv + SIL_NT - 1) / SIL_NT;
-    unsigned char *ws = S.ws.as<unsigned char>(), *cs = S.cs.as<unsigned char>();
-    const SilCam* cams = reinterpret_cast<const SilCam*>(ws + S.o_cam);
-    const int* sbody = reinterpret_cast<const int*>(ws + S.o_sbody);
-    const int* simg = reinterpret_cast<const int*>(ws + S.o_simg);
-    unsigned long long* acc = S.nchunks ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
-    if (acc) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * nv * 16, stream));
-    if (S.nchunks)
-        hipLaunchKernelGGL(sil_search_kernel<true>, dim3(S.nchunks), dim3(SIL_NT), 0, stream, vertices, nv, cams,
-                           reinterpret_cast<const int*>(ws + S.o_body), reinterpret_cast<const SilChunk*>(cs + S.o_chunk),
-                           reinterpret_cast<const int2*>(cs + S.o_xy), sigma, S.stride, acc,
-                           reinterpret_cast<double*>(cs + S.o_partB), (int*)nullptr, SilGate<true>{gate});
-    hipLaunchKernelGGL(sil_vertex_kernel<true>, dim3(nblk, num_bodies), dim3(SIL_NT), 0, stream, vertices, nv, cams, sbody, simg,
-                       S.M, reinterpret_cast<const float*>(ws + S.o_field), S.H, S.W, reinterpret_cast<const int*>(ws + S.o_flags),
-                       w_in, w_out, sigma, reinterpret_cast<const long long*>(acc), g_vertices,
-                       reinterpret_cast<double*>(ws + S.o_partA), SilGate<true>{gate});
-    hipLaunchKernelGGL(sil_loss_kernel<true>, dim3(num_bodies), dim3(64), 0, stream, sbody, simg, S.M,
-                       reinterpret_cast<const double*>(ws + S.o_partA), nblk,
-                       reinterpret_cast<const double*>(cs + S.o_partB), reinterpret_cast<const int*>(ws + S.o_cfirst), w_in,
-                       w_out, S.stride, loss, SilGate<true>{gate});
+    unsigned long long* acc = S.nchunks ? reinterpret_cast<unsigned long long*>(S.ws.as<unsigned char>() + S.o_acc) : nullptr;
+    if (acc) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * S.nv * 16, stream));
+    if (S.occ_on) sil_launch<true, true>(S, vertices, num_bodies, w_in, w_out, sigma, gate, acc, loss, g_vertices, nullptr, stream);
+    else sil_launch<true, false>(S, vertices, num_bodies, w_in, w_out, sigma, gate, acc, loss, g_vertices, nullptr, stream);
     SIL_HIP(hipGetLastError());
     return MVFIT_OK;
 }

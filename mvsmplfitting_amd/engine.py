@@ -510,6 +510,56 @@ class MvFit:
             return loss, g, win[:int(n.value)]
         return loss, g
 
+    # -------------------------------------------- occlusion between bodies (include/mvfit.h:mvfit_set_silhouette_occluders)
+    def set_silhouette_occluders(self, vertices, body_scene, margin=0.02):
+        """Freeze the other bodies of every scene as occluder depth maps per mask image (include/mvfit.h:
+        mvfit_set_silhouette_occluders): vertices [N,Nv,3], body_scene [N] int (bodies with the same value >= 0 occlude one
+        another in each other's images; < 0: no occluders), margin in the cameras' depth unit.  While they are set,
+        silhouette_loss, closure and fit ignore what the maps hide.  They go with the mask set: every set_silhouettes or
+        clear_silhouettes removes them."""
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [N, %d, 3], got %r' % (self.nv, tuple(v.shape)))
+        scene = _i32(np.asarray(body_scene).reshape(-1))
+        if scene.size != int(v.shape[0]):
+            raise MvFitError('body_scene needs one entry per body (%d), got %d' % (int(v.shape[0]), scene.size))
+        self._check(self._lib.mvfit_set_silhouette_occluders(self._ctx, v.data_ptr(), int(v.shape[0]),
+                                                             scene.ctypes.data_as(_lib._ip), float(margin)))
+
+    def clear_silhouette_occluders(self):
+        """Remove the occluders of set_silhouette_occluders (the mask set stays)."""
+        self._check(self._lib.mvfit_set_silhouette_occluders(self._ctx, None, 0, None, 0.0))
+
+    def silhouette_occluders(self):
+        """Diagnostics: (z_occ [M,H,W] float32, z_own [M,H,W] float32, point_flag [C] uint8) of the frozen occluders; +inf
+        where nothing covers the pixel sample."""
+        n = C.c_int32(0)
+        self._check(self._lib.mvfit_silhouettes_read(self._ctx, None, None, None, C.byref(n)))
+        M, H, W = self._sil_shape
+        z_occ = torch.empty(M, H, W, device=self.device)
+        z_own = torch.empty(M, H, W, device=self.device)
+        flag = torch.empty(max(int(n.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self._lib.mvfit_silhouette_occluders_read(self._ctx, z_occ.data_ptr(), z_own.data_ptr(), flag.data_ptr()))
+        return z_occ, z_own, flag[:int(n.value)]
+
+    def silhouette_hidden(self, vertices):
+        """uint8 [M,Nv]: 1 where vertex j of the image's body, at vertices [N,Nv,3], is valid and hidden by the image's
+        occluders (include/mvfit.h:mvfit_silhouette_hidden); zeros without occluders."""
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [N, %d, 3], got %r' % (self.nv, tuple(v.shape)))
+        hidden = torch.empty(self._sil_shape[0], self.nv, dtype=torch.uint8, device=self.device)
+        self._check(self._lib.mvfit_silhouette_hidden(self._ctx, v.data_ptr(), int(v.shape[0]), hidden.data_ptr()))
+        return hidden
+
+    def round_graph_info(self, drop=False):
+        """dict(builds = round graphs captured on this engine so far, occluder_buffers = the device addresses of z_occ, z_own
+        and point_flag, 0 before the first freeze) (include/mvfit.h:mvfit_round_graph_info).  drop=True drops the captured
+        graph first: the next fit with chained rounds captures a fresh one."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.mvfit_round_graph_info(self._ctx, 1 if drop else 0, out))
+        return dict(builds=int(out[0]), occluder_buffers=(int(out[1]), int(out[2]), int(out[3])))
+
     def set_vertex_targets(self, targets, weights):
         """Target vertex sets of the vertex-target term (include/mvfit.h:mvfit_set_vertex_targets): targets [B,K,Nv,3]
         (tensor or array; copied), weights [B,K] finite and >= 0, 1 <= K <= 4.  A row whose weight is 0 is never read and may

@@ -18,8 +18,12 @@ backward scales it by each body's incoming gradient.  Once differentiable: there
 refine_fit runs the term inside the engine's own fit instead (include/mvfit.h:mvfit_set_silhouette_term): every parameter
 the stage frees moves, the optimiser is the project's L-BFGS and no closure leaves the device.
 
-Not built here: instance masks shared between persons, visibility or occlusion between bodies, point-to-edge distances (the contour term measures the distance to the
-nearest projected *vertex*; its floor is about half the projected vertex spacing).
+refine_fit_occluded is refine_fit for persons that overlap in a view: the other bodies of a scene are frozen as occluder
+depth maps (include/mvfit.h:mvfit_set_silhouette_occluders), and the term ignores the vertices and contour points they hide.
+
+Not built here: label images shared between persons, a body's self-occlusion (its own mask already covers it), the joint=
+folder plumbing and the service / single-launch form of the occluders, point-to-edge distances (the contour term measures the
+distance to the nearest projected *vertex*; its floor is about half the projected vertex spacing).
 """
 from __future__ import annotations
 
@@ -246,3 +250,52 @@ def refine_fit(engine, params, stage, *, w_in=1.0, w_out=1.0, sigma=0.0, **fit_k
     finally:
         engine.clear_silhouette_term()
 
+
+
+def refine_fit_occluded(engine, params, stage, body_scene, *, margin=0.02, sweeps=2, **refine_fit_kwargs):
+    """refine_fit for scenes whose persons overlap in a view: the masks are modal (a person's mask shows its visible part
+    only), so the other bodies of each scene are frozen as occluder depth maps (include/mvfit.h:
+    mvfit_set_silhouette_occluders) and the term ignores what they hide.
+
+    params [B,118], ``body_scene`` [B] int: problems with the same value >= 0 occlude one another, < 0 none.  Per sweep:
+
+      1. the occluders are frozen at the current rows' vertices (engine.vertices); after the first sweep the captured round
+         graph is dropped, so that every sweep's fit runs on a graph of its own;
+      2. refine_fit runs - it accepts per problem and judges before and after under the same frozen maps;
+      3. a sweep that accepts nothing ends the loop.
+
+    The engine is left without occluders (also when something raises); the mask set stays.  Returns (params, report):
+    report holds the last sweep's refine_fit report (before, after, accepted, silhouette_before, silhouette_after,
+    n_closure, loss - of the rows returned) and ``sweeps``: per sweep dict(accepted [B] bool, hidden [M] = hidden vertices
+    per image at the frozen vertices, flagged [M] = flagged contour points per image)."""
+    if int(sweeps) < 1:
+        raise ValueError('refine_fit_occluded: sweeps must be >= 1')
+    scene = np.asarray(body_scene).reshape(-1).astype(np.int32)
+    x = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, np.float32))
+    x = x.to(engine.device).clone()
+    if scene.size != int(x.shape[0]):
+        raise ValueError('refine_fit_occluded: body_scene needs one entry per problem (%d), got %d' % (int(x.shape[0]), scene.size))
+
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+    report, done = None, []
+    try:
+        for sweep in range(int(sweeps)):
+            verts = engine.vertices(x)[0]
+            engine.set_silhouette_occluders(verts, scene, margin=margin)
+            if sweep:
+                # the freeze keeps the round graph valid, but a long fit that replays a graph captured before the maps changed
+                # is not reproducible from engine to engine (DESIGN.md section 7): every later sweep captures its own
+                engine.round_graph_info(drop=True)
+            first = host(engine.silhouettes()[1]).astype(np.int64)
+            flag = host(engine.silhouette_occluders()[2]).astype(np.int64)
+            csum = np.concatenate([[0], np.cumsum(flag)])
+            hidden = host(engine.silhouette_hidden(verts)).astype(np.int64).sum(axis=1)
+            x, report = refine_fit(engine, x, stage, **refine_fit_kwargs)
+            done.append(dict(accepted=np.asarray(report['accepted']).copy(), hidden=hidden, flagged=csum[first[1:]] - csum[first[:-1]]))
+            if not np.asarray(report['accepted']).any():
+                break
+        return x, dict(report, sweeps=done)
+    finally:
+        engine.clear_silhouette_occluders()
