@@ -95,6 +95,32 @@ FitPlanIn mvfit::plan_inputs(const mvfit_ctx* c) {
     return in;
 }
 
+// what the plan of a round's term (round_term.h) depends on in this ctx
+TermInputs mvfit::term_inputs(const mvfit_ctx* c) {
+    TermInputs in;
+    in.B = c->B; in.Bpad = c->Bpad; in.nv = c->nv;
+    in.sdf_faces = c->sdf_faces.as<int32_t>(); in.sdf_num_faces = c->sdf_num_faces; in.sdf_grid = c->sdf_grid; in.sdf_cull = c->sdf_cull.get();
+    in.sdf_box = c->pb.sdf_box; in.sdf_samp = c->pb.sdf_samp; in.sdf_entries = c->pb.sdf_entries; in.sdf_adj = c->pb.sdf_adj;
+    const Obstacles& ob = c->obst;
+    in.obst.on = ob.on; in.obst.tab = ob.tab; in.obst.box = ob.box; in.obst.phi = ob.phi; in.obst.grid = ob.grid; in.obst.rob = ob.rob;
+    const SilState& S = c->sil;
+    in.sil.on = S.on; in.sil.ws = S.ws.get(); in.sil.cs = S.cs.get();
+    in.sil.M = S.M; in.sil.H = S.H; in.sil.W = S.W; in.sil.C = S.C; in.sil.nchunks = S.nchunks; in.sil.stride = S.stride;
+    in.sil.occ = S.occ.get(); in.sil.occ_on = S.occ_on; in.sil.occ_margin = S.occ_margin;
+    const SilTerm& st = c->silt;
+    in.silt.on = st.on; in.silt.w_in = st.w_in; in.silt.w_out = st.w_out; in.silt.sigma = st.sigma;
+    in.silt.g_verts = st.g_verts; in.silt.loss = st.loss; in.silt.part = st.part;
+    const VtxTargets& T = c->vt;
+    in.vt.on = T.on; in.vt.term = T.term; in.vt.K = T.K; in.vt.targets = T.targets; in.vt.weights = T.weights; in.vt.partial = T.partial;
+    in.vt.g_verts = T.g_verts; in.vt.loss = T.loss; in.vt.part = T.part;
+    const TermMix& X = c->mix;
+    in.mix.on = X.on; in.mix.scene = X.scene; in.mix.silhouette = X.silhouette; in.mix.vertex_targets = X.vertex_targets;
+    in.mix.w_in = X.w_in; in.mix.w_out = X.w_out; in.mix.sigma = X.sigma;
+    in.mix.g_verts = X.g_verts; in.mix.loss = X.loss; in.mix.part = X.part; in.mix.rec_scene = X.rec_scene; in.mix.rec_verts = X.rec_verts;
+    in.mix.parts = X.parts; in.mix.sums = X.sums;
+    return in;
+}
+
 extern "C" void mvfit_options_default(mvfit_options* o) {
     if (!o) return;
     memset(o, 0, sizeof(*o));
@@ -358,20 +384,15 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
 extern "C" int mvfit_sdf_term_read(mvfit_ctx* c, float* samples, float* sums) {
     if (!c) return MVFIT_E_ARG;
     if (!c->pb.sdf_adj) return fail(c, MVFIT_E_STATE, "no interpenetration term has been evaluated yet");
-    if (samples && round_term(c))
+    const RoundTermPlan plan = plan_round_term(term_inputs(c));    // (where the round leaves the sums comes with the plan)
+    if (samples && plan.kind != TERM_SDF)
         return fail(c, MVFIT_E_UNSUPPORTED, "mvfit_sdf_term_read: the %s term keeps no per-vertex samples (sums only)", term_name(c));
     HIP_OK(c, hipSetDevice(c->device));
-    if (c->mix.on) {                                               // the weighted sum of the parts: penalty = w^2 sums
-        if (sums) HIP_OK(c, hipMemcpyAsync(sums, c->mix.sums, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        return MVFIT_OK;
-    }
-    if (c->silt.on || c->vt.term) {                                // L_j itself (the record holds its root)
-        const float* L = c->vt.term ? c->vt.loss : c->silt.loss;
-        if (sums) HIP_OK(c, hipMemcpyAsync(sums, L, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        return MVFIT_OK;
-    }
     if (samples) HIP_OK(c, hipMemcpyAsync(samples, c->pb.sdf_samp, (size_t)c->B * c->nv * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    if (sums) HIP_OK(c, hipMemcpy2DAsync(sums, sizeof(float), c->pb.sdf_adj, sizeof(SdfAdj), sizeof(float), c->B, hipMemcpyDeviceToDevice, c->stream));
+    if (sums && plan.sums_stride == sizeof(float))
+        HIP_OK(c, hipMemcpyAsync(sums, plan.sums, (size_t)c->B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    else if (sums)
+        HIP_OK(c, hipMemcpy2DAsync(sums, sizeof(float), plan.sums, plan.sums_stride, sizeof(float), c->B, hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 
@@ -418,60 +439,50 @@ bool mvfit::pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
     return !round_term(c) && c->M.bs_h2 != nullptr && c->pb.sdf_boxpart != nullptr && c->sdf_num_faces <= 128 && (chunks == 1 || c->opt.pass_kernel == 1);
 }
 
-// the interpenetration term of a chained round behind its vertex pass: against the frozen obstacles when they are set,
-// the silhouette term when it is on (silhouette evaluation -> dense pull-back -> record), the vertex-target term when it is
-// (target kernel -> the same pull-back), else the one-person term of mvfit_set_sdf.  The term mix comes first: the live vertex
-// terms' evaluations, their mixed cotangent in front of ONE pull-back, and - with a scene share - the scene term into a record
-// of its own and the merge of the two records (term_mix.hip)
-hipError_t mvfit::launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
-    if (c->mix.on) {
-        const TermMix& X = c->mix;
-        const bool sil = X.silhouette > 0.f, vt = X.vertex_targets > 0.f, scene = X.scene > 0.f;
-        hipError_t e = hipSuccess;
-        if (sil && sil_round(c->sil, verts, c->B, X.w_in, X.w_out, X.sigma, gate, c->silt.loss, c->silt.g_verts, st, c->err))
-            return hipErrorLaunchFailure;
-        if (vt) {
-            const VtxTargets& T = c->vt;
-            e = launch_vertex_target(verts, c->nv, c->B, T.K, T.targets, T.weights, gate, T.partial, T.loss, T.g_verts, st);
-            if (e != hipSuccess) return e;
+// the interpenetration term of a chained round behind its vertex pass: the steps of its plan (round_term.cpp decides which), each
+// one launch on the round's stream with no host work.  Everything a launcher takes is in the plan, but the model, the pose
+// operands and what the round itself brings: its vertices, gate, stream and the pass's tile keys of the box.
+hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, std::string& err, const float* verts,
+                              const int* gate, hipStream_t st, const unsigned long long* box_part) {
+    const int B = plan.B, nv = plan.nv;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < plan.n && e == hipSuccess; ++i) {
+        const TermStep& s = plan.step[i];
+        switch (s.kind) {
+        case STEP_SIL_EVAL:
+            if (sil_round(sil, verts, B, s.sil.w_in, s.sil.w_out, s.sil.sigma, gate, s.sil.loss, s.sil.g_verts, st, err)) e = hipErrorLaunchFailure;
+            break;
+        case STEP_VT_EVAL:
+            e = launch_vertex_target(verts, nv, B, s.vt.K, s.vt.targets, s.vt.weights, gate, s.vt.partial, s.vt.loss, s.vt.g_verts, st);
+            break;
+        case STEP_MIX_COTANGENT:
+            e = launch_term_mix_cotangent(nv, B, s.cot.lam_sil, s.cot.g_sil, s.cot.L_sil, s.cot.lam_vt, s.cot.g_vt, s.cot.L_vt, gate, s.cot.g,
+                                          s.cot.L_v, s.cot.parts, s.cot.sums, st);
+            break;
+        case STEP_PULLBACK:
+            e = launch_silhouette_pullback(M, P, B, plan.Bpad, gate, s.pull.g_verts, s.pull.loss, s.pull.part, s.pull.rec, st);
+            break;
+        case STEP_SCENE:
+            e = launch_scene_term(M, P, verts, B, s.scene.tab, static_cast<const float4*>(s.scene.box), s.scene.phi, s.scene.grid, s.scene.rob, gate,
+                                  s.scene.null_box, s.scene.entries, s.scene.rec, st);
+            break;
+        case STEP_MIX_RECORD:
+            e = launch_term_mix_record(B, s.rec.lam_sc, s.rec.rec_scene, s.rec.rec_verts, s.rec.lam_sil, s.rec.L_sil, s.rec.lam_vt, s.rec.L_vt, gate,
+                                       s.rec.rec, s.rec.parts, s.rec.sums, st);
+            break;
+        case STEP_SDF:
+            e = launch_sdf_term(M, P, verts, B, s.sdf.faces, s.sdf.num_faces, s.sdf.grid, gate, s.sdf.box, static_cast<float4*>(s.sdf.samp),
+                                s.sdf.entries, s.sdf.adj, st, s.sdf.cull, nullptr, 0u, box_part);
+            break;
+        default:
+            e = hipErrorInvalidValue;
         }
-        // one live vertex term with share 1: its own buffers go to the pull-back as they are
-        const float *g = X.g_verts, *L = X.loss;
-        if (sil && !vt && X.silhouette == 1.f) { g = c->silt.g_verts; L = c->silt.loss; }
-        else if (vt && !sil && X.vertex_targets == 1.f) { g = c->vt.g_verts; L = c->vt.loss; }
-        else {
-            e = launch_term_mix_cotangent(c->nv, c->B, X.silhouette, c->silt.g_verts, c->silt.loss, X.vertex_targets, c->vt.g_verts,
-                                          c->vt.loss, gate, X.g_verts, X.loss, scene ? nullptr : X.parts, X.sums, st);
-            if (e != hipSuccess) return e;
-        }
-        e = launch_silhouette_pullback(c->M, c->P, c->B, c->Bpad, gate, g, L, X.part, scene ? X.rec_verts : c->pb.sdf_adj, st);
-        if (e != hipSuccess || !scene) return e;
-        e = launch_scene_term(c->M, c->P, verts, c->B, c->obst.tab, c->obst.box, c->obst.phi, c->obst.grid, c->obst.rob, gate,
-                              c->pb.sdf_box, c->pb.sdf_entries, X.rec_scene, st);
-        if (e != hipSuccess) return e;
-        return launch_term_mix_record(c->B, X.scene, X.rec_scene, X.rec_verts, X.silhouette, sil ? c->silt.loss : nullptr,
-                                      X.vertex_targets, vt ? c->vt.loss : nullptr, gate, c->pb.sdf_adj, X.parts, X.sums, st);
     }
-    if (c->vt.term) {
-        const VtxTargets& T = c->vt;
-        const hipError_t e = launch_vertex_target(verts, c->nv, c->B, T.K, T.targets, T.weights, gate, T.partial, T.loss, T.g_verts, st);
-        if (e != hipSuccess) return e;
-        return launch_silhouette_pullback(c->M, c->P, c->B, c->Bpad, gate, T.g_verts, T.loss, T.part, c->pb.sdf_adj, st);
-    }
-    if (c->silt.on) {
-        const SilTerm& T = c->silt;
-        if (sil_round(c->sil, verts, c->B, T.w_in, T.w_out, T.sigma, gate, T.loss, T.g_verts, st, c->err)) return hipErrorLaunchFailure;
-        return launch_silhouette_pullback(c->M, c->P, c->B, c->Bpad, gate, T.g_verts, T.loss, T.part, c->pb.sdf_adj, st);
-    }
-    if (c->obst.on)
-        return launch_scene_term(c->M, c->P, verts, c->B, c->obst.tab, c->obst.box, c->obst.phi, c->obst.grid, c->obst.rob, gate,
-                                 c->pb.sdf_box, c->pb.sdf_entries, c->pb.sdf_adj, st);
-    return launch_sdf_term(c->M, c->P, verts, c->B, c->sdf_faces.as<int32_t>(), c->sdf_num_faces, c->sdf_grid, gate, c->pb.sdf_box, c->pb.sdf_samp,
-                           c->pb.sdf_entries, c->pb.sdf_adj, st, c->sdf_cull.get(), nullptr, 0u, box_part);
+    return e;
 }
 
 int mvfit::run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st) {
-    const hipError_t e = launch_term(c, verts, gate, st, nullptr);
+    const hipError_t e = launch_term(plan_round_term(term_inputs(c)), c->M, c->P, c->sil, c->err, verts, gate, st, nullptr);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s term launch: %s", term_name(c), hipGetErrorString(e));
     return MVFIT_OK;
 }

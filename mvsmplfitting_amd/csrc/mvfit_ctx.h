@@ -17,6 +17,7 @@
 #include "fit_kernels.h"
 #include "fit_plan.h"
 #include "launchers.h"
+#include "round_term.h"
 #include "silhouette.h"
 #include "term_mix.h"
 #include "vertex_target.h"
@@ -188,16 +189,34 @@ void prof_end(mvfit_ctx* c, std::vector<std::pair<hipEvent_t, hipEvent_t>>& evs)
 int run_vertex_pass(mvfit_ctx* c, float* verts);
 int ensure_sdf_buffers(mvfit_ctx* c);
 bool pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi);
-hipError_t launch_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part);
+// the round's term: what launch_term needs is in the plan (round_term.h) - it never sees the ctx
+TermInputs term_inputs(const mvfit_ctx* c);
+hipError_t launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, std::string& err, const float* verts,
+                       const int* gate, hipStream_t st, const unsigned long long* box_part);
 int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st);
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
 void free_vertex_targets(mvfit_ctx* c);
 void free_term_mix(mvfit_ctx* c);
-inline const char* term_name(const mvfit_ctx* c) {
-    return c->mix.on ? "mix" : c->vt.term ? "vertex-target" : c->silt.on ? "silhouette" : c->obst.on ? "scene" : "sdf";
-}
+inline const char* term_name(const mvfit_ctx* c) { return term_kind_name(term_slot(term_inputs(c))); }
 // a term other than mvfit_set_sdf's is configured: it runs in chained rounds only and keeps no per-vertex samples
-inline bool round_term(const mvfit_ctx* c) { return c->mix.on || c->obst.on || c->silt.on || c->vt.term; }
+inline bool round_term(const mvfit_ctx* c) { return term_slot(term_inputs(c)) != TERM_SDF; }
+
+// A data set a term reads went away (or is about to be re-made): its own term goes off, and so does a mix that gives it a share.
+enum TermSource { SRC_OBSTACLES = 0, SRC_MASKS, SRC_TARGETS };
+inline bool& term_flag(mvfit_ctx* c, TermSource src) { return src == SRC_OBSTACLES ? c->obst.on : src == SRC_MASKS ? c->silt.on : c->vt.term; }
+inline void term_source_gone(mvfit_ctx* c, TermSource src) {
+    const float share[] = {c->mix.scene, c->mix.silhouette, c->mix.vertex_targets};
+    term_flag(c, src) = false;
+    if (share[src] > 0.f) c->mix.on = false;
+}
+// the same around a re-make that can fail: a failure leaves no term behind, restore() after success brings both flags back
+struct TermSuspend {
+    mvfit_ctx* c;
+    TermSource src;
+    bool term, mix;
+    TermSuspend(mvfit_ctx* c_, TermSource s) : c(c_), src(s), term(term_flag(c_, s)), mix(c_->mix.on) { term_source_gone(c, s); }
+    void restore() { term_flag(c, src) = term; c->mix.on = mix; }
+};
 
 }  // namespace mvfit

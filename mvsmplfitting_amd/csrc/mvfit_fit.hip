@@ -50,51 +50,10 @@ static int make_opts(mvfit_ctx* c, const mvfit_lbfgs_opts* o, uint32_t flags, Lb
 static const int kGraphRounds = 24;
 
 static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O) {
-    // (the scene term's obstacles: buffers and scalars baked into its kernel node; a re-freeze changes none of them)
-    struct { const void *tab, *box, *phi; int grid; float rob; } obst = {nullptr, nullptr, nullptr, 0, 0.f};
-    if (c->obst.on) { obst.tab = c->obst.tab; obst.box = c->obst.box; obst.phi = c->obst.phi; obst.grid = c->obst.grid; obst.rob = c->obst.rob; }
-    // (the silhouette term: mask workspace and contour buffers, the sizes their offsets and grids derive from, the round's
-    // buffers and the weights; a re-set of a mask set of the same sizes and contour changes none of them)
-    // (its occluders: the maps' buffer, whether they are set, and the margin; a re-freeze at the same sizes changes none)
-    struct { const void *ws, *cs, *g_verts, *loss, *part, *occ; int M, H, W, C, nchunks, stride, occ_on; float w_in, w_out, sigma, margin; } silk;
-    memset(&silk, 0, sizeof(silk));
-    if ((c->silt.on || (c->mix.on && c->mix.silhouette > 0.f)) && c->sil.occ_on) {
-        silk.occ = c->sil.occ.get(); silk.occ_on = 1; silk.margin = c->sil.occ_margin;
-    }
-    if (c->silt.on) {
-        silk.ws = c->sil.ws.get(); silk.cs = c->sil.cs.get(); silk.g_verts = c->silt.g_verts; silk.loss = c->silt.loss; silk.part = c->silt.part;
-        silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
-        silk.w_in = c->silt.w_in; silk.w_out = c->silt.w_out; silk.sigma = c->silt.sigma;
-    }
-    // (the vertex-target term: the set's buffers and K, the round's buffers; the weights are read from their device buffer, so
-    // a re-freeze with the same (B, K) changes nothing here)
-    struct { const void *targets, *weights, *partial, *g_verts, *loss, *part; long long K; } vtk;
-    memset(&vtk, 0, sizeof(vtk));
-    if (c->vt.term) {
-        vtk.targets = c->vt.targets; vtk.weights = c->vt.weights; vtk.partial = c->vt.partial; vtk.g_verts = c->vt.g_verts;
-        vtk.loss = c->vt.loss; vtk.part = c->vt.part; vtk.K = c->vt.K;
-    }
-    // (the term mix: what its live components bake in - as above, so a re-freeze with the same shapes changes nothing - its own
-    // buffers, the three shares and the silhouette scalars)
-    struct { const void *g_verts, *loss, *part, *rec_scene, *rec_verts, *parts, *sums; float scene, silhouette, vertex_targets, w_in, w_out, sigma; } mixk;
-    memset(&mixk, 0, sizeof(mixk));
-    if (c->mix.on) {
-        const TermMix& X = c->mix;
-        if (X.scene <= 0.f) memset(&obst, 0, sizeof(obst));           // (obstacles may be set without taking part)
-        if (X.silhouette > 0.f) {
-            silk.ws = c->sil.ws.get(); silk.cs = c->sil.cs.get(); silk.g_verts = c->silt.g_verts; silk.loss = c->silt.loss;
-            silk.M = c->sil.M; silk.H = c->sil.H; silk.W = c->sil.W; silk.C = c->sil.C; silk.nchunks = c->sil.nchunks; silk.stride = c->sil.stride;
-        }
-        if (X.vertex_targets > 0.f) {
-            vtk.targets = c->vt.targets; vtk.weights = c->vt.weights; vtk.partial = c->vt.partial; vtk.g_verts = c->vt.g_verts;
-            vtk.loss = c->vt.loss; vtk.K = c->vt.K;
-        }
-        mixk.g_verts = X.g_verts; mixk.loss = X.loss; mixk.part = X.part; mixk.rec_scene = X.rec_scene; mixk.rec_verts = X.rec_verts;
-        mixk.parts = X.parts; mixk.sums = X.sums;
-        mixk.scene = X.scene; mixk.silhouette = X.silhouette; mixk.vertex_targets = X.vertex_targets;
-        mixk.w_in = X.w_in; mixk.w_out = X.w_out; mixk.sigma = X.sigma;
-    }
-    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(obst) + sizeof(silk) + sizeof(vtk) + sizeof(mixk));
+    // the key: everything baked into the kernel nodes.  The term's part of it is the plan launch_term executes below - what a
+    // step does not take is not in the plan, so a re-freeze or re-set that keeps the buffers and sizes keeps the graph
+    const RoundTermPlan term = plan_round_term(term_inputs(c), c->F.sdf_adj != nullptr);
+    std::vector<unsigned char> key(sizeof(SW) + sizeof(O) + sizeof(DevPose) + sizeof(FitBuffers) + sizeof(DevProblems) + sizeof(int) + sizeof(term));
     unsigned char* k = key.data();
     memcpy(k, &SW, sizeof(SW)); k += sizeof(SW);
     memcpy(k, &O, sizeof(O)); k += sizeof(O);
@@ -102,10 +61,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
     memcpy(k, &c->F, sizeof(FitBuffers)); k += sizeof(FitBuffers);
     memcpy(k, &c->Q, sizeof(DevProblems)); k += sizeof(DevProblems);
     memcpy(k, &c->opt.pass_kernel, sizeof(int)); k += sizeof(int);
-    memcpy(k, &obst, sizeof(obst)); k += sizeof(obst);
-    memcpy(k, &silk, sizeof(silk)); k += sizeof(silk);
-    memcpy(k, &vtk, sizeof(vtk)); k += sizeof(vtk);
-    memcpy(k, &mixk, sizeof(mixk));
+    memcpy(k, &term, sizeof(term));
     if (c->round_graph && key == c->graph_key) return MVFIT_OK;
     drop_graph(c);
     hipStream_t cs;
@@ -120,7 +76,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         for (int r = 0; r < kGraphRounds && e == hipSuccess; ++r) {
             e = launch_vertex_pass(c->M, Pg, c->B, c->pb.verts, c->opt.pass_kernel, cs);
             if (e == hipSuccess && c->F.sdf_adj)
-                e = launch_term(c, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
+                e = launch_term(term, c->M, c->P, c->sil, c->err, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
             launch_fit_step(O.reuse_outer != 0, c->B, cs, c->M, c->pb.obs, c->V, SW, O, c->P, c->F);
         }
         hipError_t e2 = hipStreamEndCapture(cs, &g);

@@ -173,8 +173,7 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (!c) return MVFIT_E_ARG;
     HIP_OK(c, hipSetDevice(c->device));
     if (!vertices) {                                         // remove: the buffers stay for the next freeze of this batch
-        c->obst.on = false;
-        if (c->mix.scene > 0.f) c->mix.on = false;           // no obstacles, no mix that uses them
+        term_source_gone(c, SRC_OBSTACLES);                  // no obstacles: no scene term and no mix that uses them
         return MVFIT_OK;
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
@@ -193,6 +192,7 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
     if (scene_first[num_scenes] != c->B)
         return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: the scenes hold %d bodies, the ctx %d problems", scene_first[num_scenes], c->B);
     const size_t nvox = (size_t)grid_size * grid_size * grid_size;
+    TermSuspend off(c, SRC_OBSTACLES);                       // a failed freeze leaves no term behind (and no mix that uses it)
     if (c->obst.grid != grid_size || !c->obst.phi) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
         free_obstacles(c);
@@ -201,9 +201,6 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
         HIP_OK(c, c->obst_mem.alloc(&c->obst.phi, (size_t)c->B * nvox * 4));
         c->obst.grid = grid_size;
     }
-    c->obst.on = false;                                      // a failed freeze leaves no term behind (and no mix that uses it)
-    const bool mix = c->mix.on;
-    if (c->mix.scene > 0.f) c->mix.on = false;
     rc = ensure_sdf_buffers(c);
     if (rc) return rc;
     hipError_t e = launch_scene_null_boxes(c->pb.sdf_box, c->B, c->stream);
@@ -212,8 +209,8 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
                        scale_factor, robustifier, nullptr, nullptr, c->obst.phi, c->obst.box, c->obst.tab);
     if (rc) return rc;
     c->obst.rob = robustifier;
+    off.restore();
     c->obst.on = true;
-    c->mix.on = mix;
     return MVFIT_OK;
 }
 
@@ -236,8 +233,7 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
     HIP_OK(c, hipSetDevice(c->device));
     if (num_images == 0) {                                   // clear: the work areas stay for a next set of the same size
         c->sil.on = false;
-        c->silt.on = false;                                  // no masks, no term
-        if (c->mix.silhouette > 0.f) c->mix.on = false;      // and no mix that uses them
+        term_source_gone(c, SRC_MASKS);                      // no masks: no term and no mix that uses them
         return MVFIT_OK;
     }
     if (num_images < 0 || num_images > 65535 || height < 2 || height > 8192 || width < 2 || width > 8192)
@@ -253,8 +249,7 @@ extern "C" int mvfit_set_silhouettes(mvfit_ctx* c, int num_images, int height, i
     // problems' buffers by image_body); a failed or unfit set leaves no term behind
     const bool in_mix = c->mix.on && c->mix.silhouette > 0.f;
     if ((c->silt.on || in_mix) && (rc || c->sil.body_min < 0 || c->sil.body_max >= c->B)) {
-        c->silt.on = false;
-        if (in_mix) c->mix.on = false;
+        term_source_gone(c, SRC_MASKS);
         if (!rc)
             return fail(c, MVFIT_E_ARG, "mvfit_set_silhouettes: image_body holds %d .. %d, outside the %d problems of the enabled "
                         "silhouette term (the term is switched off)", c->sil.body_min, c->sil.body_max, c->B);
@@ -290,7 +285,7 @@ static int ensure_vt_round(mvfit_ctx* c) {
     return MVFIT_OK;
 }
 
-// The silhouette term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (mvfit_api.hip: launch_term).
+// The silhouette term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (round_term.cpp plans the launches).
 extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, float w_out, float sigma) {
     if (!c) return MVFIT_E_ARG;
     HIP_OK(c, hipSetDevice(c->device));
@@ -389,8 +384,7 @@ extern "C" int mvfit_set_vertex_targets(mvfit_ctx* c, int K, const float* target
     HIP_OK(c, hipSetDevice(c->device));
     if (K == 0 || !targets) {                                // clear: the buffers stay for a next set of the same shape
         c->vt.on = false;
-        c->vt.term = false;                                  // no targets, no term
-        if (c->mix.vertex_targets > 0.f) c->mix.on = false;  // and no mix that uses them
+        term_source_gone(c, SRC_TARGETS);                    // no targets: no term and no mix that uses them
         return MVFIT_OK;
     }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
@@ -405,17 +399,15 @@ extern "C" int mvfit_set_vertex_targets(mvfit_ctx* c, int K, const float* target
     VtxTargets& T = c->vt;
     if (!T.partial || T.K != K) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
-        const bool term = T.term, mix = c->mix.on;
+        TermSuspend off(c, SRC_TARGETS);                     // (a failed allocation leaves no set and no term behind)
         c->vtgt_mem.release();
-        T.on = false; T.term = false;                        // (a failed allocation leaves no set and no term behind)
-        if (c->mix.vertex_targets > 0.f) c->mix.on = false;
+        T.on = false;
         T.targets = nullptr; T.weights = nullptr; T.partial = nullptr; T.K = 0;
         HIP_OK(c, c->vtgt_mem.alloc(&T.targets, (size_t)c->B * K * row));
         HIP_OK(c, c->vtgt_mem.alloc(&T.weights, (size_t)c->B * K * sizeof(float)));
         HIP_OK(c, c->vtgt_mem.alloc(&T.partial, (size_t)c->B * vertex_target_blocks(c->nv) * sizeof(double), true));   // last: a set with partials is complete
         T.K = K;
-        T.term = term;
-        c->mix.on = mix;
+        off.restore();
     }
     HIP_OK(c, hipMemcpyAsync(T.targets, targets, (size_t)c->B * K * row, hipMemcpyDefault, c->stream));
     HIP_OK(c, hipMemcpyAsync(T.weights, weights, (size_t)c->B * K * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -435,7 +427,7 @@ extern "C" int mvfit_vertex_target_loss(mvfit_ctx* c, const float* vertices, flo
     return MVFIT_OK;
 }
 
-// The vertex-target term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (mvfit_api.hip: launch_term).
+// The vertex-target term inside mvfit_fit / mvfit_closure (include/mvfit.h): state only - the rounds launch it (round_term.cpp plans the launches).
 extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
     if (!c) return MVFIT_E_ARG;
     HIP_OK(c, hipSetDevice(c->device));
@@ -456,7 +448,7 @@ extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
 }
 
 // The weighted sum of the scene, silhouette and vertex-target terms inside mvfit_fit / mvfit_closure (include/mvfit.h): state
-// and buffers only - the rounds launch it (mvfit_api.hip: launch_term).
+// and buffers only - the rounds launch it (round_term.cpp plans the launches).
 extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
     if (!c) return MVFIT_E_ARG;
     HIP_OK(c, hipSetDevice(c->device));

@@ -421,31 +421,40 @@ def test_chained_rounds_evaluate_the_closures_function(world):
 
 def test_the_round_graph_follows_the_frozen_data_and_the_shares(world):
     eng, x = _three(world)
+    builds = []                                              # round graphs captured so far, read after every fit
+
+    def fit():
+        out = _fit(eng, x, [_stage(w)])
+        builds.append(eng.round_graph_info()['builds'])
+        return out
     try:
         w = _w3(eng, x)
-        first = _fit(eng, x, [_stage(w)])
+        first = fit()
         # a re-freeze with unchanged shapes: other obstacles, other targets and a re-set mask set in the same buffers
         _freeze(eng, x, 30)
         T = torch.roll(world['T'][list(ROWS3)], 1, dims=1)
         a = np.roll(world['a'][list(ROWS3)], 1, axis=1) * np.float32(1.5)
         eng.set_vertex_targets(T, a)
         eng.set_silhouettes(*_mask_set(world, ROWS3))
-        second = _fit(eng, x, [_stage(w)])
+        second = fit()
         # another share
         other = (0.25, 1.0, 0.75)
         eng.set_term_mix(scene=other[0], silhouette=other[1], vertex_targets=other[2], **SIL)
-        third = _fit(eng, x, [_stage(w)])
+        third = fit()
         # after the mix: each single term as on an engine that never saw it
         eng.clear_term_mix()
-        singles = [_fit(eng, x, [_stage(w)])]                                  # the obstacles alone are the scene term
+        singles = [fit()]                                                      # the obstacles alone are the scene term
         eng.clear_scene_obstacles()
         eng.set_silhouette_term(**SIL)
-        singles.append(_fit(eng, x, [_stage(w)]))
+        singles.append(fit())
         eng.clear_silhouette_term()
         eng.set_vertex_target_term()
-        singles.append(_fit(eng, x, [_stage(w)]))
+        singles.append(fit())
     finally:
         eng.close()
+    # the graph is captured once per launch list: the re-freeze replays the first one, every other step bakes other nodes in
+    print('round graphs after each fit:', builds)
+    assert [n - m for m, n in zip([0] + builds, builds)] == [1, 0, 1, 1, 1, 1], builds
     assert not _same(first, second) and not _same(second, third)
     for shares, got in ((SHARES, second), (other, third)):
         fresh, xs = _three(world, shares=None)
