@@ -207,21 +207,48 @@ __device__ __forceinline__ void mat3_mul(const float* a, const float* b, float* 
 }
 
 // Rodrigues (lbs.py:269-300): angle = ||r + 1e-8||, k = r / angle, R = I + sin K + (1 - cos) K^2
-__device__ __forceinline__ void rodrigues(const float* r, float* R, float* rod) {
+//   K = [[0,-kz,ky],[kz,0,-kx],[-ky,kx,0]] ; K^2 = k k^T - |k|^2 I
+//   kk = kx kx + ky ky + kz kz
+//   R[0] = 1 + oc (kx kx - kk)   R[1] = -sn kz + oc kx ky     R[2] = sn ky + oc kx kz
+//   R[3] = sn kz + oc kx ky      R[4] = 1 + oc (ky ky - kk)   R[5] = -sn kx + oc ky kz
+//   R[6] = -sn ky + oc kx kz     R[7] = sn kx + oc ky kz      R[8] = 1 + oc (kz kz - kk)
+// E1 used to evaluate these plain expressions twice per joint, once for R and once for the pose feature R - I, and the
+// compiler had contracted the two copies differently: R with every sum fused onto one rounded product, the pose feature
+// with packed multiplies - both products of a sum rounded, the sum plain.  The words differ in the last bit, and both
+// are what every later phase and every recorded result was computed from.  So the expensive part (norm, division,
+// sincos: the same in both copies) is evaluated once, rodrigues_axis, and the nine elements are stated in each of the
+// two forms, operation by operation, with contraction off.
+struct RodAxis { float kx, ky, kz, sn, oc; };
+__device__ __forceinline__ RodAxis rodrigues_axis(const float* r, float* rod) {
+#pragma clang fp contract(off)
     const float rx = r[0], ry = r[1], rz = r[2];
     const float ex = rx + 1e-8f, ey = ry + 1e-8f, ez = rz + 1e-8f;
-    const float a = sqrtf(ex * ex + ey * ey + ez * ez);
+    const float a = sqrtf(fmaf(ey, ey, ex * ex) + ez * ez);
     const float ia = 1.0f / a;
-    const float kx = rx * ia, ky = ry * ia, kz = rz * ia;
     float sn, cs;
     sincosf(a, &sn, &cs);
-    const float oc = 1.0f - cs;
-    // K = [[0,-kz,ky],[kz,0,-kx],[-ky,kx,0]] ; K^2 = k k^T - |k|^2 I
-    const float kk = kx * kx + ky * ky + kz * kz;
-    R[0] = 1.f + oc * (kx * kx - kk); R[1] = -sn * kz + oc * kx * ky;   R[2] = sn * ky + oc * kx * kz;
-    R[3] = sn * kz + oc * kx * ky;    R[4] = 1.f + oc * (ky * ky - kk); R[5] = -sn * kx + oc * ky * kz;
-    R[6] = -sn * ky + oc * kx * kz;   R[7] = sn * kx + oc * ky * kz;    R[8] = 1.f + oc * (kz * kz - kk);
     rod[0] = a; rod[1] = sn; rod[2] = cs;
+    return RodAxis{rx * ia, ry * ia, rz * ia, sn, 1.0f - cs};
+}
+// the elements of R as L.pose.R / Mj hold them
+__device__ __forceinline__ void rodrigues_R(const RodAxis& k, float* R) {
+#pragma clang fp contract(off)
+    const float kk = fmaf(k.kz, k.kz, fmaf(k.kx, k.kx, k.ky * k.ky));
+    const float okx = k.kx * k.oc, oky = k.ky * k.oc, okxy = k.ky * okx, okyz = k.kz * oky, sky = k.ky * k.sn;
+    R[0] = fmaf(fmaf(k.kx, k.kx, -kk), k.oc, 1.f); R[1] = fmaf(-k.kz, k.sn, okxy); R[2] = fmaf(k.kz, okx, sky);
+    R[3] = fmaf(k.kz, k.sn, okxy); R[4] = fmaf(fmaf(k.ky, k.ky, -kk), k.oc, 1.f); R[5] = fmaf(-k.kx, k.sn, okyz);
+    R[6] = fmaf(k.kz, okx, -sky);  R[7] = fmaf(k.kx, k.sn, okyz); R[8] = fmaf(fmaf(k.kz, k.kz, -kk), k.oc, 1.f);
+}
+// the same elements as the pose feature (L.coef) holds them, before the identity is subtracted
+__device__ __forceinline__ void rodrigues_feature(const RodAxis& k, float* P) {
+#pragma clang fp contract(off)
+    const float kx2 = k.kx * k.kx, kz2 = k.kz * k.kz;
+    const float kk = kz2 + fmaf(k.ky, k.ky, kx2);
+    const float okx = k.kx * k.oc, oky = k.ky * k.oc;
+    const float xy = k.ky * okx, xz = k.kz * okx, yz = k.kz * oky, sx = k.kx * k.sn, sy = k.sn * k.ky, sz = k.kz * k.sn;
+    P[0] = fmaf(kx2 - kk, k.oc, 1.f); P[1] = xy - sz; P[2] = sy + xz;
+    P[3] = sz + xy; P[4] = fmaf(fmaf(k.ky, k.ky, -kk), k.oc, 1.f); P[5] = yz - sx;
+    P[6] = xz - sy; P[7] = sx + yz; P[8] = fmaf(kz2 - kk, k.oc, 1.f);
 }
 
 // Streamed GEMV for the decoder: out[o] = sum_{i < n} W[i * ld + o] * h[i], o < ncols (multiple of 4).
@@ -562,12 +589,68 @@ __device__ __forceinline__ void vposer_backward(const DevModel& M, ClosureLds& L
     __syncthreads();
 }
 
-constexpr int FWD_SLICES = 8, FWD_RPS = KROWS / FWD_SLICES;      // 28 basis rows per k-slice of the forward contraction
+static_assert(FWD_THREADS == STEP_NT - 64, "the forward stream runs on waves 1-7");
+
+// One forward item (k-slice ks of float4 column group cq) in two halves, as bwd_item_load / bwd_item_fma below: the loads
+// depend on nothing the round computes - pd_sub is a model constant, only the FMAs need the blendshape coefficients -, so
+// the waves that idle in E1 issue them there, one barrier ahead of E2, and E2 finds the data on its way.  The addresses
+// (slice rotation by blockIdx.x: workgroups of one XCD run in near lock-step on the same matrix and start at different
+// slices so that they do not queue on the same L2 channel), the 28 x 2-accumulator FMAs, their order and the store are
+// contraction_forward's own - it is these two in sequence.
+__device__ __forceinline__ void fwd_item_load(const DevModel& M, int nc_pad, int item, float4 (&v)[FWD_RPS]) {
+    const int ncq = nc_pad >> 2;                   // float4 column groups
+    const int cq = item % ncq, ks = (item / ncq + (int)blockIdx.x) & (FWD_SLICES - 1);
+    // address = the lane's byte offset + a scalar multiple of the row's bytes
+    const unsigned voff = (unsigned)((ks * FWD_RPS) * ncq + cq) * 16u;
+    const char* base = reinterpret_cast<const char*>(M.pd_sub);
+    const unsigned row = (unsigned)__builtin_amdgcn_readfirstlane(ncq) * 16u;      // bytes per basis row (a model constant)
+#pragma unroll
+    for (int r = 0; r < FWD_RPS; ++r) {
+        v[r] = *reinterpret_cast<const float4*>(base + (size_t)(r * row) + voff);
+        if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);          // issue order = the order the FMAs consume
+    }
+}
+
+__device__ __forceinline__ void fwd_item_fma(ClosureLds& L, int nc_pad, int item, const float4 (&v)[FWD_RPS]) {
+    const int ncq = nc_pad >> 2;
+    const int cq = item % ncq, ks = (item / ncq + (int)blockIdx.x) & (FWD_SLICES - 1);
+    float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+#pragma unroll
+    for (int r = 0; r < FWD_RPS; r += 2) {
+        const float c0 = L.coef[ks * FWD_RPS + r], c1 = L.coef[ks * FWD_RPS + r + 1];
+        acc0.x = fmaf(c0, v[r].x, acc0.x); acc0.y = fmaf(c0, v[r].y, acc0.y);
+        acc0.z = fmaf(c0, v[r].z, acc0.z); acc0.w = fmaf(c0, v[r].w, acc0.w);
+        acc1.x = fmaf(c1, v[r + 1].x, acc1.x); acc1.y = fmaf(c1, v[r + 1].y, acc1.y);
+        acc1.z = fmaf(c1, v[r + 1].z, acc1.z); acc1.w = fmaf(c1, v[r + 1].w, acc1.w);
+    }
+    float4* dst = reinterpret_cast<float4*>(L.scratch + ks * nc_pad + 4 * cq);
+    *dst = make_float4(acc0.x + acc1.x, acc0.y + acc1.y, acc0.z + acc1.z, acc0.w + acc1.w);
+}
+
+// What a wave that idles in E1 carries across E1's closing barrier into E2: its thread's forward item, loaded early.
+// wave: this wave is one of them (scalar: a whole wave's role) and the stream runs behind this E1; the lane owns an item
+// where fwd_item_owner says so (none at all for a model of few columns).  Live across that one barrier only.
+struct FwdEarly {
+    bool wave = false;
+    float4 v[FWD_RPS];
+};
+// stream: the forward stream runs behind this E1 (sparse_forward with from_pass == false) in a kernel that loads early
+__device__ __forceinline__ bool fwd_early_wave(const ClosureLds& L, bool stream, int tid) {
+#ifdef MVFIT_DEBUG_HOOKS
+    const bool fwd_late = (__builtin_amdgcn_readfirstlane(L.M.stream_late) & 2) != 0;      // the test's switch: every wave loads in E2
+#else
+    constexpr bool fwd_late = false;
+#endif
+    return stream && !fwd_late && __builtin_amdgcn_readfirstlane(tid) >= E1_IDLE_T0;
+}
 
 // ---------------------------------------------------------------------------------------------
 // E1: x -> theta, R, J, blendshape coefficients, relative transforms.   lbs.py:183-195,269-348
-// Every thread derives what it needs straight from x (Rodrigues is recomputed per output element)
-// so the phase has no internal barrier.  Ends with __syncthreads.
+// Every thread derives what it needs straight from x, so the phase has no internal barrier: one Rodrigues per element of
+// R - the thread that owns R[j][e] also writes the pose feature's word of that element (the same element less the
+// identity's, in the rounding the pose feature has always had: rodrigues_feature) -, on waves 0-4 (model_layout.h:
+// E1_WORKERS).  Waves 5-7 have no work here and, where the forward stream follows (ev.wave), issue their forward item's
+// loads in front of the closing barrier.  Ends with __syncthreads.
 // ---------------------------------------------------------------------------------------------
 template <bool REMOTE = false>
 // (inlining is spelled out for everything the fit kernels use: left to the heuristics it changes with the number of
@@ -587,38 +670,37 @@ __device__ __forceinline__ void pose_prep_decode_inl(const DevModel& M, ClosureL
 }
 
 // second half of E1 (force-inlined: the fit kernels keep a thread's prefetched basis rows in registers across it)
-__device__ __forceinline__ void pose_prep_elems(const DevModel& M, ClosureLds& L, uint32_t flags, int tid) {
+__device__ __forceinline__ void pose_prep_elems(const DevModel& M, ClosureLds& L, uint32_t flags, int tid, FwdEarly& ev) {
     // the axis-angle vectors: the decoder's output with VPoser (behind its barrier), else x's own slots (no copy to wait for)
     const float* th = (flags & MVFIT_F_VPOSER) ? &L.pose.theta[0] : &L.opt.x[X_GO];
-    if (tid < KROWS) {
-        // blendshape coefficients: pose_feature (lbs.py:192), betas, zero pad
-        const int p = tid;
-        float v = 0.f;
-        if (p < 207) {
-            const int j = 1 + p / 9, e = p % 9;
-            float R[9], rod[3];
-            rodrigues(&th[3 * j], R, rod);
-            float sel = R[0];
-#pragma unroll
-            for (int q = 1; q < 9; ++q) sel = (e == q) ? R[q] : sel;
-            v = sel - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-        } else if (p < 217) {
-            v = L.opt.x[X_BETAS + p - 207];
-        }
-        L.coef[p] = v;
+    const int wave_t0 = __builtin_amdgcn_readfirstlane(tid);                               // this wave's first thread
+    if (wave_t0 >= E1_IDLE_T0) {
+        // waves 5-7: no E1 work (the early loads below are an `if` of their own, see closure_backward)
+    } else if (tid >= E1_POSE_T) {
+        // blendshape coefficients behind the pose feature (lbs.py:192): betas, zero pad
+        const int p = E1_NPOSE + (tid - E1_POSE_T);
+        if (p < KROWS) L.coef[p] = p < E1_NPOSE + 10 ? L.opt.x[X_BETAS + p - E1_NPOSE] : 0.f;
     } else {
-        // relative transforms (lbs.py:341-348) + the cached R / J the adjoint needs
-        const int i = tid - KROWS;                 // 0..287
-        const int j = i / 12, e = i - j * 12;
+        // relative transforms (lbs.py:341-348) + the cached R / J the adjoint needs + the pose feature
+        const int j = tid / 12, e = tid - j * 12;
         if (e < 9) {
             float R[9], rod[3];
-            rodrigues(&th[3 * j], R, rod);
+            const RodAxis k = rodrigues_axis(&th[3 * j], rod);
+            rodrigues_R(k, R);
             float sel = R[0];
 #pragma unroll
             for (int q = 1; q < 9; ++q) sel = (e == q) ? R[q] : sel;
             L.pose.R[j][e] = sel;
             L.pose.Mj[j][4 * (e / 3) + (e % 3)] = (j == 0 ? L.opt.x[X_SC] : 1.0f) * sel;
             if (e < 3) L.pose.rod[j][e] = rod[e];
+            if (j >= 1) {
+                // pose_feature = R - I of the joints below the root (lbs.py:192), in its own rounding (rodrigues_feature)
+                rodrigues_feature(k, R);
+                sel = R[0];
+#pragma unroll
+                for (int q = 1; q < 9; ++q) sel = (e == q) ? R[q] : sel;
+                L.coef[9 * (j - 1) + e] = sel - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+            }
         } else {
             // J = J_t + J_S beta   (== J_regressor (v_template + shapedirs beta), lbs.py:179-183)
             const int a = e - 9;
@@ -636,7 +718,16 @@ __device__ __forceinline__ void pose_prep_elems(const DevModel& M, ClosureLds& L
             L.pose.Mj[j][4 * a + 3] = s - sp;
         }
     }
+    if (ev.wave) {
+        const FwdOwner own = fwd_item_owner(L.M.nc_pad, tid - 64);
+        if (own.early) fwd_item_load(M, L.M.nc_pad, own.first, ev.v);
+    }
     __syncthreads();
+}
+// (no forward stream behind this E1, or a kernel that loads it in the slot)
+__device__ __forceinline__ void pose_prep_elems(const DevModel& M, ClosureLds& L, uint32_t flags, int tid) {
+    FwdEarly none;
+    pose_prep_elems(M, L, flags, tid, none);
 }
 
 template <bool REMOTE = false>
@@ -649,6 +740,12 @@ __device__ __forceinline__ void pose_prep(const DevModel& M, ClosureLds& L, uint
     if constexpr (CALL) pose_prep_decode<false>(M, L, flags, tid);
     else pose_prep_decode_inl<false>(M, L, flags, tid);
     pose_prep_elems(M, L, flags, tid);
+}
+template <bool CALL = false>
+__device__ __forceinline__ void pose_prep(const DevModel& M, ClosureLds& L, uint32_t flags, int tid, FwdEarly& ev) {
+    if constexpr (CALL) pose_prep_decode<false>(M, L, flags, tid);
+    else pose_prep_decode_inl<false>(M, L, flags, tid);
+    pose_prep_elems(M, L, flags, tid, ev);
 }
 
 // kinematic chain (lbs.py:349-355) G_j = G_parent M_j in 3x4 form, then A_j = [Gr_j | Gt_j - Gr_j J_j]
@@ -742,32 +839,23 @@ __device__ __forceinline__ void chain_forward_block(ClosureLds& L, int tid) {
 
 // k-split partial sums of v_posed = v_template + coef . pd_sub  (lbs.py:179,192-203 on the selected
 // vertices): 8 slices of 28 basis rows x nc_pad/4 float4 column groups = items; threads [0, nthreads)
-// take items round-robin (one each for the SMPL keypoint set).  All 28 loads of an item are issued
+// take the items fwd_item_owner hands them (one each for the SMPL keypoint set).  All 28 loads of an item are issued
 // before the first FMA: the stream is then limited by bandwidth, not by one L2 round trip per row pair.
 __device__ __forceinline__ int fwd_slices(int, int) { return FWD_SLICES; }
 
-__device__ __forceinline__ void contraction_forward(const DevModel& M, ClosureLds& L, int t, int nthreads) {
+// the in-slot stream of stream thread t: load + FMA of every item it owns (the waves that loaded early do not come here)
+__device__ __forceinline__ void contraction_forward(const DevModel& M, ClosureLds& L, int t) {
     const int nc_pad = L.M.nc_pad;
-    const int ncq = nc_pad >> 2;                   // float4 column groups
-    for (int item = t; item < ncq * FWD_SLICES; item += nthreads) {
-        // workgroups of one XCD run in near lock-step on the same matrix: start each at a different slice
-        // so that they do not queue on the same L2 channel
-        const int cq = item % ncq, ks = (item / ncq + (int)blockIdx.x) & (FWD_SLICES - 1);
-        const float4* src = reinterpret_cast<const float4*>(M.pd_sub) + (size_t)(ks * FWD_RPS) * ncq + cq;
+    const FwdOwner own = fwd_item_owner(nc_pad, t);
+#pragma unroll 1
+    for (int k = 0, item = own.first; k < own.n; ++k, item += FWD_THREADS) {
         float4 v[FWD_RPS];
-#pragma unroll
-        for (int r = 0; r < FWD_RPS; ++r) v[r] = src[(size_t)r * ncq];
-        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
-#pragma unroll
-        for (int r = 0; r < FWD_RPS; r += 2) {
-            const float c0 = L.coef[ks * FWD_RPS + r], c1 = L.coef[ks * FWD_RPS + r + 1];
-            acc0.x = fmaf(c0, v[r].x, acc0.x); acc0.y = fmaf(c0, v[r].y, acc0.y);
-            acc0.z = fmaf(c0, v[r].z, acc0.z); acc0.w = fmaf(c0, v[r].w, acc0.w);
-            acc1.x = fmaf(c1, v[r + 1].x, acc1.x); acc1.y = fmaf(c1, v[r + 1].y, acc1.y);
-            acc1.z = fmaf(c1, v[r + 1].z, acc1.z); acc1.w = fmaf(c1, v[r + 1].w, acc1.w);
-        }
-        float4* dst = reinterpret_cast<float4*>(L.scratch + ks * nc_pad + 4 * cq);
-        *dst = make_float4(acc0.x + acc1.x, acc0.y + acc1.y, acc0.z + acc1.z, acc0.w + acc1.w);
+        fwd_item_load(M, nc_pad, item, v);
+        // (all 28 loads in front of the first FMA, in the order the FMAs consume them - fwd_item_load: left to itself the
+        // scheduler of the single-launch kernel issued them in three groups with a full wait behind each, or all of them
+        // with the rows of the first FMAs last; measured, either form makes the slot 0.6 k cycles longer)
+        __builtin_amdgcn_sched_barrier(0);
+        fwd_item_fma(L, nc_pad, item, v);
     }
 }
 
@@ -802,14 +890,29 @@ __device__ __forceinline__ void keypoints_from_xs(ClosureLds& L, int tid) {
 // E2 + E3: chain || forward contraction, then v_posed, T rows (lbs.py:209-213) and skinned positions.
 // from_pass: L.vposed / L.xs of the selected vertices were written by the kernel prologue from the
 // vertex pass's side outputs (full mode); run_chain = false when the pose block (G, A) is already in LDS.
-__device__ __forceinline__ void sparse_forward(const DevModel& M, ClosureLds& L, bool from_pass, int tid, bool run_chain = true) {
+// ev: what pose_prep_elems left for this slot - the waves with ev.wave set have their forward item on its way since E1
+// and only accumulate here (ev.wave implies !from_pass: fwd_early_wave).
+__device__ __forceinline__ void sparse_forward(const DevModel& M, ClosureLds& L, bool from_pass, int tid, bool run_chain, const FwdEarly& ev) {
     const int nc = L.M.nc, nc_pad = L.M.nc_pad;
     const int nks = fwd_slices(nc_pad, STEP_NT - 64);
     if (run_chain || !from_pass) {
-        // wave 0: the kinematic chain; waves 1-7: the forward basis stream (k-split partial sums) - overlapped
+        // wave 0: the kinematic chain; waves 1-7: the forward basis stream (k-split partial sums) - overlapped.  The roles
+        // are whole waves and their branches scalar; the early waves' FMAs are an `if` of their own ahead of the others (as
+        // the else side of the in-slot stream the compiler lays them behind it and keeps ev.v allocated across its registers)
         const long long t_e2 = PH_CLK();
-        if (tid < 64) { if (run_chain) chain_forward_wave(L, tid); PH_T(22); }
-        else if (!from_pass) { contraction_forward(M, L, tid - 64, STEP_NT - 64); PH_W(60, 64, t_e2); PH_W(62, 448, t_e2); }
+        const int wave_t0 = __builtin_amdgcn_readfirstlane(tid);
+        if (ev.wave) {
+            const FwdOwner own = fwd_item_owner(nc_pad, tid - 64);
+            if (own.early) fwd_item_fma(L, nc_pad, own.first, ev.v);
+        }
+        if (wave_t0 == 0) {
+            if (run_chain) chain_forward_wave(L, tid);
+            PH_T(22);
+        } else if (!from_pass && !ev.wave) {
+            __builtin_assume(tid >= 64);
+            contraction_forward(M, L, tid - 64);
+        }
+        PH_W(60, 64, t_e2); PH_W(62, 448, t_e2);
         __syncthreads();
     }
     PH_T(1);
@@ -854,6 +957,11 @@ __device__ __forceinline__ void sparse_forward(const DevModel& M, ClosureLds& L,
     }
     __syncthreads();
     keypoints_from_xs(L, tid);
+}
+// (every stream wave loads in the slot)
+__device__ __forceinline__ void sparse_forward(const DevModel& M, ClosureLds& L, bool from_pass, int tid, bool run_chain = true) {
+    FwdEarly none;
+    sparse_forward(M, L, from_pass, tid, run_chain, none);
 }
 
 // the scalar terms of the loss out of the reduced sums (fixed order, float64 like the reference's float() of the tensors):

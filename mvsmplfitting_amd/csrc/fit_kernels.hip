@@ -100,13 +100,15 @@ __global__ __launch_bounds__(STEP_NT) void closure_kernel(DevModel M, const ObsB
     prologue(L, M, obs + b, nullptr, nullptr, from_pass ? P.vposed_sel + (size_t)b * NC_MAX : nullptr,
              from_pass ? P.xs_sel + (size_t)b * NC_MAX : nullptr, params + (size_t)b * DV, tid, sdf_adj ? sdf_adj + b : nullptr);
     __syncthreads();
+    FwdEarly ev;                                   // the sparse closure: waves 5-7 load their forward item in E1
+    ev.wave = fwd_early_wave(L, from_pass == 0, tid);
     if constexpr (REMOTE) {
         pose_prep_decode_inl<true>(M, L, W.flags, tid);
-        pose_prep_elems(M, L, W.flags, tid);
+        pose_prep_elems(M, L, W.flags, tid, ev);
     } else {
-        pose_prep(M, L, W.flags, tid);
+        pose_prep(M, L, W.flags, tid, ev);
     }
-    sparse_forward(M, L, from_pass != 0, tid);
+    sparse_forward(M, L, from_pass != 0, tid, true, ev);
     if constexpr (REMOTE) publish_pose(L, P, b, tid);
     const bool want_grad = grad != nullptr;
     const double total = loss_and_keypoint_grad(M, L, nviews, W, want_grad, tid);
@@ -215,12 +217,16 @@ __device__ __forceinline__ bool fit_round(const DevModel& M, ClosureLds& L, int 
     PH_T0();
     // have_pose: the previous launch left the pose block of this x (and, with VPoser, the decoder state the
     // adjoint needs - the VpBlock)
+    // (the single-launch kernel: its waves 5-7 carry their forward item from E1 into E2; the chained step kernel reads the
+    // vertex pass's side outputs - from_pass - and has no forward stream)
+    FwdEarly ev;
+    ev.wave = fwd_early_wave(L, !from_pass && !have_pose, tid);
     if (!have_pose) {
         pose_prep_decode_inl<REMOTE>(M, L, W.flags, tid);
-        pose_prep_elems(M, L, W.flags, tid);
+        pose_prep_elems(M, L, W.flags, tid, ev);
     }
     PH_T(0);
-    sparse_forward(M, L, from_pass, tid, !have_pose);
+    sparse_forward(M, L, from_pass, tid, !have_pose, ev);
     PH_T(2);
     // asynchronous fit: the 6890-vertex pass of THIS trial point is already queued on the other CUs and waits for the
     // operands (coefficients, skinning transforms, translation: all complete here) in the ring slot of this round

@@ -22,6 +22,29 @@ constexpr int VPS_SLICES = 8;     // VPoser decoder helpers per set = slices of 
 constexpr int VPS_PMAX = 24;      // problems per helper set (wave w polls the slots w, w + 8, w + 16)
 constexpr int VPS_MAX_SETS = 16;  // 16 for launches of <= 32 problems, else 8 (fit_plan.h)
 
+// Who does what in the closure's first two phases (closure_device.h: pose_prep_elems, sparse_forward), as plain functions
+// the host can evaluate (tests/test_fwd_items_cpu.py restates them).
+// E1, 512 threads: thread tid < E1_POSE_T is (joint j, element e) = (tid / 12, tid % 12) - e < 9: one Rodrigues, the word
+// R[j][e], its Mj word and, for j >= 1, the pose feature coef[9 (j - 1) + e]; e >= 9: J[j][e - 9] and Mj's translation column -,
+// the next KROWS - 207 threads write the betas and the zero padding of coef.  Waves 5-7 have no E1 work.
+constexpr int E1_POSE_T = NJ * 12;                          // 288
+constexpr int E1_NPOSE = (NJ - 1) * 9;                      // 207 words of the pose feature
+constexpr int E1_WORKERS = E1_POSE_T + (KROWS - E1_NPOSE);  // 305
+constexpr int E1_IDLE_T0 = 320;                             // first thread of the waves without E1 work
+static_assert(E1_WORKERS <= E1_IDLE_T0 && E1_IDLE_T0 % 64 == 0, "E1's workers leave whole waves free");
+// E2's forward basis stream: FWD_SLICES k-slices x nc_pad / 4 float4 column groups = items; stream thread t (thread 64 + t
+// of the workgroup, waves 1-7) owns the items t and t + FWD_THREADS that exist.  The threads of the waves that idle in E1
+// (t >= FWD_EARLY_T0) never own a second item and load their first one there, one barrier ahead of its FMAs.
+constexpr int FWD_SLICES = 8, FWD_RPS = KROWS / FWD_SLICES;      // 28 basis rows per k-slice of the forward contraction
+constexpr int FWD_THREADS = 512 - 64, FWD_EARLY_T0 = E1_IDLE_T0 - 64;
+static_assert(FWD_EARLY_T0 + FWD_THREADS >= (NC_MAX / 4) * FWD_SLICES, "an early thread owns one item at most");
+struct FwdOwner { int first, n; bool early; };              // items first, first + FWD_THREADS, ... (n of them); early: the first one
+constexpr FwdOwner fwd_item_owner(int nc_pad, int t) {
+    const int nitems = (nc_pad >> 2) * FWD_SLICES;
+    const int n = t >= nitems ? 0 : (t + FWD_THREADS < nitems ? 2 : 1);
+    return FwdOwner{t, n, n > 0 && t >= FWD_EARLY_T0};
+}
+
 // Model constants every per-problem workgroup keeps in LDS (bulk-copied once per launch).
 struct ModelLds {
     float wT[NJ][NS_STRIDE];          // lbs_weights of the selected vertices, transposed: wT[j][s]
@@ -71,7 +94,8 @@ struct ModelLds {
     // is 1 - the kernels' prologue then lays HostModel::e6_cells over the first E6_ROW_BYTES of each row of wT, which nothing
     // else reads in that case (the image itself always holds the dense wT)
     // stream_late: always 0 in the image the host builds; the -DMVFIT_DEBUG_HOOKS build sets bit 0 on request (MVFIT_BWD_STREAM_LATE)
-    // and only that build's kernels read it: every wave of the adjoint's transposed stream then loads inside E7
+    // and only that build's kernels read it: every wave of the adjoint's transposed stream then loads inside E7; bit 1
+    // (MVFIT_FWD_STREAM_LATE): every wave of the forward stream loads inside E2
     int sel_sparse, e6_cells, stream_late, spad2;
 };
 constexpr int E6_NZ = 4;                                // padded entries per E6 cell
