@@ -686,6 +686,67 @@ int mvfit_associate_views(mvfit_ctx* ctx, int F, int V, int Nmax, const float* k
                           const double* intris, const double* extris, double max_cost, int min_joints, int min_views,
                           double* cost_out, int32_t* labels, int32_t* num_clusters);
 
+/* Refinement of the rig's cameras against held bodies.  Every term of a fit takes the rig of mvfit_set_problems as exact; these
+ * two ops hold the bodies' 17 keypoints and move the cameras, one independent problem per view: the keypoint data term of the
+ * closure restricted to the view, as a function of the view's camera.  B, V, gt_xy and w_conf are those of mvfit_set_problems
+ * (MVFIT_E_STATE before it); the ctx's own cameras are neither read nor changed - the caller passes the refined rig to
+ * mvfit_set_problems.  Both ops are asynchronous on the ctx stream, do no host synchronisation and use no workspace.
+ *   joints[B,17,3] float32 dev (the keypoints of mvfit_closure / mvfit_vertices) ; a camera is 15 float64: R (9, row-major),
+ *   t (3), f, cx, cy ; cams[V,15] float64 dev.  The 9 parameters of a camera are omega (3), dt (3), f, cx, cy.
+ *
+ * Arithmetic of view v (float64, no fused multiply-add; the float32 inputs are widened first).  Point (b, j) with
+ * X = joints[b,j], (gx, gy) = gt_xy[b,v,j], w = w_conf[b,v,j]; a point with w == 0 is not read further and adds nothing:
+ *   p = R X + t, a = px / pz, b = py / pz, u = f a + cx, v = f b + cy, r_u = gx - u, r_v = gy - v, k = data_weight^2 w^2 ;
+ *   E = sum k (G(r_u) + G(r_v)), G(r) = rho^2 r^2 / (r^2 + rho^2)          (the closure's data term, Geman-McClure) ;
+ *   s(r) = rho^4 / (r^2 + rho^2)^2, so G'(r) = 2 r s(r) ; per residual with Jacobian row J (of u or v):
+ *   g -= 2 k s(r) r J,  H += 2 k s(r) J^T J                                 (H positive semi-definite: the IRLS form).
+ * The parameters perturb the camera frame, p' = exp([omega]x) p + dt, so
+ *   du/dp = (f/pz, 0, -f a/pz), dv/dp = (0, f/pz, -f b/pz), dp/domega = -[p]x (rows (0, pz, -py), (-pz, 0, px), (py, -px, 0)),
+ *   dp/ddt = I, du/df = a, dv/df = b, du/dcx = 1, dv/dcy = 1, every other entry 0 ;
+ * and a step d means R' = exp([omega]x) R, t' = exp([omega]x) t + dt (Rodrigues in float64; below |omega|^2 = 1e-24 with
+ * sin(x)/x = 1 and (1 - cos x)/x^2 = 1/2), f' = f + df, c' = c + dc.
+ * count = the number of points with w != 0.  A view with a counted point at pz <= 1e-6 is "behind": E = +inf, and g and H are
+ * not defined (mvfit_camera_normal_eqs writes NaN).  The points are summed strided over 256 threads, per wave and then in
+ * wave order: a view's results depend on nothing but that view's inputs and B.
+ *
+ * mvfit_camera_normal_eqs: E[V], g[V,9] or NULL, H[V,9,9] (full, symmetric) or NULL, count[V] int32 or NULL, all dev out.
+ * MVFIT_E_ARG: a NULL joints / cams / E, rho not finite and > 0, data_weight not finite and >= 0.
+ *
+ * mvfit_refine_cameras: Levenberg-Marquardt per view, the whole loop on the device.  free = the ascending list of the parameters
+ * named by free_mask (bit 0: omega, bit 1: dt, bit 2: f, bit 3: cx and cy).
+ *   E, g, H at theta ; E0 = E ; lam = lambda0 ; it = acc = 0
+ *   while it < max_iter:
+ *       it += 1
+ *       A = H[free, free] with its diagonal multiplied by (1 + lam)
+ *       Cholesky of A ; a pivot <= 0 (or not a number):  lam *= 10 ; continue
+ *       d = -A^-1 g[free] ; theta' = step(theta, d)
+ *       E' at theta'                                        (+inf when behind)
+ *       if E' < E:  dec = E - E' ; theta = theta' ; E = E' ; g, H at theta ; lam = max(lam / 10, 1e-9) ; acc += 1
+ *                   if dec <= ftol * max(E, 1): status 0, stop
+ *       else:       lam *= 10 ; if lam > 1e12: status 2, stop
+ *   the loop left by it == max_iter: status 1
+ * E' of a candidate and E of the evaluation at the same camera are one summation, hence one number.  A view is skipped - its
+ * 15 output doubles are the input's bits - with status 3 when its bit is set in fixed_views, else status 4 when
+ * count < min_points, else status 5 when it is behind at the start.
+ *   cams_out[V,15] dev out (cams_out == cams_in is allowed) ; report[V,8] float64 dev out:
+ *   (E0, E1, it, acc, status, count, lam, 0) per view, E1 the energy at the returned camera.
+ * MVFIT_E_ARG, the message naming the field: a NULL joints / cams_in / opts / cams_out / report, size below the struct's,
+ * free_mask 0 or above 15, max_iter outside 1..64, min_points < 1, rho not finite and > 0, data_weight not finite and >= 0,
+ * lambda0 not finite and > 0, ftol not >= 0.  Bits of fixed_views at or above V are ignored. */
+typedef struct mvfit_camera_refine_opts {
+    uint32_t size;                 /* sizeof of this struct at the caller, as in mvfit_term_mix */
+    uint32_t free_mask;            /* bit 0: omega, 1: dt, 2: f, 3: c */
+    uint32_t fixed_views;          /* bit v: view v is returned as given */
+    int32_t max_iter;              /* 1..64 */
+    int32_t min_points;            /* >= 1 */
+    float rho, data_weight;
+    double lambda0, ftol;          /* > 0 ; >= 0 */
+} mvfit_camera_refine_opts;
+int mvfit_camera_normal_eqs(mvfit_ctx* ctx, const float* joints, const double* cams, float rho, float data_weight, double* E,
+                            double* g, double* H, int32_t* count);
+int mvfit_refine_cameras(mvfit_ctx* ctx, const float* joints, const double* cams_in, const mvfit_camera_refine_opts* opts,
+                         double* cams_out, double* report);
+
 /* Per-frame initial guess, stage 1 for single-view input (code/utils/init_guess.py:54-74): the depth guess that replaces
  * the triangulation when a frame has ONE view - the model's rest-pose keypoints pushed along the camera's z axis by
  * est_d = fx * (torso height in camera space) / (torso height in the image) and mapped back with inv(extri); the

@@ -72,6 +72,13 @@ class TermMix(C.Structure):
                 ('sil_w_out', C.c_float), ('sil_sigma', C.c_float), ('vertex_targets', C.c_float)]
 
 
+class CameraRefineOpts(C.Structure):
+    """mvfit_camera_refine_opts (include/mvfit.h): the Levenberg-Marquardt loop of mvfit_refine_cameras."""
+    _fields_ = [('size', C.c_uint32), ('free_mask', C.c_uint32), ('fixed_views', C.c_uint32), ('max_iter', C.c_int32),
+                ('min_points', C.c_int32), ('rho', C.c_float), ('data_weight', C.c_float), ('lambda0', C.c_double),
+                ('ftol', C.c_double)]
+
+
 TERM_RECORD_FLOATS = 516      # MVFIT_TERM_RECORD_FLOATS
 
 EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'mvfit_set_problems', 'mvfit_set_joints3d',
@@ -81,7 +88,8 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_associate_views', 'mvfit_set_silhouettes', 'mvfit_silhouettes_read', 'mvfit_silhouette_loss',
            'mvfit_set_silhouette_term', 'mvfit_set_silhouette_occluders', 'mvfit_silhouette_occluders_read',
            'mvfit_silhouette_hidden', 'mvfit_round_graph_info', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
-           'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge']
+           'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge',
+           'mvfit_camera_normal_eqs', 'mvfit_refine_cameras']
 
 
 def load(path=None):
@@ -143,6 +151,10 @@ def load(path=None):
     lib.mvfit_triangulate.restype = C.c_int
     lib.mvfit_associate_views.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp]
     lib.mvfit_associate_views.restype = C.c_int
+    lib.mvfit_camera_normal_eqs.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
+    lib.mvfit_camera_normal_eqs.restype = C.c_int
+    lib.mvfit_refine_cameras.argtypes = [vp, vp, vp, C.POINTER(CameraRefineOpts), vp, vp]
+    lib.mvfit_refine_cameras.restype = C.c_int
     lib.mvfit_depth_guess.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.mvfit_depth_guess.restype = C.c_int
     lib.mvfit_umeyama.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]

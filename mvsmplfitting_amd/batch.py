@@ -41,6 +41,7 @@ from .init_guess import init_guess_batch, initial_params
 from .scene_fit import refine_scenes
 from .sequence import fit_sequences
 from .silhouette import refine_fit, refine_fit_occluded
+from .calibrate import camera_matrices, refine_rig
 from .joint_refine import refine_joint
 from .temporal import smooth_sequences
 
@@ -421,11 +422,46 @@ def refine_serial_joint(eng, xf, stage, cfg, serial, cams, frames, problems, rig
     return out, report
 
 
+CAMERA_REFINE_DEFAULTS = dict(sweeps=2, anchor=0, free='extrinsics', min_points=34)
+
+
+def check_refine_cameras(cfg, is_seq=False, use_3d=False, scene_collision=None, silhouettes=None, temporal=None, joint=None):
+    """The refine_cameras option of fit_folder -> its dict with the defaults filled in; ValueError for what is not built."""
+    if not isinstance(cfg, dict):
+        raise ValueError('refine_cameras: a dict with any of the keys %s' % sorted(CAMERA_REFINE_DEFAULTS))
+    unknown = set(cfg) - set(CAMERA_REFINE_DEFAULTS)
+    if unknown:
+        raise ValueError('refine_cameras: unknown keys %s' % sorted(unknown))
+    for name, on in (('is_seq', is_seq), ('use_3d', use_3d), ('scene_collision', scene_collision is not None),
+                     ('silhouettes', silhouettes is not None), ('temporal', temporal is not None), ('joint', joint is not None)):
+        if on:
+            raise ValueError('refine_cameras with %s is not built' % name)
+    out = dict(CAMERA_REFINE_DEFAULTS, **cfg)
+    if int(out['sweeps']) < 1 or int(out['min_points']) < 1:
+        raise ValueError('refine_cameras: sweeps and min_points must be >= 1')
+    if out['free'] not in ('extrinsics', 'extrinsics+focal', 'all'):
+        raise ValueError("refine_cameras: free must be 'extrinsics', 'extrinsics+focal' or 'all'")
+    return out
+
+
+def refine_serial_cameras(eng, xf, stage, cfg, serial, rig, gt_xy, conf, intris, result_folder):
+    """refine_rig on a serial's whole batch after its fit (the engine holds the serial's problems under ``rig``) -> (params,
+    report, (extris [V,4,4], intris [V,3,3])); writes <result_folder>/<serial>/cameras_refined.txt.  The engine is left with
+    the refined rig, so the vertices and overlays that follow are those of the refined fit."""
+    xr, cams15, report = refine_rig(eng, xf, stage, rig, gt_xy, conf, sweeps=int(cfg['sweeps']), anchor=cfg['anchor'],
+                                    free=cfg['free'], min_points=int(cfg['min_points']))
+    ex, K = camera_matrices(cams15, intris)
+    d = os.path.join(result_folder, serial)
+    os.makedirs(d, exist_ok=True)
+    iof.save_camera_para(os.path.join(d, 'cameras_refined.txt'), ex, K)
+    return xr, report, (ex, K)
+
+
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
                save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
-               silhouettes=None, temporal=None, joint=None):
+               silhouettes=None, temporal=None, joint=None, refine_cameras=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -495,7 +531,16 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     single options.  The serial's result gains ``joint_report`` (refine_joint's, plus images and mask_size with a silhouette
     part), ``timing`` a 'joint' entry, and ``final_loss`` is the report's loss.  ValueError together with any of the three
     single options, with is_seq=True, for a scene part without persons=, fewer than two parts, unknown keys and non-positive
-    numbers."""
+    numbers.
+    refine_cameras: None, or dict(sweeps=2, anchor=0, free='extrinsics', min_points=34) - after the serial's batched fit the
+    rig is refined against the fitted bodies of the serial's whole batch and the bodies are refitted under it, with the last
+    stage (calibrate.refine_rig; anchor: the view kept as the camera file gives it, or None).  Single-person and persons=
+    path alike.  The result files, meshes and overlays come from the refined fit and rig; <result_folder>/<serial>/
+    cameras_refined.txt is written in the camera file's layout (its intrinsics are the file's with f in [0,0] and [1,1] and c
+    in [:2,2]); the serial's result gains ``camera_report`` (refine_rig's) and ``cameras`` = (extris, intris), ``timing`` a
+    'cameras' entry, and ``final_loss`` is the report's loss.  The next serial starts from the camera file again.  Not built,
+    ValueError before any engine work: together with is_seq, use_3d, scene_collision, silhouettes, temporal or joint; also
+    for unknown keys."""
     import time as _time
 
     def _tick(key, t0):
@@ -529,6 +574,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision, multi) if silhouettes is not None else None
     tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
     joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal) if joint is not None else None
+    cam_cfg = (check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint)
+               if refine_cameras is not None else None)
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -737,6 +784,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             xf = xr.to(xf.dtype)
             final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
             _t = _tick('joint', _t)
+        camera_report = cameras = None
+        if cam_cfg is not None:
+            xr, camera_report, cameras = refine_serial_cameras(eng, xf, stages_for(False)[-1], cam_cfg, serial, rig, gt_xy, conf,
+                                                               it, result_folder)
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(camera_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('cameras', _t)
         full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
         xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
         res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
@@ -765,6 +819,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             out['joint_report'] = joint_report
         if association is not None:
             out['association'] = association
+        if camera_report is not None:
+            out['camera_report'], out['cameras'] = camera_report, cameras
         _t = _tick('write', _t)
         if save_images:
             palette = np.asarray(SCENE_PALETTE, np.float32)
@@ -887,6 +943,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 xf = xr.to(xf.dtype)
                 final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
                 _t = _tick('joint', _t)
+            camera_report = cameras = None
+            if cam_cfg is not None:
+                xr, camera_report, cameras = refine_serial_cameras(eng, xf, stages_for(False)[-1], cam_cfg, serial, rig, gt_xy,
+                                                                   conf, it, result_folder)
+                xf = xr.to(xf.dtype)
+                final = torch.as_tensor(camera_report['loss'], dtype=final.dtype, device=final.device)
+                _t = _tick('cameras', _t)
             full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
             xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
             res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
@@ -913,6 +976,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 results[serial]['temporal_report'] = temporal_report
             if joint_report is not None:
                 results[serial]['joint_report'] = joint_report
+            if camera_report is not None:
+                results[serial]['camera_report'], results[serial]['cameras'] = camera_report, cameras
             _t = _tick('write', _t)
             if save_images:
                 results[serial]['images'] = render_serial_images(
@@ -928,4 +993,4 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
 
 __all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
            'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes',
-           'check_joint', 'load_serial_masks', 'refine_serial_joint']
+           'check_joint', 'load_serial_masks', 'refine_serial_joint', 'check_refine_cameras', 'refine_serial_cameras']

@@ -64,6 +64,13 @@ size_t assoc_head_bytes();
 hipError_t launch_associate_group(const float* kps, const int32_t* count, const double* intris, const double* extris, int f0,
                                   int nf, int V, int Nmax, double max_cost, int min_joints, int min_views, void* ws,
                                   double* cost_out, int32_t* labels, int32_t* num_clusters, hipStream_t stream);
+hipError_t launch_camera_normal_eqs(const float* joints, const float* gt_xy, const float* w_conf, int B, int V,
+                                    const double* cams, float rho, float data_weight, double* E, double* g, double* H,
+                                    int32_t* count, hipStream_t stream);
+hipError_t launch_camera_refine(const float* joints, const float* gt_xy, const float* w_conf, int B, int V,
+                                const double* cams_in, uint32_t free_mask, uint32_t fixed_views, int max_iter, int min_points,
+                                float rho, float data_weight, double lambda0, double ftol, double* cams_out, double* report,
+                                hipStream_t stream);
 int scene_sdf_blocks(int nv);
 hipError_t launch_scene_boxes(const float* verts, int nv, int b0, int n, float factor, float4* box, float* local,
                               hipStream_t stream);

@@ -588,6 +588,46 @@ extern "C" int mvfit_associate_views(mvfit_ctx* c, int F, int V, int Nmax, const
     return MVFIT_OK;
 }
 
+// Camera refinement against held bodies (camera_refine.hip): one workgroup per view, no workspace, no host synchronisation.
+extern "C" int mvfit_camera_normal_eqs(mvfit_ctx* c, const float* joints, const double* cams, float rho, float data_weight,
+                                       double* E, double* g, double* H, int32_t* count) {
+    if (!c) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!joints || !cams || !E)
+        return fail(c, MVFIT_E_ARG, "mvfit_camera_normal_eqs: null %s", !joints ? "joints" : !cams ? "cams" : "E");
+    if (!std::isfinite(rho) || !(rho > 0.f)) return fail(c, MVFIT_E_ARG, "mvfit_camera_normal_eqs: rho = %g must be finite and > 0", (double)rho);
+    if (!std::isfinite(data_weight) || !(data_weight >= 0.f))
+        return fail(c, MVFIT_E_ARG, "mvfit_camera_normal_eqs: data_weight = %g must be finite and >= 0", (double)data_weight);
+    HIP_OK(c, hipSetDevice(c->device));
+    const hipError_t e = launch_camera_normal_eqs(joints, c->pb.gt, c->pb.wc, c->B, c->V, cams, rho, data_weight, E, g, H, count, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_camera_normal_eqs: launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_refine_cameras(mvfit_ctx* c, const float* joints, const double* cams_in, const mvfit_camera_refine_opts* o,
+                                    double* cams_out, double* report) {
+    if (!c) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    if (!joints || !cams_in || !o || !cams_out || !report)
+        return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: null %s",
+                    !joints ? "joints" : !cams_in ? "cams_in" : !o ? "opts" : !cams_out ? "cams_out" : "report");
+    if (o->size < sizeof(mvfit_camera_refine_opts))
+        return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: size %u < %zu", o->size, sizeof(mvfit_camera_refine_opts));
+    if (o->free_mask == 0u || o->free_mask > 15u) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: free_mask %u outside [1, 15]", o->free_mask);
+    if (o->max_iter < 1 || o->max_iter > 64) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: max_iter %d outside [1, 64]", o->max_iter);
+    if (o->min_points < 1) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: min_points %d < 1", o->min_points);
+    if (!std::isfinite(o->rho) || !(o->rho > 0.f)) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: rho = %g must be finite and > 0", (double)o->rho);
+    if (!std::isfinite(o->data_weight) || !(o->data_weight >= 0.f))
+        return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: data_weight = %g must be finite and >= 0", (double)o->data_weight);
+    if (!std::isfinite(o->lambda0) || !(o->lambda0 > 0.0)) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: lambda0 = %g must be finite and > 0", o->lambda0);
+    if (!(o->ftol >= 0.0)) return fail(c, MVFIT_E_ARG, "mvfit_refine_cameras: ftol = %g must be >= 0", o->ftol);
+    HIP_OK(c, hipSetDevice(c->device));
+    const hipError_t e = launch_camera_refine(joints, c->pb.gt, c->pb.wc, c->B, c->V, cams_in, o->free_mask, o->fixed_views, o->max_iter,
+                                              o->min_points, o->rho, o->data_weight, o->lambda0, o->ftol, cams_out, report, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "mvfit_refine_cameras: launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
 extern "C" int mvfit_depth_guess(mvfit_ctx* c, int B, const double* rest_joints, const double* extri, const double* intri,
                                  const float* keypoints, double* joints3d) {
     if (!c) return MVFIT_E_ARG;

@@ -706,6 +706,54 @@ class MvFit:
             int(min_views), cost.data_ptr() if return_cost else None, labels.data_ptr(), num.data_ptr()))
         return (labels, num, cost) if return_cost else (labels, num)
 
+    def _cams15(self, cams):
+        if isinstance(cams, (tuple, list)) and len(cams) == 4:
+            cams = pack_cameras(cams)
+        return self._f64(cams, (self.V, 15))
+
+    def camera_normal_eqs(self, joints, cams15, rho=100., data_weight=1., need_grad=True):
+        """Energy of the keypoint data term per view as a function of the view's camera, with its gradient and Gauss-Newton
+        matrix over the 9 camera parameters (include/mvfit.h:mvfit_camera_normal_eqs).  joints [B,17,3] (closure(...,
+        want_joints=True)), cams15 [V,15] float64 (pack_cameras) or the (R, t, f, c) tuple; gt_xy and w_conf are those of
+        set_problems.  Returns dict(E[V], count[V] int32, g[V,9]?, H[V,9,9]?) of CUDA tensors, float64."""
+        j = self._dev(joints, (self.B, 17, 3))
+        cm = self._cams15(cams15)
+        V = self.V
+        out = dict(E=torch.empty(V, dtype=torch.float64, device=self.device),
+                   count=torch.empty(V, dtype=torch.int32, device=self.device))
+        g = torch.empty(V, 9, dtype=torch.float64, device=self.device) if need_grad else None
+        H = torch.empty(V, 9, 9, dtype=torch.float64, device=self.device) if need_grad else None
+        self._check(self._lib.mvfit_camera_normal_eqs(
+            self._ctx, j.data_ptr(), cm.data_ptr(), float(rho), float(data_weight), out['E'].data_ptr(),
+            g.data_ptr() if need_grad else None, H.data_ptr() if need_grad else None, out['count'].data_ptr()))
+        if need_grad:
+            out['g'], out['H'] = g, H
+        return out
+
+    def refine_cameras(self, joints, cams, free='extrinsics', fixed_views=(), max_iter=20, min_points=34, rho=100.,
+                       data_weight=1., lambda0=1e-3, ftol=1e-12):
+        """Move the cameras against held bodies: Levenberg-Marquardt per view on the device (include/mvfit.h:
+        mvfit_refine_cameras).  joints [B,17,3]; cams: the (R, t, f, c) tuple of set_problems or a [V,15] array; free:
+        'extrinsics' | 'extrinsics+focal' | 'all' (or the free_mask itself); fixed_views: views returned as given.  Returns
+        (cams15 [V,15] float64 tensor, report [V,8] float64 tensor: E0, E1, it, acc, status, count, lam, 0)."""
+        j = self._dev(joints, (self.B, 17, 3))
+        cm = self._cams15(cams)
+        if isinstance(free, str) and free not in FREE_MASKS:
+            raise MvFitError('free must be one of %s, got %r' % (sorted(FREE_MASKS), free))
+        mask = FREE_MASKS[free] if isinstance(free, str) else free
+        fixed = 0
+        for v in fixed_views:
+            if not 0 <= int(v) < self.V:
+                raise MvFitError('fixed view %r outside [0, %d)' % (v, self.V))
+            fixed |= 1 << int(v)
+        o = _lib.CameraRefineOpts(C.sizeof(_lib.CameraRefineOpts), int(mask), fixed, int(max_iter), int(min_points), float(rho),
+                                  float(data_weight), float(lambda0), float(ftol))
+        out = torch.empty(self.V, 15, dtype=torch.float64, device=self.device)
+        report = torch.empty(self.V, 8, dtype=torch.float64, device=self.device)
+        self._check(self._lib.mvfit_refine_cameras(self._ctx, j.data_ptr(), cm.data_ptr(), C.byref(o), out.data_ptr(),
+                                                   report.data_ptr()))
+        return out, report
+
     def depth_guess(self, rest_joints, extri, intri, keypoints):
         """joints3d [B,17,3] float64 for frames seen by ONE camera (include/mvfit.h:mvfit_depth_guess; reference
         init_guess.py:54-74): rest_joints [17,3] float64, extri [4,4], intri [3,3] float64, keypoints [B,17,3]
@@ -909,6 +957,34 @@ class MvFit:
                                                  C.byref(n2)))
         return dict(vertex_pass_ms=a.value, vertex_pass_launches=n1.value,
                     step_ms=b.value, step_launches=n2.value)
+
+
+# free_mask of mvfit_refine_cameras by name (bit 0: omega, 1: dt, 2: f, 3: c)
+FREE_MASKS = {'extrinsics': 3, 'extrinsics+focal': 7, 'all': 15}
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def pack_cameras(cams):
+    """The (R[V,3,3], t[V,3], f[V], c[V,2]) tuple of set_problems as [V,15] float64 rows R (9, row-major), t (3), f, cx, cy:
+    the camera form of camera_normal_eqs / refine_cameras.  float32 values widen exactly."""
+    R, t, f, c = (np.asarray(_host(a), np.float64) for a in cams)
+    if R.ndim != 3:
+        raise ValueError('pack_cameras takes one rig [V,3,3], not per-problem cameras')
+    V = R.shape[0]
+    return np.concatenate([R.reshape(V, 9), t.reshape(V, 3), f.reshape(V, 1), c.reshape(V, 2)], axis=1)
+
+
+def unpack_cameras(cams15, dtype=np.float64):
+    """The inverse of pack_cameras: [V,15] -> (R[V,3,3], t[V,3], f[V], c[V,2]) NumPy arrays of ``dtype``."""
+    a = np.asarray(_host(cams15), np.float64)
+    if a.ndim != 2 or a.shape[1] != 15:
+        raise ValueError('cams15 must be [V, 15]')
+    V = a.shape[0]
+    return (a[:, :9].reshape(V, 3, 3).astype(dtype), a[:, 9:12].astype(dtype), a[:, 12].astype(dtype),
+            a[:, 13:15].astype(dtype))
 
 
 def pack_params(betas=None, global_orient=None, body_pose=None, transl=None, scale=None,

@@ -47,6 +47,24 @@ def load_camera_para(path):
     return np.array(extris), np.array(intris)
 
 
+def save_camera_para(path, extris, intris):
+    """The inverse of load_camera_para, in the layout of the 3DOH50K parameter file: per camera an index line, three
+    intrinsic rows, ``0 0``, the three upper extrinsic rows and a blank line.  Numbers are written with repr, so that
+    load after save returns the same bits."""
+    extris, intris = np.asarray(extris, np.float64), np.asarray(intris, np.float64)
+    if extris.ndim != 3 or extris.shape[1] < 3 or extris.shape[2] != 4 or intris.shape != (extris.shape[0], 3, 3):
+        raise ValueError('extris must be [V,4,4] (or [V,3,4]) and intris [V,3,3]')
+    with open(path, 'w') as f:
+        for v in range(extris.shape[0]):
+            f.write('%d\n' % v)
+            for row in intris[v]:
+                f.write(' '.join(repr(float(x)) for x in row) + ' \n')
+            f.write('0 0\n')
+            for row in extris[v, :3]:
+                f.write(' '.join(repr(float(x)) for x in row) + ' \n')
+            f.write('\n')
+
+
 def read_keypoints(path):
     with open(path) as f:
         data = json.load(f)
