@@ -578,6 +578,64 @@ int mvfit_vertex_target_loss(mvfit_ctx* ctx, const float* vertices, float* loss,
  * target set. */
 int mvfit_set_vertex_target_term(mvfit_ctx* ctx, int enable);
 
+/* ---- Scan loss: measured 3-D surface points against the posed body and back, with its gradient on the vertices
+ * (csrc/scan_loss.hip).  The reference has no term on scan data: this contract is the project's own.  A scan has no
+ * correspondences with the model; they are searched for at every evaluation.
+ *
+ * mvfit_set_scans keeps, once per scan set, up to max_points world points for each of num_bodies bodies.  Point i of body n
+ * takes part iff i < count[n] and its weight is > 0 (weights = NULL: every weight is 1).  A point that does not take part is
+ * never read and may hold anything, NaN included.  num_bodies = 0 clears the set (the other arguments are ignored).  Faces
+ * are the model's.
+ *
+ * mvfit_scan_loss evaluates at vertices[N,Nv,3] float32 (translation included, as mvfit_vertices returns them), N the set's.
+ * Distances are in the unit of the vertices, and so is sigma.  All fp32 arithmetic below is un-contracted (no FMA fusion).
+ *   Term S (scan to mesh).  For a point p and a face (a, b, c) with ab = b - a, ac = c - a in fp32: the closest point of the
+ *     triangle by region - with ap = p - a, bp = ap - ab, cp = ap - ac, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp,
+ *     d5 = ab.cp, d6 = ac.cp (dots as (x + y) + z), vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, the first
+ *     that matches of: vertex a (d1 <= 0, d2 <= 0): (v, w) = (0, 0); vertex b (d3 >= 0, d4 <= d3): (1, 0); edge ab (vc <= 0,
+ *     d1 >= 0, d3 <= 0): (d1 / (d1 - d3), 0); vertex c (d6 >= 0, d5 <= d6): (0, 1); edge ac (vb <= 0, d2 >= 0, d6 <= 0):
+ *     (0, d2 / (d2 - d6)); edge bc (va <= 0, d4 - d3 >= 0, d5 - d6 >= 0): (d5 - d6, d4 - d3) / ((d4 - d3) + (d5 - d6));
+ *     interior: (vb, vc) / ((va + vb) + vc); every quotient as a product with one fp32 reciprocal.  q = a + v ab + w ac, the
+ *     barycentrics of (a, b, c) are (b0, b1, b2) = ((1 - v) - w, v, w), and m = |q - p|^2 is recomputed from
+ *     q - p = (v ab + w ac) - ap in fp32.  The winner is the face with the smallest fp32 m, ties to the lowest face index
+ *     (a face whose m is NaN never wins; with no winner the point reports -1 and contributes 0).
+ *     rho(m) = m when sigma <= 0, else sigma^2 m / (sigma^2 + m), in float64 from the fp32 m.  S_n = sum_p w_p rho(m_p).
+ *     The gradient goes to the winner's three vertices with the barycentrics held fixed: w_p rho'(m) 2 (q - p) b_k - exact
+ *     wherever the closest point is unique.
+ *   Term M (mesh to scan).  For every vertex j of the model the participating point with the smallest fp32
+ *     m = |v_j - p|^2 (differences, products and the sum (x + y) + z each rounded to fp32), ties to the lowest point index; a
+ *     body without participating points contributes 0 and reports -1.  Same rho; M_n = sum_j rho(m_j), the gradient
+ *     rho'(m) 2 (v_j - p) goes to the vertex.
+ *   loss[n] = float32(w_s2m S_n + w_m2s M_n), g_vertices = w_s2m dS/dV + w_m2s dM/dV summed in float64 and rounded to float32
+ *     once.  A term whose weight is 0 is not searched; its winner array, when asked for, is filled with -1.  The gradient
+ *     flows through the vertex positions only: points, winners and barycentrics are constants.
+ *   search: 0 (auto) or 1 (exhaustive: every point against every face).  Auto skips faces whose bounding sphere lies beyond
+ *     a conservative bound of the point's distance; it returns the bits of the exhaustive search.
+ *   Determinism: no float atomics; a body's loss, gradient and winners are bit-identical alone, in any batch, at any position
+ *     and from run to run; a body without participating points gets, at w_m2s = 0, loss 0 and an exactly zero gradient.
+ *     Term S's many-points-to-one-vertex sum is a 64-bit integer accumulation in units of 2^-32 of the vertices' unit (each
+ *     point's contribution to a vertex coordinate is rounded to that unit; the sum of one coordinate must stay below 2^31
+ *     units of the vertices in magnitude).  S_n and M_n are float64 sums whose order is fixed by max_points, Nv and the
+ *     kernel shapes (256 points or vertices per workgroup: a wave64 butterfly, the waves, then the workgroups in order),
+ *     never by N.
+ *
+ * points[N,max_points,3] float32 dev or host; count[N] int32 host; weights[N,max_points] float32 host or NULL.  loss[N] dev
+ * out; g_vertices[N,Nv,3] dev out or NULL; nearest_face[N,max_points] int32 dev out or NULL (-1 for a point that does not
+ * take part); nearest_point[N,Nv] int32 dev out or NULL.  mvfit_set_scans waits for the stream; mvfit_scan_loss is
+ * asynchronous.
+ * Workspace, kept in the ctx and reused - every address kept - by a second set of the same (N, max_points):
+ *     N * (32 max_points + 4 + 64 Nf + 16 ceil(Nf / 8) + 24 Nv + 8 ceil(max_points / 256) + 8 ceil(Nv / 256))   bytes
+ *     (points, weights and packed points; counts; face records; seed vertices; the fixed-point accumulators; the partials of
+ *     both terms), each part rounded up to 256 bytes.
+ * MVFIT_E_ARG: a NULL required pointer, sizes out of range (N <= 65535, max_points >= 1, N max_points <= 2^28), a count[n]
+ * outside [0, max_points], a negative or non-finite weight below count[n], a negative or non-finite w_s2m, w_m2s or sigma,
+ * search > 1, num_bodies other than the set's.  MVFIT_E_STATE: mvfit_scan_loss without a scan set; mvfit_set_scans on a
+ * model without (valid) faces. */
+int mvfit_set_scans(mvfit_ctx* ctx, int num_bodies, int max_points, const float* points, const int32_t* count,
+                    const float* weights);
+int mvfit_scan_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float w_s2m, float w_m2s, float sigma, uint32_t search,
+                    float* loss, float* g_vertices, int32_t* nearest_face, int32_t* nearest_point);
+
 /* ---- Term mix: the scene, silhouette and vertex-target terms together behind coll_loss_weight ----
  * With the mix on, a weight set with coll_loss_weight = w > 0 adds to problem j
  *   pen_j = w^2 * (scene * S_sc^2 + silhouette * L_sil + vertex_targets * L_vt),

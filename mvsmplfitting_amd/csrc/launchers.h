@@ -8,8 +8,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace mvfit {
 
+struct ScanState;
 struct DevModel;
 struct DevPose;
 struct DevProblems;
@@ -85,5 +88,13 @@ hipError_t launch_scene_group(const DevProblems& Q, const int32_t* tab, int num_
                               const float* verts, const double* nrm, int Nv, const int32_t* faces, int Nf, const float* points,
                               int num_points, int H, int W, const uint8_t* in, uint8_t* out, int32_t* face_id, int32_t* body_id,
                               void* ws_mem, hipStream_t stream);
+// The scan loss (scan_loss.hip; the state: scan_loss.h).  Both return an MVFIT_* code and, on failure, a message in err; the
+// caller (mvfit_scan.hip) has checked the arguments.  scan_set: points [N][Pmax][3] dev or host, count [N] and weights
+// [N][Pmax] (or null) host.  scan_loss: faces [nf][3] dev, the model's; exhaustive = the search without the cull.
+int scan_set(ScanState& S, int nv, int nf, int N, int Pmax, const float* points, const int32_t* count, const float* weights,
+             hipStream_t stream, std::string& err);
+int scan_loss(ScanState& S, const int32_t* faces, const float* vertices, float w_s2m, float w_m2s, float sigma, bool exhaustive,
+              float* loss, float* g_vertices, int32_t* nearest_face, int32_t* nearest_point, hipStream_t stream,
+              std::string& err);
 
 }  // namespace mvfit

@@ -18,6 +18,7 @@
 #include "fit_plan.h"
 #include "launchers.h"
 #include "round_term.h"
+#include "scan_loss.h"
 #include "silhouette.h"
 #include "term_mix.h"
 #include "vertex_target.h"
@@ -90,6 +91,8 @@ struct mvfit_ctx {
     // mask set of the silhouette term (mvfit_set_silhouettes, silhouette.hip): fields, contours, tables and work areas
     SilState sil;
     SilTerm silt;
+    // scan set of the scan loss (mvfit_set_scans, scan_loss.hip): points, face records and work areas
+    ScanState scan;
     // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
     VtxTargets vt;
     // the weighted sum of the scene, silhouette and vertex-target terms (mvfit_set_term_mix, term_mix.hip)

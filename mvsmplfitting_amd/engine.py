@@ -127,6 +127,7 @@ class MvFit:
         self._sil_term = False
         self._vt_term = False
         self._mix = None                         # the shares of set_term_mix while it is on
+        self._scan_shape = None                  # (N, Pmax) of set_scans while a scan set is present
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -551,6 +552,64 @@ class MvFit:
         hidden = torch.empty(self._sil_shape[0], self.nv, dtype=torch.uint8, device=self.device)
         self._check(self._lib.mvfit_silhouette_hidden(self._ctx, v.data_ptr(), int(v.shape[0]), hidden.data_ptr()))
         return hidden
+
+    # ------------------------------------------------------------------ scan loss (include/mvfit.h:mvfit_set_scans)
+    def set_scans(self, points, count=None, weights=None):
+        """Keep a scan set (include/mvfit.h:mvfit_set_scans): points [N,Pmax,3] world points (tensor or array; copied), count[N]
+        = how many of a body's rows are points (None: all Pmax), weights [N,Pmax] finite and >= 0 (None: 1).  A row at or
+        beyond count[n], or with weight 0, takes no part and may hold anything.  The set stays in the engine until
+        clear_scans() or the next set; a second set of the same (N, Pmax) keeps the library's buffers."""
+        p = self._dev(points)
+        if p.dim() != 3 or p.shape[2] != 3:
+            raise MvFitError('points must be [N, Pmax, 3], got %r' % (tuple(p.shape),))
+        N, Pmax = int(p.shape[0]), int(p.shape[1])
+        if N == 0:
+            return self.clear_scans()
+        cnt = np.full(N, Pmax, np.int32) if count is None else _i32(np.asarray(count).reshape(-1))
+        if cnt.size != N:
+            raise MvFitError('count needs one entry per body (%d), got %d' % (N, cnt.size))
+        w = None
+        if weights is not None:
+            w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else weights
+            w = _f32(np.asarray(w))
+            if w.shape != (N, Pmax):
+                raise MvFitError('weights must be [%d, %d], got %r' % (N, Pmax, tuple(w.shape)))
+        self._check(self._lib.mvfit_set_scans(self._ctx, N, Pmax, p.data_ptr(), cnt.ctypes.data_as(_lib._ip),
+                                              w.ctypes.data_as(_lib._fp) if w is not None else None))
+        self._scan_shape = (N, Pmax)
+
+    def clear_scans(self):
+        """Remove the scan set of set_scans."""
+        self._check(self._lib.mvfit_set_scans(self._ctx, 0, 0, None, None, None))
+        self._scan_shape = None
+
+    def scan_loss(self, vertices, w_s2m=1.0, w_m2s=0.0, sigma=0.0, need_grad=True, return_nearest=False, search='auto'):
+        """The scan loss of the scan set at vertices[N,Nv,3], translation included (include/mvfit.h:mvfit_scan_loss): w_s2m
+        weighs the squared distance of every scan point to the nearest point of the body's surface, w_m2s that of every
+        vertex to its nearest scan point; sigma > 0 (in the vertices' unit) makes both robust.  search: 'auto' or
+        'exhaustive' (the same bits).  Returns (loss[N], g_vertices[N,Nv,3] or None) and, with return_nearest, the int32
+        nearest_face [N,Pmax] and nearest_point [N,Nv] (-1: none, or a term with weight 0)."""
+        if search not in ('auto', 'exhaustive'):
+            raise MvFitError("search must be 'auto' or 'exhaustive', got %r" % (search,))
+        v = self._dev(vertices)
+        if v.dim() != 3 or v.shape[1] != self.nv or v.shape[2] != 3:
+            raise MvFitError('vertices must be [N, %d, 3], got %r' % (self.nv, tuple(v.shape)))
+        N = int(v.shape[0])
+        loss = torch.empty(N, device=self.device)
+        g = torch.empty_like(v) if need_grad else None
+        nf = npt = None
+        if return_nearest:
+            shape = self._scan_shape or (N, 1)
+            nf = torch.empty(N, shape[1], dtype=torch.int32, device=self.device)
+            npt = torch.empty(N, self.nv, dtype=torch.int32, device=self.device)
+        self._check(self._lib.mvfit_scan_loss(self._ctx, v.data_ptr(), N, float(w_s2m), float(w_m2s), float(sigma),
+                                              1 if search == 'exhaustive' else 0, loss.data_ptr(),
+                                              g.data_ptr() if need_grad else None,
+                                              nf.data_ptr() if return_nearest else None,
+                                              npt.data_ptr() if return_nearest else None))
+        if return_nearest:
+            return loss, g, nf, npt
+        return loss, g
 
     def round_graph_info(self, drop=False):
         """dict(builds = round graphs captured on this engine so far, occluder_buffers = the device addresses of z_occ, z_own
