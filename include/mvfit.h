@@ -278,9 +278,10 @@ int mvfit_fit(mvfit_ctx* ctx, const mvfit_weights* stage_weights, const mvfit_lb
  *            read them; resident pass - the LARGEST number of (problem, round) operand sets any one of its workgroups found
  *            overwritten (every workgroup reports; such a round is skipped by that workgroup, never computed from another
  *            round's operands);
- *   out4[3]  waits given up (expected 0): gate kernels / resident workgroups that waited 20 ms for operands and left + problems
- *            whose optimiser waited 20 ms for the ring's back-pressure and stopped honouring it + service rounds (SDF term,
- *            mvfit_options::sdf_service) whose problem waited 200 ms for the term's answer (mvfit_fit then fails).
+ *   out4[3]  waits given up (expected 0): gate kernels that waited 3 ms and resident workgroups that waited 20 ms for operands
+ *            and left + problems whose optimiser waited 20 ms for the ring's back-pressure and stopped honouring it + service
+ *            rounds (SDF term, mvfit_options::sdf_service) whose problem waited 200 ms for the term's answer - once per problem:
+ *            its later rounds do not wait again (mvfit_fit then fails).
  * A non-zero out4[2] or out4[3] means "every closure round got its full vertex pass" does not hold for that fit (the fitted
  * parameters never depend on the passes); with mvfit_options::resident_pass = -1 the ctx then runs its later fits with
  * per-round launches (until mvfit_set_options is called). */

@@ -470,10 +470,12 @@ __global__ __launch_bounds__(STEP_NT) void fit_persistent_kernel(DevModel M, con
         if (L.sh_stage >= pause_stage) { paused = true; break; }
     }
     store_block16(F.opt + b, &L.opt, sizeof(OptBlock), tid);
-    // the next problem of the batch, if the launch has a queue and this one is finished (a paused problem or the round cap ends
-    // the workgroup): decided here, before the row says "nothing more comes"
+    // the next problem of the batch, if the launch has a queue and this one has left it - finished, or paused at the stage
+    // boundary of a lead phase (what the tail needs of a paused problem is stored below, before the row moves on; every row
+    // pauses there, so a row that ended instead would leave the queue's problems without their lead stages).  The round cap
+    // ends the workgroup.  Decided here, before the row says "nothing more comes"
     int b_next = -1;
-    if (QUEUE && queue && done) {                                       // uniform
+    if (QUEUE && queue && (done || paused)) {                           // uniform
         if (tid == 0) L.sh_next = atomicAdd(queue, 1);
         __syncthreads();
         if (L.sh_next < b_end) b_next = L.sh_next;

@@ -23,9 +23,12 @@ struct SdfAdj;
 hipError_t launch_vertex_pass(const DevModel& M, const DevPose& P, int B, float* verts, int pass_kernel,
                               hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 hipError_t vertex_pass_configure();
-hipError_t launch_pass_gate(const DevPose& P, int b_lo, int B, hipStream_t stream);
+// gate / gate_round (service rounds of a fit with the SDF term): the gate kernel copies the problems' gate words into the round's own
+// copy, which the term's kernels behind the pass read
+hipError_t launch_pass_gate(const DevPose& P, int b_lo, int B, hipStream_t stream, const int* gate = nullptr, int* gate_round = nullptr);
 hipError_t launch_vertex_pass_resident(const DevModel& M, const ResidentArgs& RA, int tpw, hipStream_t stream);
-hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* verts, int B, const int32_t* faces, int num_faces,
+// B: the problems the grid covers; layout_B >= B: the problems `entries` and `cull` were allocated for (sdf_layout.h)
+hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* verts, int B, int layout_B, const int32_t* faces, int num_faces,
                            int G, const int* gate, SdfBox* box, float4* samp, void* entries, SdfAdj* adj, hipStream_t stream,
                            void* cull, unsigned* answer_tag = nullptr, unsigned answer = 0u, const unsigned long long* box_parts = nullptr);
 size_t sdf_cull_bytes(int B, int num_faces);

@@ -429,6 +429,7 @@ int mvfit::ensure_sdf_buffers(mvfit_ctx* c) {
     HIP_OK(c, hipMemset(work + sdf_ticket_offset(c->B, c->nv), 0, (size_t)c->B * sizeof(int)));
     c->pb.sdf_entries = work;
     HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_adj, (size_t)c->B * sizeof(SdfAdj)));
+    HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_gate_round, (size_t)c->B * 4));
     HIP_OK(c, c->problem_mem.alloc(&c->pb.sdf_boxpart, (size_t)c->Bpad * c->M.ntiles * 6 * 8));
     return MVFIT_OK;
 }
@@ -472,7 +473,7 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
                                        s.rec.rec, s.rec.parts, s.rec.sums, st);
             break;
         case STEP_SDF:
-            e = launch_sdf_term(M, P, verts, B, s.sdf.faces, s.sdf.num_faces, s.sdf.grid, gate, s.sdf.box, static_cast<float4*>(s.sdf.samp),
+            e = launch_sdf_term(M, P, verts, B, B, s.sdf.faces, s.sdf.num_faces, s.sdf.grid, gate, s.sdf.box, static_cast<float4*>(s.sdf.samp),
                                 s.sdf.entries, s.sdf.adj, st, s.sdf.cull, nullptr, 0u, box_part);
             break;
         default:

@@ -35,6 +35,7 @@ struct ProblemBufs {
     float4* sdf_samp = nullptr;        // [B][nv]
     void* sdf_entries = nullptr;       // [B][nv] entry list
     SdfAdj* sdf_adj = nullptr;         // [B]
+    int* sdf_gate_round = nullptr;     // [B] service rounds: the gate words as the round's gate kernel found them (what the term's kernels read)
     unsigned long long* sdf_boxpart = nullptr;   // [B][ntiles][6] the vertex pass's own per-tile keys of the term's bounding box (single-chunk split kernel)
 };
 

@@ -250,6 +250,8 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
             // the problems outside this sub-batch stay shut: the term's kernels cover all problems up to b_hi)
             HIP_OK(c, hipMemsetAsync(c->F.sdf_tag, 0, (size_t)c->Bpad * 4, c->stream));
             HIP_OK(c, hipMemsetAsync(c->F.sdf_gate, 0, (size_t)B * 4, c->stream));
+            // (the rounds' own copies of the gates, written by the gate kernels for [b_lo, b_hi) and read by the term's kernels)
+            HIP_OK(c, hipMemsetAsync(c->pb.sdf_gate_round, 0, (size_t)B * 4, c->stream));
         }
         if (log_on) HIP_OK(c, hipMemsetAsync(c->vp_log.get(), 0, c->vp_log.size(), c->stream));      // (a profiled fit keeps the last sub-batch's stamps)
         HIP_OK(c, hipEventRecord(c->ev_init, c->stream));
@@ -299,7 +301,8 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
                 float* vout = c->pb.verts;
                 if (c->capture_verts && (int)r == c->capture_round) vout = c->capture_verts;      // test hook
                 if (sdf_service && pass_writes_box_parts(c, b_lo, b_hi)) P.box_part = c->pb.sdf_boxpart;      // (the term's box from the pass's tile keys)
-                hipError_t e = launch_pass_gate(P, b_lo, b_hi, c->pass_stream);
+                hipError_t e = launch_pass_gate(P, b_lo, b_hi, c->pass_stream, sdf_service ? c->F.sdf_gate : nullptr,
+                                                sdf_service ? c->pb.sdf_gate_round : nullptr);
                 hipEvent_t ea = nullptr, eb = nullptr;
                 if (c->profile && c->ev_vp.size() < 4096) {            // mvfit_profile: the dispatch's own begin / end stamps
                     hipEventCreate(&ea); hipEventCreate(&eb);
@@ -308,11 +311,12 @@ static int run_async(mvfit_ctx* c, const StageWeights& SW, const LbOpts& O, cons
                 if (e == hipSuccess) e = launch_vertex_pass(c->M, P, b_hi, vout, c->opt.pass_kernel, c->pass_stream, ea, eb);
                 if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "vertex pass launch: %s", hipGetErrorString(e));
                 if (sdf_service) {
-                    // the term at the round's vertices for the problems whose gate word is set (written by the optimiser in
-                    // front of the round's tag); transforms from the ring slot, float32 coefficients from the chained layout
+                    // the term at the round's vertices for the problems whose gate word was set (written by the optimiser in
+                    // front of the round's tag, copied for the round by its gate kernel); transforms from the ring slot, float32
+                    // coefficients from the chained layout.  The grid ends at b_hi; the work areas keep the layout of the batch
                     DevPose Ps = P;
                     Ps.coefT = c->P.coefT;
-                    e = launch_sdf_term(c->M, Ps, vout, b_hi, c->sdf_faces.as<int32_t>(), c->sdf_num_faces, c->sdf_grid, c->F.sdf_gate, c->pb.sdf_box,
+                    e = launch_sdf_term(c->M, Ps, vout, b_hi, B, c->sdf_faces.as<int32_t>(), c->sdf_num_faces, c->sdf_grid, c->pb.sdf_gate_round, c->pb.sdf_box,
                                         c->pb.sdf_samp, c->pb.sdf_entries, c->pb.sdf_adj, c->pass_stream, c->sdf_cull.get(), c->F.sdf_tag, r + 1u, P.box_part);
                     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "SDF term launch: %s", hipGetErrorString(e));
                 }

@@ -275,7 +275,7 @@ hipError_t launch_scene_term(const DevModel& M, const DevPose& P, const float* v
                        sdf_work_chunks(entries, B, M.nv));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_sdf_pullback(M, P, B, gate, null_box, entries, adj, stream);
+    return launch_sdf_pullback(M, P, B, B, gate, null_box, entries, adj, stream);
 }
 
 }  // namespace mvfit

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mvfit_device.h"
+#include "sdf_layout.h"
 
 namespace mvfit {
 
@@ -12,16 +13,17 @@ constexpr int SDF_ADJ_NT = 512;      // threads of an entry / pull-back workgrou
 struct SdfEntry { int v; float g[3]; };                                  // vertex, dS/dvertex
 static_assert(sizeof(SdfEntry) == 16, "entry layout");
 
-constexpr int SDF_NC = 16;           // vertex chunks per problem in the entry kernel (one workgroup each)
+// (SDF_NC, the vertex chunks per problem in the entry kernel - one workgroup each: sdf_layout.h)
 constexpr int SDF_NIT = 1;           // 64-vertex rows per wave of a chunk: nv <= SDF_NC * 8 waves * SDF_NIT * 64 = 8192
 
 // per (problem, vertex chunk): partial sums of S and of the box adjoint, entries written (at the chunk's own offset)
 struct SdfChunk { double S, gc0, gc1, gc2, gs; int cnt, pad; };
 static_assert(sizeof(SdfChunk) == 48, "chunk record");
 
-// the chunk records inside the work area behind `entries` (sdf_work_bytes(B, nv) bytes, layout: sdf_term.hip)
-SdfChunk* sdf_work_chunks(void* entries, int B, int nv);
-hipError_t launch_sdf_pullback(const DevModel& M, const DevPose& P, int B, const int* gate, const SdfBox* box, void* entries,
+// the chunk records inside the work area behind `entries` (sdf_work_bytes(layout_B, nv) bytes, layout: sdf_layout.h)
+SdfChunk* sdf_work_chunks(void* entries, int layout_B, int nv);
+// B: the problems the grid covers; layout_B >= B: the problems the work area was allocated for
+hipError_t launch_sdf_pullback(const DevModel& M, const DevPose& P, int B, int layout_B, const int* gate, const SdfBox* box, void* entries,
                                SdfAdj* adj, hipStream_t stream);
 
 }  // namespace mvfit

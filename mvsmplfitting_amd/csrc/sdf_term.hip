@@ -306,11 +306,7 @@ __global__ __launch_bounds__(SDF_NT) void sdf_sample_kernel(const float* __restr
 // lists overflow the workspace.
 // One counting sort per problem and round (count, scan, fill) builds both structures in one bin space.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int SDF_NB = 256;                         // projective bins per axis (ray structure)
-constexpr int SDF_NC3 = 64;                         // cells per axis (distance structure)
-constexpr int SDF_NBINS = SDF_NB * SDF_NB + SDF_NC3 * SDF_NC3 * SDF_NC3;
-constexpr int SDF_OFFS_LD = SDF_NBINS + 4;           // row of the offsets (NBINS + 1 used), 16-byte aligned
-constexpr int SDF_CULL_CAP = 64;                    // list entries per face the workspace holds
+// (SDF_NB, SDF_NC3, SDF_NBINS, SDF_OFFS_LD, SDF_CULL_CAP and the workspace's byte layout: sdf_layout.h)
 constexpr float SDF_CULL_DELTA = 2e-3f;
 constexpr int SDF_CULL_MIN_FACES = 4 * SDF_CH;      // below: the staged brute-force kernel
 
@@ -321,26 +317,24 @@ struct SdfCullWs {               // per-problem slices of one allocation
     int2* ent;                   // [B][CAP * F]  {face, its pad[0] as bits}
     int* flag;                   // [B]          1 = lists do not fit / a vertex outside the normalised box: walk all faces
 };
-static size_t cull_align(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t sdf_cull_bytes(int B, int num_faces) {
-    return cull_align((size_t)B * num_faces * sizeof(SdfTri)) + cull_align((size_t)B * SDF_OFFS_LD * 4) +
-           cull_align((size_t)B * SDF_NBINS * 4) + cull_align((size_t)B * SDF_CULL_CAP * num_faces * 8) + cull_align((size_t)B * 4);
-}
-size_t sdf_cull_zero_offset(int B, int num_faces) {          // the part that must be zero before the first round: cnt
-    return cull_align((size_t)B * num_faces * sizeof(SdfTri)) + cull_align((size_t)B * SDF_OFFS_LD * 4);
-}
-size_t sdf_cull_zero_bytes(int B) { return cull_align((size_t)B * SDF_NBINS * 4); }
+static_assert(sizeof(SdfTri) == SDF_TRI_BYTES && sizeof(int2) == 8, "records of sdf_layout.h");
+static size_t cull_align(size_t x) { return sdf_align256(x); }
+size_t sdf_cull_bytes(int B, int num_faces) { return sdf_cull_layout(B, num_faces).bytes; }
+size_t sdf_cull_zero_offset(int B, int num_faces) { return sdf_cull_layout(B, num_faces).cnt; }      // the part that must be zero before the first round: cnt
+size_t sdf_cull_zero_bytes(int B) { return sdf_cull_layout(B, 0).cnt_bytes; }
 int sdf_cull_min_faces() { return SDF_CULL_MIN_FACES; }
-static SdfCullWs cull_views(void* ws, int B, int F) {
+// views of a workspace allocated for B problems (a launch may cover fewer: the first slices of every region)
+static SdfCullWs cull_views(void* ws, const SdfCullLayout& l) {
     unsigned char* p = reinterpret_cast<unsigned char*>(ws);
     SdfCullWs w;
-    w.tri = reinterpret_cast<SdfTri*>(p); p += cull_align((size_t)B * F * sizeof(SdfTri));
-    w.offs = reinterpret_cast<int*>(p);   p += cull_align((size_t)B * SDF_OFFS_LD * 4);
-    w.cnt = reinterpret_cast<int*>(p);    p += cull_align((size_t)B * SDF_NBINS * 4);
-    w.ent = reinterpret_cast<int2*>(p);   p += cull_align((size_t)B * SDF_CULL_CAP * F * 8);
-    w.flag = reinterpret_cast<int*>(p);
+    w.tri = reinterpret_cast<SdfTri*>(p + l.tri);
+    w.offs = reinterpret_cast<int*>(p + l.offs);
+    w.cnt = reinterpret_cast<int*>(p + l.cnt);
+    w.ent = reinterpret_cast<int2*>(p + l.ent);
+    w.flag = reinterpret_cast<int*>(p + l.flag);
     return w;
 }
+static SdfCullWs cull_views(void* ws, int B, int F) { return cull_views(ws, sdf_cull_layout(B, F)); }
 
 struct SdfBinBox { int a0, a1, b0, b1, c0[3], c1[3]; bool bad; float min_s; };
 __device__ __forceinline__ int sdf_bin2(float a) { return min(SDF_NB - 1, max(0, (int)(a * (float)SDF_NB))); }
@@ -731,10 +725,7 @@ hipError_t launch_sdf_voxelize_culled(const int32_t* faces, int num_faces, const
 }
 
 // (SdfEntry, SdfChunk, SDF_NC, SDF_NIT: sdf_entries.h - the scene term of scene_sdf.hip writes the same records)
-#ifndef SDF_NS_
-#define SDF_NS_ 8                   // (-DSDF_NS_=1 reproduces the single-chain summation order bit for bit: the control experiment)
-#endif
-constexpr int SDF_NS = SDF_NS_;      // workgroups (entry slices) per problem in the pull-back
+// (SDF_NS, the workgroups - entry slices - per problem in the pull-back: sdf_layout.h)
 
 // Kernel 1 of the adjoint, grid (SDF_NC, B): a workgroup scans one sixteenth (1 / SDF_NC) of a problem's vertices (the whole list
 // through one CU took 9 us): partial S and box-adjoint sums in float64, and the chunk's entries - the vertices that carry
@@ -1036,32 +1027,33 @@ __global__ __launch_bounds__(SDF_ADJ_NT) void sdf_pullback_kernel(DevModel M, De
     publish_answer();
 }
 
-// work area behind `entries`: [B][nv] SdfEntry | [B][SDF_NS] SdfAdj slice partials | [B][SDF_NC] SdfChunk | [B] tickets
-// (the tickets must be zero before the first round: mvfit_api.hip clears them when it allocates the area; every round
-// leaves them at zero)
-static size_t sdf_part_offset(int B, int nv) { return ((size_t)B * nv * sizeof(SdfEntry) + 255) & ~(size_t)255; }
-static size_t sdf_chunk_offset(int B, int nv) { return sdf_part_offset(B, nv) + (size_t)B * SDF_NS * sizeof(SdfAdj); }
-size_t sdf_ticket_offset(int B, int nv) { return (sdf_chunk_offset(B, nv) + (size_t)B * SDF_NC * sizeof(SdfChunk) + 255) & ~(size_t)255; }
-size_t sdf_work_bytes(int B, int nv) { return sdf_ticket_offset(B, nv) + (size_t)B * sizeof(int); }
+// work area behind `entries` (sdf_layout.h): [B][nv] SdfEntry | [B][SDF_NS] SdfAdj slice partials | [B][SDF_NC] SdfChunk | [B] tickets,
+// B the problems the area was ALLOCATED for - the launchers below take it as layout_B next to the problems the grid covers
+static_assert(sizeof(SdfEntry) == SDF_ENTRY_BYTES && sizeof(SdfAdj) == SDF_ADJ_BYTES && sizeof(SdfChunk) == SDF_CHUNK_BYTES, "records of sdf_layout.h");
+size_t sdf_ticket_offset(int B, int nv) { return sdf_work_layout(B, nv).tickets; }
+size_t sdf_work_bytes(int B, int nv) { return sdf_work_layout(B, nv).bytes; }
 
-hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* verts, int B, const int32_t* faces, int num_faces,
+hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* verts, int B, int layout_B, const int32_t* faces, int num_faces,
                            int G, const int* gate, SdfBox* box, float4* samp, void* entries, SdfAdj* adj, hipStream_t stream,
                            void* cull, unsigned* answer_tag, unsigned answer, const unsigned long long* box_parts) {
     static_assert(SDF_ADJ_NT == KROWS + NJ * 12, "thread per output of the pull-back");
     unsigned char* wk = reinterpret_cast<unsigned char*>(entries);
-    SdfAdj* part = reinterpret_cast<SdfAdj*>(wk + sdf_part_offset(B, M.nv));
-    SdfChunk* chunks = reinterpret_cast<SdfChunk*>(wk + sdf_chunk_offset(B, M.nv));
-    int* tickets = reinterpret_cast<int*>(wk + sdf_ticket_offset(B, M.nv));
+    SdfWorkLayout wl;
+    if (!sdf_launch_work_layout(B, layout_B, M.nv, &wl)) return hipErrorInvalidValue;
+    SdfAdj* part = reinterpret_cast<SdfAdj*>(wk + wl.part);
+    SdfChunk* chunks = reinterpret_cast<SdfChunk*>(wk + wl.chunks);
+    int* tickets = reinterpret_cast<int*>(wk + wl.tickets);
     if (M.nv > SDF_NC * 8 * SDF_NIT * 64) return hipErrorInvalidValue;
     const bool culled = cull && num_faces >= SDF_CULL_MIN_FACES;
     if (num_faces <= SDF_CH) {
         hipLaunchKernelGGL(sdf_entries_kernel<true>, dim3(SDF_NC, B), dim3(SDF_ADJ_NT), 0, stream, M.nv, verts, box, samp, gate,
                            reinterpret_cast<SdfEntry*>(entries), chunks, faces, num_faces, G, box_parts, M.ntiles);
     } else {
-        hipLaunchKernelGGL(sdf_bbox_kernel, dim3(B), dim3(512), 0, stream, verts, M.nv, gate, box,
-                           culled ? cull_views(cull, B, num_faces).flag : (int*)nullptr);
+        SdfCullLayout cl{};
+        if (culled && !sdf_launch_cull_layout(B, layout_B, num_faces, &cl)) return hipErrorInvalidValue;
+        const SdfCullWs W = culled ? cull_views(cull, cl) : SdfCullWs{};
+        hipLaunchKernelGGL(sdf_bbox_kernel, dim3(B), dim3(512), 0, stream, verts, M.nv, gate, box, culled ? W.flag : (int*)nullptr);
         if (culled) {
-            const SdfCullWs W = cull_views(cull, B, num_faces);
             const dim3 gf((num_faces + 255) / 256, B);
             hipLaunchKernelGGL(sdf_cull_count_kernel, gf, dim3(256), 0, stream, verts, M.nv, (const SdfBox*)box, faces, num_faces, gate, W);
             hipLaunchKernelGGL(sdf_cull_scan_kernel, dim3(B), dim3(SDF_SCAN_NT), 0, stream, num_faces, gate, W);
@@ -1080,18 +1072,20 @@ hipError_t launch_sdf_term(const DevModel& M, const DevPose& P, const float* ver
     return hipGetLastError();
 }
 
-SdfChunk* sdf_work_chunks(void* entries, int B, int nv) {
-    return reinterpret_cast<SdfChunk*>(reinterpret_cast<unsigned char*>(entries) + sdf_chunk_offset(B, nv));
+SdfChunk* sdf_work_chunks(void* entries, int layout_B, int nv) {
+    return reinterpret_cast<SdfChunk*>(reinterpret_cast<unsigned char*>(entries) + sdf_work_layout(layout_B, nv).chunks);
 }
 
 // the pull-back alone, for a producer of entries and chunk records other than sdf_entries_kernel (chained rounds: no answer tag)
-hipError_t launch_sdf_pullback(const DevModel& M, const DevPose& P, int B, const int* gate, const SdfBox* box, void* entries,
+hipError_t launch_sdf_pullback(const DevModel& M, const DevPose& P, int B, int layout_B, const int* gate, const SdfBox* box, void* entries,
                                SdfAdj* adj, hipStream_t stream) {
     unsigned char* wk = reinterpret_cast<unsigned char*>(entries);
-    SdfAdj* part = reinterpret_cast<SdfAdj*>(wk + sdf_part_offset(B, M.nv));
-    int* tickets = reinterpret_cast<int*>(wk + sdf_ticket_offset(B, M.nv));
+    SdfWorkLayout wl;
+    if (!sdf_launch_work_layout(B, layout_B, M.nv, &wl)) return hipErrorInvalidValue;
+    SdfAdj* part = reinterpret_cast<SdfAdj*>(wk + wl.part);
+    int* tickets = reinterpret_cast<int*>(wk + wl.tickets);
     hipLaunchKernelGGL(sdf_pullback_kernel, dim3(SDF_NS, B), dim3(SDF_ADJ_NT), 0, stream, M, P, gate, box,
-                       reinterpret_cast<const SdfEntry*>(entries), (const SdfChunk*)sdf_work_chunks(entries, B, M.nv), part, tickets, adj,
+                       reinterpret_cast<const SdfEntry*>(entries), reinterpret_cast<const SdfChunk*>(wk + wl.chunks), part, tickets, adj,
                        (unsigned*)nullptr, 0u);
     return hipGetLastError();
 }

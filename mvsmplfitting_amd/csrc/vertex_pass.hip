@@ -55,8 +55,18 @@ constexpr int VP_GPS = KGROUPS / VP_KSPLIT;      // 7 groups of 4 k-steps per sl
 // stream (216 waiting workgroups per pass cost the optimiser 5 % of its speed; one costs nothing measurable): lane b
 // polls the tag of problem b (relaxed agent-scope loads, s_sleep between polls, bounded by the wall clock - on a
 // timeout the pass simply runs on what the slot holds).  The kernel boundary behind it is the acquire.
-__global__ void pass_gate_kernel(const unsigned* __restrict__ tag, const unsigned* __restrict__ done_round,
-                                 unsigned* __restrict__ stats, unsigned* __restrict__ pass_done, unsigned round, int b_lo, int B) {
+// Service rounds of a fit with the SDF term (pass_gate_copy_kernel: gate, gate_round): a problem's gate word belongs to the optimiser workgroup, which
+// rewrites it in front of every round's tag - also in front of round r + 1 while round r's term kernels may still run, when round
+// r did not ask for the term and so waited for no answer.  Once the round's tag is seen the word is copied into gate_round, and
+// the round's term kernels read the copy: it is written here and only here, the next gate kernel is behind them in stream
+// order, so every workgroup of every kernel of a round sees one value per problem.  (A round that asked for the term has its
+// problem waiting for the answer: the word read behind its tag is that round's.  The copy of a round that did not ask may
+// already be the next round's 1: its kernels then compute an answer nobody waits for, complete and with all tickets returned.)
+// (Two kernels over one body: the fits without the term keep the gate kernel they had - no argument, no branch of the copy.)
+template <bool COPY_GATE>
+__device__ __forceinline__ void pass_gate_body(const unsigned* __restrict__ tag, const unsigned* __restrict__ done_round,
+                                               unsigned* __restrict__ stats, unsigned* __restrict__ pass_done, unsigned round, int b_lo, int B,
+                                               const int* gate, int* __restrict__ gate_round) {
     const int b = b_lo + blockIdx.x * blockDim.x + threadIdx.x;      // grid covers [b_lo, B); every wave polls its own 64 problems
     const bool mine = b < B;
     const unsigned want = round + 1u;
@@ -78,16 +88,33 @@ __global__ void pass_gate_kernel(const unsigned* __restrict__ tag, const unsigne
         if (wall_clock64() - t_start > 300000) { timed_out = true; break; }            // 3 ms at 100 MHz
         __builtin_amdgcn_s_sleep(8);                              // (round 6: 8 instead of 32 - measured in round 5: the round span 4.74 -> 4.6 us, closures/s unchanged)
     }
+    if constexpr (COPY_GATE) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // (the word is read behind the tag that was published behind it)
+        if (mine) gate_round[b] = __hip_atomic_load(gate + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const unsigned long long missed = __ballot(mine && d > round && t > want);
     if ((threadIdx.x & 63) == 0) {
         if (missed) atomicAdd(stats + 2, (unsigned)__popcll(missed));
         if (timed_out) atomicAdd(stats + 3, 1u);
     }
 }
+__global__ void pass_gate_kernel(const unsigned* __restrict__ tag, const unsigned* __restrict__ done_round,
+                                 unsigned* __restrict__ stats, unsigned* __restrict__ pass_done, unsigned round, int b_lo, int B) {
+    pass_gate_body<false>(tag, done_round, stats, pass_done, round, b_lo, B, nullptr, nullptr);
+}
+__global__ void pass_gate_copy_kernel(const unsigned* __restrict__ tag, const unsigned* __restrict__ done_round,
+                                      unsigned* __restrict__ stats, unsigned* __restrict__ pass_done, unsigned round, int b_lo, int B,
+                                      const int* gate, int* __restrict__ gate_round) {
+    pass_gate_body<true>(tag, done_round, stats, pass_done, round, b_lo, B, gate, gate_round);
+}
 
-hipError_t launch_pass_gate(const DevPose& P, int b_lo, int B, hipStream_t stream) {
-    hipLaunchKernelGGL(pass_gate_kernel, dim3((B - b_lo + 63) / 64), dim3(64), 0, stream, P.tag, P.done_round, P.stats, P.pass_done,
-                       P.round, b_lo, B);
+hipError_t launch_pass_gate(const DevPose& P, int b_lo, int B, hipStream_t stream, const int* gate, int* gate_round) {
+    const dim3 grid((B - b_lo + 63) / 64);
+    if (gate && gate_round)
+        hipLaunchKernelGGL(pass_gate_copy_kernel, grid, dim3(64), 0, stream, P.tag, P.done_round, P.stats, P.pass_done, P.round, b_lo, B,
+                           gate, gate_round);
+    else
+        hipLaunchKernelGGL(pass_gate_kernel, grid, dim3(64), 0, stream, P.tag, P.done_round, P.stats, P.pass_done, P.round, b_lo, B);
     return hipGetLastError();
 }
 

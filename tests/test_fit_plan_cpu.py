@@ -291,9 +291,10 @@ def test_sdf_service_tail_sub_batches(shim):
 
 
 def test_sdf_lead_phase_keeps_the_work_queue(shim):
-    """KNOWN DEFECT, pinned as it is: two-phase fit, B = 165, sparse skinning, no helpers - the lead phase
-    plans refill together with a pause_stage; a row that pauses takes no further problem, so problems 128..164 never run and the
-    fit ends with 'hit the round cap ... stages without the SDF term'.  Its fix is a change to this row."""
+    """Two-phase fit, B = 165, sparse skinning, no helpers: the lead phase plans refill together with a pause_stage - one launch
+    of 128 rows whose target is the whole batch.  A row whose problem pauses at the stage boundary takes the next problem from
+    the queue like one whose problem finished (fit_persistent_kernel: `done || paused`), so problems 128..164 run their lead
+    stages on rows that became free (on the GPU: tests/test_gpu_sdf_batches.py, work_queue 1 against 0)."""
     p = plan(shim, B=165, **SDF)
     assert p['rc'] == 0 and p['init'] == 0 and len(p['phases']) == 2
     check_async(p['phases'][0], 128, 3, 108, True, [(0, 128)], cap=3 * CAP, pause=2)

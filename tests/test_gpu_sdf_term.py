@@ -27,9 +27,13 @@ from tests.test_gpu_lbfgs import eng_stage_weights
 pytestmark = pytest.mark.gpu
 
 
-def _closure_case(num_faces, G, coll_w, nprob, use_vp=False):
+def _closure_case(num_faces, G, coll_w, nprob, use_vp=False, problems=None, check=None):
+    """closure with the term on nprob problems of the golden case against the oracle; problems = (x [nprob, 86 | 49], gt_xy, conf)
+    replaces the golden ones, check = the problems the oracle looks at (default: all) - one result per checked problem"""
     name = 'vp_s0_v8' if use_vp else 'l2_s3_v6'
     cfg, g, model, vpw, gmm, wts, cams = load_case(name)
+    if problems is not None:
+        g = dict(g, x=problems[0], gt_xy=problems[1], conf=problems[2])
     orc = oracle_for(model, vpw, gmm)
     eng = make_engine(model, vpw, gmm)
     eng.set_problems(cams, g['gt_xy'][:nprob], g['conf'][:nprob])
@@ -47,7 +51,7 @@ def _closure_case(num_faces, G, coll_w, nprob, use_vp=False):
     nf = model['faces'].shape[0] if num_faces is None else num_faces
     sdf = dict(faces=model['faces'], num_faces=nf, grid_size=G)
     res = []
-    for b in range(nprob):
+    for b in (range(nprob) if check is None else check):
         pen_r, g_sdf, aux = st.sdf_term(verts[b], sdf['faces'], coll_w, nf, G)
         Lr, gr, o = orc.closure(g['x'][b], cams, g['gt_xy'][b], g['conf'][b], dict(wts, coll_loss_weight=0.0),
                                 use_vposer=use_vp, g_verts_extra=g_sdf)
