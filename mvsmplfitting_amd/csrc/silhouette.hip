@@ -371,6 +371,19 @@ __global__ __launch_bounds__(64) void sil_loss_kernel(const int* __restrict__ sb
     if (lane == 0) loss[n] = (float)tot;
 }
 
+// grid (ceil(nv / SIL_NT), M): term B's accumulators of the images whose body is live -> 0 (one 16-byte store per (image,
+// vertex)).  The rounds' form of sil_loss's memset, as a kernel: a captured round then holds kernel nodes only.  A workaround
+// for an observation, not for an understood mechanism: with a memset node here, a two-stage fit that
+// replayed an earlier fit's graph on the idle stream behind its lead phase had the closure's loss and another gradient in its
+// first round, for the bodies with images only.  A gated-off body's accumulators keep what they hold: its search and vertex
+// workgroups return before they touch them.
+__global__ __launch_bounds__(SIL_NT) void sil_clear_kernel(unsigned long long* __restrict__ acc, int nv,
+                                                           const int* __restrict__ image_body, SilGate<true> gate) {
+    const int j = blockIdx.x * SIL_NT + threadIdx.x, i = blockIdx.y;
+    if (gate.off(image_body[i]) || j >= nv) return;
+    *reinterpret_cast<ulonglong2*>(acc + ((size_t)i * nv + j) * 2) = make_ulonglong2(0ull, 0ull);
+}
+
 // ========================================================================================================== host side
 static int sil_fail(std::string& err, int code, const char* fmt, ...) {
     char buf[512];
@@ -540,11 +553,14 @@ int sil_loss(SilState& S, const float* vertices, int num_bodies, float w_in, flo
 }
 
 // One evaluation for the fit's chained rounds: sil_loss's sequence with the gated kernels, every body's loss and vertex
-// gradient; no host work, so a stream capture records it as it is (one memset node and three kernel nodes).
+// gradient; no host work, so a stream capture records it as it is (four kernel nodes: the accumulators are cleared by a
+// kernel, not by a memset node - sil_clear_kernel).
 int sil_round(SilState& S, const float* vertices, int num_bodies, float w_in, float w_out, float sigma, const int* gate,
               float* loss, float* g_vertices, hipStream_t stream, std::string& err) {
     unsigned long long* acc = S.nchunks ? reinterpret_cast<unsigned long long*>(S.ws.as<unsigned char>() + S.o_acc) : nullptr;
-    if (acc) SIL_HIP(hipMemsetAsync(acc, 0, (size_t)S.M * S.nv * 16, stream));
+    if (acc)
+        hipLaunchKernelGGL(sil_clear_kernel, dim3((S.nv + SIL_NT - 1) / SIL_NT, S.M), dim3(SIL_NT), 0, stream, acc, S.nv,
+                           reinterpret_cast<const int*>(S.ws.as<unsigned char>() + S.o_body), SilGate<true>{gate});
     if (S.occ_on) sil_launch<true, true>(S, vertices, num_bodies, w_in, w_out, sigma, gate, acc, loss, g_vertices, nullptr, stream);
     else sil_launch<true, false>(S, vertices, num_bodies, w_in, w_out, sigma, gate, acc, loss, g_vertices, nullptr, stream);
     SIL_HIP(hipGetLastError());
