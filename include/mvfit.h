@@ -614,9 +614,16 @@ int mvfit_set_vertex_target_term(mvfit_ctx* ctx, int enable);
  *     a conservative bound of the point's distance; it returns the bits of the exhaustive search.
  *   Determinism: no float atomics; a body's loss, gradient and winners are bit-identical alone, in any batch, at any position
  *     and from run to run; a body without participating points gets, at w_m2s = 0, loss 0 and an exactly zero gradient.
- *     Term S's many-points-to-one-vertex sum is a 64-bit integer accumulation in units of 2^-32 of the vertices' unit (each
- *     point's contribution to a vertex coordinate is rounded to that unit; the sum of one coordinate must stay below 2^31
- *     units of the vertices in magnitude).  S_n and M_n are float64 sums whose order is fixed by max_points, Nv and the
+ *     Term S's many-points-to-one-vertex sum is a 64-bit integer accumulation of the contributions scaled by 2^e_n,
+ *     e_n = -ilogb(largest participating weight of body n) (0 for a body without one; computed once by mvfit_set_scans), in
+ *     units of 2^-32 of the vertices' unit: with w' = 2^e_n w_p, so that the body's largest w' lies in [1, 2), each
+ *     contribution w' rho'(m) 2 (q - p) b_k to a vertex coordinate is rounded to that unit, the sum of one coordinate must
+ *     stay below 2^31 units of the vertices in magnitude, and 2^-e_n is applied to the sum in float64 before w_s2m and the
+ *     one rounding to float32.  The unit is therefore relative to the body's weights - weights scaled by a power of two scale
+ *     the loss and every gradient word by exactly that power, and a body whose largest weight lies in [1, 2) has e_n = 0 -
+ *     but absolute in q - p: a contribution carries up to 2^-33 / (2 w' rho' |q - p| b_k) of relative rounding, 1e-8 at 5 mm
+ *     (in metres) and weight 1, more where the distances or rho' are small.
+ *     S_n and M_n are float64 sums whose order is fixed by max_points, Nv and the
  *     kernel shapes (256 points or vertices per workgroup: a wave64 butterfly, the waves, then the workgroups in order),
  *     never by N.
  *
@@ -625,8 +632,8 @@ int mvfit_set_vertex_target_term(mvfit_ctx* ctx, int enable);
  * take part); nearest_point[N,Nv] int32 dev out or NULL.  mvfit_set_scans waits for the stream; mvfit_scan_loss is
  * asynchronous.
  * Workspace, kept in the ctx and reused - every address kept - by a second set of the same (N, max_points):
- *     N * (32 max_points + 4 + 64 Nf + 16 ceil(Nf / 8) + 24 Nv + 8 ceil(max_points / 256) + 8 ceil(Nv / 256))   bytes
- *     (points, weights and packed points; counts; face records; seed vertices; the fixed-point accumulators; the partials of
+ *     N * (32 max_points + 8 + 64 Nf + 16 ceil(Nf / 8) + 24 Nv + 8 ceil(max_points / 256) + 8 ceil(Nv / 256))   bytes
+ *     (points, weights and packed points; counts and the exponents e_n; face records; seed vertices; the fixed-point accumulators; the partials of
  *     both terms), each part rounded up to 256 bytes.
  * MVFIT_E_ARG: a NULL required pointer, sizes out of range (N <= 65535, max_points >= 1, N max_points <= 2^28), a count[n]
  * outside [0, max_points], a negative or non-finite weight below count[n], a negative or non-finite w_s2m, w_m2s or sigma,

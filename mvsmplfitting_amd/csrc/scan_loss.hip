@@ -12,10 +12,12 @@
 //       minimum (bits of m, face) stays in registers: m >= 0 orders like its bits, a NaN compares above +inf, ascending
 //       faces and a strict compare send ties to the lowest face.  CULL: a face is skipped when its sphere lies farther than
 //       the bound sb - see "the cull" below.  The winner's gradient goes to a 64-bit fixed-point accumulator per (body,
-//       vertex, axis) (integer atomics: the sum does not depend on the order), w rho to one float64 partial per workgroup.
+//       vertex, axis) (integer atomics: the sum does not depend on the order), taken with the weight times 2^e_n - e_n puts
+//       the body's largest weight into [1, 2), so the unit 2^-32 is relative to the body's weights, not absolute;
+//       w rho to one float64 partial per workgroup.
 //   scan_m2s_kernel<SEARCH> (term M and the gradient's last step): a thread per (body, vertex); the packed points stream
-//       through LDS in tiles of SCAN_PT, same minimum.  Then g = w_m2s rho' 2 (v - p) + w_s2m acc / 2^32 in float64, rounded
-//       and stored once; rho to one float64 partial per workgroup.
+//       through LDS in tiles of SCAN_PT, same minimum.  Then g = w_m2s rho' 2 (v - p) + w_s2m 2^-e_n acc / 2^32 in float64,
+//       rounded and stored once; rho to one float64 partial per workgroup.
 //   scan_sum_kernel: a wave per body, the partials of each term in ascending order.
 // No float atomics; nothing a body gets depends on the other bodies of the call or on its position in it.
 //
@@ -30,6 +32,7 @@
 // search return the same bits.  A NaN anywhere fails the skip test: the face is evaluated, as in the exhaustive search.
 #include "scan_loss.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -148,9 +151,11 @@ __global__ __launch_bounds__(SCAN_NT) void scan_face_kernel(const float* __restr
 }
 
 // grid (ceil(Pmax / SCAN_NT), N): 256 points of body n against its nf face records.
-// acc[(n nv + vertex) 3 + axis] += round(2^32 w_p rho'(m) 2 d[axis] b_k); partS[n gridDim.x + blockIdx.x] = sum of w_p rho.
+// acc[(n nv + vertex) 3 + axis] += round(2^32 (2^e_n w_p) rho'(m) 2 d[axis] b_k), e_n = expo[n] (scan_set: the body's largest
+// weight scaled into [1, 2)); partS[n gridDim.x + blockIdx.x] = sum of w_p rho.
 template <bool CULL>
-__global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restrict__ pk, const int* __restrict__ count, int Pmax,
+__global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restrict__ pk, const int* __restrict__ count,
+                                                           const int* __restrict__ expo, int Pmax,
                                                            const float4* __restrict__ rec, const float4* __restrict__ seed,
                                                            int nf, int ns, const int32_t* __restrict__ faces, int nv, float sigma,
                                                            unsigned long long* __restrict__ acc, double* __restrict__ partS,
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restr
         s = (double)P.w * rho;
         if (acc) {
             const float bary[3] = {(1.f - v) - w, v, w};
-            const double k2 = 2.0 * (double)P.w * drho * SCAN_FIX;
+            const double k2 = 2.0 * ldexp((double)P.w, expo[n]) * drho * SCAN_FIX;       // e_n = 0: the weight itself
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 unsigned long long* o = acc + ((size_t)n * nv + faces[(size_t)bj * 3 + k]) * 3;
@@ -242,10 +247,11 @@ __global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restr
 }
 
 // grid (ceil(nv / SCAN_NT), N): thread = (body n, vertex j).  SEARCH: the nearest participating point (term M).  Either way
-// the vertex's gradient is finished here: g = w_m2s rho' 2 (v - p) + w_s2m acc / 2^32.
+// the vertex's gradient is finished here: g = w_m2s rho' 2 (v - p) + w_s2m 2^-e_n acc / 2^32.
 template <bool SEARCH>
 __global__ __launch_bounds__(SCAN_NT) void scan_m2s_kernel(const float* __restrict__ verts, int nv, const float4* __restrict__ pk,
-                                                           const int* __restrict__ count, int Pmax, float w_s2m, float w_m2s,
+                                                           const int* __restrict__ count, const int* __restrict__ expo, int Pmax,
+                                                           float w_s2m, float w_m2s,
                                                            float sigma, const long long* __restrict__ acc,
                                                            float* __restrict__ g_verts, double* __restrict__ partM,
                                                            int32_t* __restrict__ nearest) {
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_m2s_kernel(const float* __restri
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             double t = g[c];
-            if (acc) t += (double)w_s2m * ((double)acc[((size_t)n * nv + j) * 3 + c] / SCAN_FIX);
+            if (acc) t += (double)w_s2m * ldexp((double)acc[((size_t)n * nv + j) * 3 + c] / SCAN_FIX, -expo[n]);
             o[c] = (float)t;
         }
     }
@@ -341,7 +347,7 @@ int scan_set(ScanState& S, int nv, int nf, int N, int Pmax, const float* points,
     const int ns = (nf + SCAN_SEED - 1) / SCAN_SEED;
     size_t o = 0;
     auto take = [&o](size_t bytes) { const size_t at = o; o += scan_al(bytes); return at; };
-    const size_t o_pts = take(np * 12), o_w = take(np * 4), o_pk = take(np * 16), o_cnt = take((size_t)N * 4),
+    const size_t o_pts = take(np * 12), o_w = take(np * 4), o_pk = take(np * 16), o_cnt = take((size_t)N * 8),
                  o_rec = take((size_t)N * nf * 64), o_seed = take((size_t)N * ns * 16), o_acc = take((size_t)N * nv * 24),
                  o_partS = take((size_t)N * scan_blocks(Pmax) * 8), o_partM = take((size_t)N * scan_blocks(nv) * 8);
     SCAN_HIP(hipStreamSynchronize(stream));      // an evaluation in flight may still read the workspace
@@ -355,12 +361,23 @@ int scan_set(ScanState& S, int nv, int nf, int N, int Pmax, const float* points,
     S.o_partS = o_partS; S.o_partM = o_partM;
     // effective weights: 0 beyond count[n], 1 without weights
     S.h_w.assign(np, 0.f);
-    S.h_cnt.assign(count, count + N);
-    for (int n = 0; n < N; ++n)
-        for (int i = 0; i < count[n]; ++i) S.h_w[(size_t)n * Pmax + i] = weights ? weights[(size_t)n * Pmax + i] : 1.f;
+    // and, behind the counts, e_n: term S's fixed-point sums of body n are taken with the weights times 2^e_n, which puts the
+    // body's largest weight into [1, 2) - the accumulator's unit is then relative to the body's own weights, and a set
+    // whose weights are scaled by a power of two keeps every bit of the sums (the scaling is undone in float64)
+    S.h_cnt.assign((size_t)2 * N, 0);
+    for (int n = 0; n < N; ++n) {
+        float wmax = 0.f;
+        for (int i = 0; i < count[n]; ++i) {
+            const float w = weights ? weights[(size_t)n * Pmax + i] : 1.f;
+            S.h_w[(size_t)n * Pmax + i] = w;
+            wmax = std::fmax(wmax, w);
+        }
+        S.h_cnt[n] = count[n];
+        S.h_cnt[(size_t)N + n] = wmax > 0.f ? -std::ilogb(wmax) : 0;
+    }
     SCAN_HIP(hipMemcpyAsync(ws + o_pts, points, np * 12, hipMemcpyDefault, stream));
     SCAN_HIP(hipMemcpyAsync(ws + o_w, S.h_w.data(), np * 4, hipMemcpyHostToDevice, stream));
-    SCAN_HIP(hipMemcpyAsync(ws + o_cnt, S.h_cnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream));
+    SCAN_HIP(hipMemcpyAsync(ws + o_cnt, S.h_cnt.data(), (size_t)N * 8, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(scan_pack_kernel, dim3(scan_blocks(Pmax), N), dim3(SCAN_NT), 0, stream,
                        reinterpret_cast<const float*>(ws + o_pts), reinterpret_cast<const float*>(ws + o_w), Pmax,
                        reinterpret_cast<float4*>(ws + o_pk));
@@ -377,6 +394,7 @@ int scan_loss(ScanState& S, const int32_t* faces, const float* vertices, float w
     unsigned char* const ws = S.ws.as<unsigned char>();
     const float4* pk = reinterpret_cast<const float4*>(ws + S.o_pk);
     const int* count = reinterpret_cast<const int*>(ws + S.o_cnt);
+    const int* expo = count + N;
     float4* rec = reinterpret_cast<float4*>(ws + S.o_rec);
     float4* seed = reinterpret_cast<float4*>(ws + S.o_seed);
     double* partS = reinterpret_cast<double*>(ws + S.o_partS);
@@ -388,20 +406,20 @@ int scan_loss(ScanState& S, const int32_t* faces, const float* vertices, float w
         hipLaunchKernelGGL(scan_face_kernel, dim3(scan_blocks(nf), N), dim3(SCAN_NT), 0, stream, vertices, nv, faces, nf, S.ns, rec,
                            seed);
         if (exhaustive)
-            hipLaunchKernelGGL(scan_s2m_kernel<false>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, Pmax,
+            hipLaunchKernelGGL(scan_s2m_kernel<false>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
                                (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face);
         else
-            hipLaunchKernelGGL(scan_s2m_kernel<true>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, Pmax,
+            hipLaunchKernelGGL(scan_s2m_kernel<true>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
                                (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face);
     } else if (nearest_face) {
         SCAN_HIP(hipMemsetAsync(nearest_face, 0xff, (size_t)N * Pmax * 4, stream));
     }
     if (termM)
-        hipLaunchKernelGGL(scan_m2s_kernel<true>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, Pmax, w_s2m,
-                           w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, nearest_point);
+        hipLaunchKernelGGL(scan_m2s_kernel<true>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
+                           w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, nearest_point);
     else {
         if (g_vertices)
-            hipLaunchKernelGGL(scan_m2s_kernel<false>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, Pmax,
+            hipLaunchKernelGGL(scan_m2s_kernel<false>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
                                w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM,
                                (int32_t*)nullptr);
         if (nearest_point) SCAN_HIP(hipMemsetAsync(nearest_point, 0xff, (size_t)N * nv * 4, stream));

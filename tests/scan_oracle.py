@@ -43,9 +43,12 @@ def rho(m, sigma):
 def scan_to_mesh(points, verts, faces, rel=1e-5, absolute=1e-7, apart=1e-4, prune=True, chunk=256):
     """Per point: the winner (smallest m, ties to the lowest face), its m, (v, w), d, region - and ``ambiguous``: another
     face whose distance is within rel * best + absolute of the best and whose closest point lies more than ``apart`` from the
-    best one.  prune=False evaluates every (point, face) pair.  prune=True first drops the pairs that cannot matter, in
+    best one.  A face whose m is NaN (a repeated vertex index can make it so) counts as +inf and never wins; a point whose
+    every face is such has no winner: face -1, m, v, w and d zero, region -1, not ambiguous.
+    prune=False evaluates every (point, face) pair.  prune=True first drops the pairs that cannot matter, in
     float64 and with room to spare: a face whose bounding sphere (centroid, largest corner distance) lies farther from the
-    point than the nearest first corner of any face, widened by the ambiguity margin, is neither the winner nor near it."""
+    point than the nearest first corner of any face whose m cannot be NaN (three different indices, or three equal ones),
+    widened by the ambiguity margin, is neither the winner nor near it; without such a face nothing is dropped."""
     P = len(points)
     out = dict(face=np.full(P, -1, np.int64), m=np.zeros(P), v=np.zeros(P), w=np.zeros(P), d=np.zeros((P, 3)),
                region=np.zeros(P, np.int64), ambiguous=np.zeros(P, bool))
@@ -54,11 +57,13 @@ def scan_to_mesh(points, verts, faces, rel=1e-5, absolute=1e-7, apart=1e-4, prun
     cen = a + (ab + ac) / 3.0
     rad = np.sqrt(np.maximum(((a - cen) ** 2).sum(axis=1), np.maximum(((a + ab - cen) ** 2).sum(axis=1),
                                                                        ((a + ac - cen) ** 2).sum(axis=1))))
+    f0, f1, f2 = faces[:, 0], faces[:, 1], faces[:, 2]
+    sure = ((f0 != f1) & (f1 != f2) & (f0 != f2)) | ((f0 == f1) & (f1 == f2))
     for i0 in range(0, P, chunk):
         p = points[i0:i0 + chunk]
         if prune:
             lower = np.sqrt(((p[:, None, :] - cen[None]) ** 2).sum(axis=-1)) - rad[None]
-            upper = np.sqrt(((p[:, None, :] - a[None]) ** 2).sum(axis=-1)).min(axis=1)
+            upper = np.sqrt(((p[:, None, :] - a[None, sure]) ** 2).sum(axis=-1)).min(axis=1, initial=np.inf)
             slack = 1e-9 * (np.abs(p).max() + np.abs(verts).max())
             pi, fi = np.nonzero(lower <= (upper * (1.0 + 2.0 * rel) + 2.0 * absolute + slack)[:, None])
         else:
@@ -77,7 +82,47 @@ def scan_to_mesh(points, verts, faces, rel=1e-5, absolute=1e-7, apart=1e-4, prun
         near[first] = False
         far = np.linalg.norm(d - d[first][pi], axis=-1) > apart                  # q_f - q_best = d_f - d_best
         out['ambiguous'][sl] = np.bincount(pi[near & far], minlength=len(p)) > 0
+        none = i0 + np.flatnonzero(np.isinf(best_m))                             # every face's m was NaN
+        out['face'][none], out['region'][none], out['ambiguous'][none] = -1, -1, False
+        out['m'][none] = out['v'][none] = out['w'][none] = out['d'][none] = 0.0
     return out
+
+
+def lowest_zero_face(points, verts, faces):
+    """Per point the lowest face whose float64 m is exactly 0, -1 where no face has it (the winner of scan_to_mesh: the
+    smallest m, ties to the lowest face - so where the smallest m is 0 the winner is that face)."""
+    r = scan_to_mesh(points, verts, faces)
+    return np.where((r['face'] >= 0) & (r['m'] == 0.0), r['face'], -1)
+
+
+def repeated_faces(faces, copies):
+    """faces repeated ``copies`` times: copy k with its corner order rotated by k mod 3, the odd copies in reverse face
+    order.  Every copy is the same surface, so a point's closest point is shared by its winner's copies."""
+    out = []
+    for k in range(copies):
+        f = np.roll(faces, -(k % 3), axis=1)
+        out.append(f[::-1] if k % 2 else f)
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def far_points(verts, faces, k, lo=5.0, hi=50.0, tries=256, seed=0, rel=1e-5, absolute=1e-7):
+    """k points between lo and hi from the mesh whose nearest feature is one vertex, by a margin the ambiguity test of
+    scan_to_mesh cannot reach.  For a direction u let v be the vertex (of a face) with the largest u.x and s the gap to the
+    second largest; every other point x of the surface has u.(v - x) >= s, so from p = v + t u it lies at
+    sqrt(t^2 + 2 t u.(v - x) + |v - x|^2) >= t + s (as |v - x| >= u.(v - x)), while the faces at v tie at the closest
+    point v itself.  Not ambiguous when s > rel t + absolute: the k directions of ``tries`` random ones with the largest s
+    are taken, and t, spread geometrically over [lo, hi], is cut to s / (4 rel) where that is nearer.  -> ([k,3], s[k], t[k])"""
+    rng = np.random.default_rng(seed)
+    u = rng.normal(size=(tries, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    used = np.unique(faces)
+    h = verts[used] @ u.T                                                        # [vertices, tries]
+    top2 = np.sort(h, axis=0)[-2:]
+    s = top2[1] - top2[0]
+    pick = np.argsort(-s)[:k]
+    t = np.minimum(lo * (hi / lo) ** (np.arange(k) / max(k - 1, 1)), s[pick] / (4.0 * rel))
+    v = verts[used[h[:, pick].argmax(axis=0)]]
+    return v + t[:, None] * u[pick], s[pick], t
 
 
 def m_of_faces(points, verts, faces, face_idx):

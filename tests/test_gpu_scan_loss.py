@@ -33,14 +33,29 @@ COUNT = np.array([257, 0, 64], np.int32)
 
 
 @functools.lru_cache(maxsize=None)
-def model(nv):
+def model(nv, faces=None):
+    """faces: None (the model's own), an int k (its first k faces), 'x13' (so.repeated_faces, 13 copies), 'pair' (faces 0 and
+    1 replaced by (a, a, c) and (a, a, a), a and c corners of face 2) or 'line' (the two faces (a, a, c), (a, a, c))"""
     full = syn.make_body_model(skin_topk=4)
-    return full if nv is None else sub_model(full, nv)
+    m = full if nv is None else sub_model(full, nv)
+    if faces is None:
+        return m
+    f = np.asarray(m['faces'], np.int32)
+    a, c = f[2, 0], f[2, 2]
+    if faces == 'x13':
+        f = so.repeated_faces(f, 13)
+    elif faces == 'pair':
+        f = np.concatenate([[[a, a, c], [a, a, a]], f[2:]])
+    elif faces == 'line':
+        f = np.array([[a, a, c], [a, a, c]])
+    else:
+        f = f[:faces]
+    return dict(m, faces=np.ascontiguousarray(f, np.int32))
 
 
 @functools.lru_cache(maxsize=None)
-def layer(nv):
-    return BodyLayer(model(nv))
+def layer(nv, faces=None):
+    return BodyLayer(model(nv, faces))
 
 
 def posed(nv, B, seed0):
@@ -59,24 +74,38 @@ def surface_samples(verts, faces, P, noise, rng):
     flip = u.sum(axis=1) > 1
     u[flip] = 1.0 - u[flip]
     a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
-    return (a + u[:, :1] * (b - a) + u[:, 1:] * (c - a) + rng.normal(0, noise, (P, 3))).astype(np.float32)
+    return a + u[:, :1] * (b - a) + u[:, 1:] * (c - a) + rng.normal(0, noise, (P, 3))
+
+
+FAR_AT = 10 + 30 * np.arange(8)                           # rows of body 0 that far=True moves away; none has weight 0
 
 
 @functools.lru_cache(maxsize=None)
-def world(nv, noise, count=tuple(COUNT.tolist()), pmax=257, seed=5):
-    faces = np.asarray(model(nv)['faces'], np.int64)
+def world(nv, noise, count=tuple(COUNT.tolist()), pmax=257, seed=5, faces=None, shift=None, scale=1.0, far=False):
+    """faces: the face list of model(nv, faces); the points are samples of it ('pair' and 'line': of the model's own faces).
+    shift, scale: bodies and points become (x + shift) * scale in float64 before they are rounded to float32.  far: the rows
+    FAR_AT of body 0 become so.far_points of the body, 5 to 50 units (times scale) away."""
+    mesh = np.asarray(model(nv, faces)['faces'], np.int64)
+    sampled = np.asarray(model(nv)['faces'], np.int64) if faces in ('pair', 'line') else mesh
     N = len(count)
     verts = posed(nv, N, 4100 + N)
     v64 = verts.cpu().numpy().astype(np.float64)
+    move = lambda x: x if shift is None and scale == 1.0 else (x + np.asarray(shift or (0.0, 0.0, 0.0))) * scale
     rng = np.random.default_rng(seed)
-    points = np.stack([surface_samples(v64[n], faces, pmax, noise, rng) for n in range(N)])
+    points = np.stack([move(surface_samples(v64[n], sampled, pmax, noise, rng)).astype(np.float32) for n in range(N)])
     weights = rng.uniform(0.5, 2.0, (N, pmax)).astype(np.float32)
     weights[:, 5::41] = 0.0
-    return dict(nv=nv, faces=faces, verts=verts, v64=v64, points=points, count=np.asarray(count, np.int32), weights=weights)
+    if shift is not None or scale != 1.0:
+        verts = torch.from_numpy(move(v64).astype(np.float32)).to(verts.device)
+        v64 = verts.cpu().numpy().astype(np.float64)
+    if far:
+        points[0, FAR_AT] = so.far_points(v64[0], mesh, len(FAR_AT), lo=5.0 * scale, hi=50.0 * scale)[0].astype(np.float32)
+    return dict(nv=nv, variant=faces, faces=mesh, verts=verts, v64=v64, points=points, count=np.asarray(count, np.int32),
+                weights=weights)
 
 
 def run(w, search='auto', **kw):
-    eng = layer(w['nv']).engine
+    eng = layer(w['nv'], w.get('variant')).engine
     eng.set_scans(w['points'], w['count'], w['weights'])
     try:
         loss, g, nf, npt = eng.scan_loss(w['verts'], return_nearest=True, search=search, **kw)
@@ -86,20 +115,24 @@ def run(w, search='auto', **kw):
     return loss.cpu().numpy(), g.cpu().numpy(), nf.cpu().numpy(), npt.cpu().numpy()
 
 
-def check_against_oracle(w, w_s2m, w_m2s, sigma):
-    """-> the oracle's own result (its winners, regions and ambiguity flags)"""
+def check_against_oracle(w, w_s2m, w_m2s, sigma, grad_tol=GRAD_TOL, found=None):
+    """-> the oracle's own result (its winners, regions and ambiguity flags), with the GPU's (loss, g, nearest_face,
+    nearest_point) under 'gpu' and the gradient error under 'grad_err'.  found: the 'found' of an earlier call for the same
+    bodies, faces and participating points (the weights may differ in size), to skip the oracle's search."""
     loss, g, nf, npt = run(w, w_s2m=w_s2m, w_m2s=w_m2s, sigma=sigma)
     pts64 = w['points'].astype(np.float64)
-    free = so.evaluate(w['v64'], w['faces'], pts64, w['count'], w['weights'], w_s2m=w_s2m, w_m2s=w_m2s, sigma=sigma)
+    free = so.evaluate(w['v64'], w['faces'], pts64, w['count'], w['weights'], w_s2m=w_s2m, w_m2s=w_m2s, sigma=sigma,
+                       found=found if w_s2m > 0 else None)
     part = free['part']
-    assert ((nf >= 0) == part).all() if w_s2m > 0 else (nf == -1).all()
+    # a point takes part and has a winner (the oracle reports -1 only where every face's m is NaN: repeated indices)
+    assert ((nf >= 0) == (part & (free['nearest_face'] >= 0))).all() if w_s2m > 0 else (nf == -1).all()
     scale = max(np.abs(pts64[part]).max() if part.any() else 0.0, np.abs(w['v64']).max())
     ref = so.evaluate(w['v64'], w['faces'], pts64, w['count'], w['weights'], w_s2m=w_s2m, w_m2s=w_m2s, sigma=sigma,
                       face_override=nf, found=free['found'] if w_s2m > 0 else None)
     bound = np.zeros(len(loss))
     if w_s2m > 0:
         share = free['ambiguous'][part].mean()
-        print('ambiguous share %.4f, regions %s' % (share, np.bincount(free['region'][part], minlength=7).tolist()))
+        print('ambiguous share %.4f, regions %s' % (share, np.bincount(free['region'][nf >= 0], minlength=7).tolist()))
         assert share <= 0.01
         ok = part & ~free['ambiguous']
         dm = ref['m_s'] - free['m_s']                       # float64 m of the GPU's face against the oracle's best
@@ -122,8 +155,9 @@ def check_against_oracle(w, w_s2m, w_m2s, sigma):
     print('loss', loss, 'ref', ref['loss'], 'dl / bound', dl / np.maximum(bound + 2.0 ** -24 * np.abs(ref['loss']), 1e-300))
     assert (dl <= bound + 2.0 ** -24 * np.abs(ref['loss'])).all()
     err = np.abs(g - ref['grad']).max() / np.abs(ref['grad']).max()
-    print('gradient error %.3g' % err)
-    assert err <= GRAD_TOL
+    print('gradient error %.3g, over its bound %.3g' % (err, err / grad_tol))
+    free['gpu'], free['grad_err'], free['grad_ref'] = (loss, g, nf, npt), err, ref['grad']
+    assert err <= grad_tol
     return free
 
 

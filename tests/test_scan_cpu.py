@@ -79,6 +79,94 @@ def test_a_body_without_points_contributes_nothing():
     assert ref['loss'][0] == 0 and not ref['grad'].any() and (ref['nearest_point'] == -1).all()
 
 
+# ------------------------------------------------------------------- what tests/test_gpu_scan_edges.py builds its cases from
+def template_mesh(nv):
+    from tests.small_models import sub_model
+    m = sub_model(syn.make_body_model(skin_topk=4), nv)
+    return np.asarray(m['v_template'], np.float32).astype(np.float64), np.asarray(m['faces'], np.int64)
+
+
+def samples(verts, faces, P, noise, seed):
+    rng = np.random.default_rng(seed)
+    f = faces[rng.integers(0, len(faces), P)]
+    u = rng.random((P, 2))
+    u[u.sum(axis=1) > 1] = 1.0 - u[u.sum(axis=1) > 1]
+    a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
+    return a + u[:, :1] * (b - a) + u[:, 1:] * (c - a) + rng.normal(0, noise, (P, 3))
+
+
+def test_the_repeated_face_list_is_the_same_surface_and_not_ambiguous():
+    verts, faces = template_mesh(1001)
+    many = so.repeated_faces(faces, 13)
+    assert many.shape == (13 * 1399, 3) and -(-len(many) // 8) > 2048
+    nf = len(faces)
+    for k in range(13):                                    # copy k: rotated by k mod 3, the odd copies in reverse order
+        block = many[k * nf:(k + 1) * nf]
+        block = block[::-1] if k % 2 else block
+        assert np.array_equal(np.roll(block, k % 3, axis=1), faces)
+    pts = samples(verts, faces, 321, 0.03, 5)
+    one, all13 = so.scan_to_mesh(pts, verts, faces), so.scan_to_mesh(pts, verts, many)
+    assert all13['ambiguous'].mean() <= 0.01 and one['ambiguous'].mean() <= 0.01
+    assert np.abs(all13['m'] - one['m']).max() <= 1e-12 * one['m'].max()
+    assert np.abs(all13['d'] - one['d']).max() <= 1e-9      # the copies share the closest point
+    k, pos = np.divmod(all13['face'], nf)
+    base = np.where(k % 2 == 1, nf - 1 - pos, pos)
+    assert (np.sort(faces[base], axis=1) == np.sort(many[all13['face']], axis=1)).all()
+
+
+def test_the_lowest_face_with_m_zero_is_the_lowest_face_at_the_vertex():
+    verts, faces = template_mesh(700)
+    assert len(np.unique(verts, axis=0)) == len(verts)     # distinct positions: only a vertex's own faces reach m = 0
+    got = so.lowest_zero_face(verts, verts, faces)
+    want = np.full(len(verts), -1)
+    for f in range(len(faces) - 1, -1, -1):
+        want[faces[f]] = f
+    assert (want == -1).sum() == 88 and np.array_equal(got, want)
+    # brute force over every pair agrees
+    m = so.closest(verts[:, None, :], verts[faces[:, 0]][None], (verts[faces[:, 1]] - verts[faces[:, 0]])[None],
+                   (verts[faces[:, 2]] - verts[faces[:, 0]])[None])[3]
+    assert np.array_equal(np.where((m == 0).any(axis=1), (m == 0).argmax(axis=1), -1), want)
+
+
+@pytest.mark.parametrize('shift,scale', [((512.0, -300.0, 40.0), 1.0), (None, 2.0 ** -6)])
+def test_far_points_are_far_and_not_ambiguous(shift, scale):
+    verts, faces = template_mesh(1001)
+    verts = ((verts + (0.0 if shift is None else np.asarray(shift))) * scale).astype(np.float32).astype(np.float64)
+    far, s, t = so.far_points(verts, faces, 8, lo=5.0 * scale, hi=50.0 * scale)
+    assert (s > 1e-5 * t + 1e-7).all() and t.min() >= 5.0 * scale and t.max() <= 50.0 * scale and t.max() > 10 * scale
+    pts = np.concatenate([far.astype(np.float32).astype(np.float64),
+                          (samples(verts / scale, faces, 313, 0.03, 5) * scale).astype(np.float32).astype(np.float64)])
+    r = so.scan_to_mesh(pts, verts, faces)
+    dist = np.sqrt(r['m'][:8])
+    assert np.abs(dist - t).max() <= 1e-5 * t.max() and (r['region'][:8] != 6).all()
+    assert not r['ambiguous'][:8].any() and r['ambiguous'].mean() <= 0.01
+
+
+def test_a_point_whose_every_face_gives_nan_has_no_winner_and_pays_nothing():
+    verts, faces = template_mesh(700)
+    a, c = faces[2, 0], faces[2, 2]
+    line = np.array([[a, a, c], [a, a, c]])
+    pts = samples(verts, faces, 200, 0.03, 7)
+    d2 = ((pts - verts[a]) * (verts[c] - verts[a])).sum(axis=1)
+    for prune in (True, False):
+        r = so.scan_to_mesh(pts, verts, line, prune=prune)
+        assert (d2 > 0).sum() > 20 and (d2 <= 0).sum() > 20
+        assert (r['face'][d2 > 0] == -1).all() and (r['face'][d2 <= 0] == 0).all()
+        assert not r['m'][d2 > 0].any() and not r['ambiguous'].any()
+        assert np.allclose(r['m'][d2 <= 0], ((pts - verts[a]) ** 2).sum(axis=1)[d2 <= 0], rtol=1e-14)
+    ref = so.evaluate(verts[None], line, pts[None], [200], None, w_s2m=1.0)
+    only = so.evaluate(verts[None], line, pts[None][:, d2 <= 0], [(d2 <= 0).sum()], None, w_s2m=1.0)
+    assert only['loss'][0] > 0 and abs(ref['loss'][0] - only['loss'][0]) <= 1e-13 * only['loss'][0]
+    assert np.array_equal(ref['grad'], only['grad'])
+    assert (ref['nearest_face'][0][d2 > 0] == -1).all()
+    # among the model's other faces the two repeated-index faces never win where their m is NaN
+    pair = np.concatenate([[[a, a, c], [a, a, a]], faces[2:]])
+    r = so.scan_to_mesh(pts, verts, pair)
+    brute = so.scan_to_mesh(pts, verts, pair, prune=False)
+    assert all(np.array_equal(r[k], brute[k]) for k in r) and (r['face'] >= 0).all() and np.isfinite(r['m']).all()
+    assert (r['face'][d2 > 0] >= 1).all()
+
+
 # ------------------------------------------------------------------------------------------------------------- ScanLoss
 def test_scanloss_argument_errors():
     eng = QuadScanEngine(np.zeros((2, 5, 3)))
