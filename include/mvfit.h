@@ -644,6 +644,30 @@ int mvfit_set_scans(mvfit_ctx* ctx, int num_bodies, int max_points, const float*
 int mvfit_scan_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float w_s2m, float w_m2s, float sigma, uint32_t search,
                     float* loss, float* g_vertices, int32_t* nearest_face, int32_t* nearest_point);
 
+/* The scan loss as a term of the fit (enable != 0; 0 switches it off and ignores the scalars).  Scan body n is problem n, so
+ * the set holds B bodies.  While it is on, a weight set with coll_loss_weight = w > 0 adds w^2 * L_j to problem j, L_j exactly
+ * loss[j] of mvfit_scan_loss(w_s2m, w_m2s, sigma, search = 0) at the trial point's vertices; its gradient is w^2 times the
+ * pull-back of that call's g_vertices through the fp32 model (the adjoint mvfit_vertices_backward computes).  The form, the
+ * record and the L < FLT_MIN rule are the silhouette term's: a problem without participating points (at w_m2s = 0) keeps the
+ * loss and gradient bits it has without the term.
+ * mvfit_closure and mvfit_fit both honour the term.  mvfit_fit runs the stages that carry it as chained rounds (pass -> clear
+ * -> face records -> scan to mesh -> mesh to scan -> sum -> dense pull-back -> record -> step kernel; kernel launches only, the
+ * term's kernels skipping finished problems, whose loss, gradient rows, partials and accumulators stay as they are); stages
+ * without it in front keep their single-launch phase.  MVFIT_F_SPARSE_VERTS is ignored while the term is active.
+ * mvfit_sdf_term_read returns L_j in sums; samples: MVFIT_E_UNSUPPORTED.  mvfit_scan_loss stays available and returns the
+ * bits it returns without the term; it shares the set's work areas with the rounds, on the ctx's stream.
+ * The scan set may be replaced while the term is on: the next fit uses the new points, and the captured round graph is kept
+ * when (N, max_points) are the same.  A set with num_bodies != B switches the term off and returns MVFIT_E_ARG; clearing the
+ * set switches it off too.  mvfit_set_problems with another batch switches the term off and keeps the scan set.  The round's
+ * buffers (12 B Nv + 4 bytes of cotangent and loss, 2112 ceil(Nv / 32) bytes of pull-back partials per problem of the batch
+ * rounded up to 32) are allocated by the first enable and keep their addresses while B stays.
+ * One term slot per ctx: MVFIT_E_STATE while mvfit_set_sdf's term, scene obstacles, the silhouette term, the vertex-target
+ * term or the term mix are configured (and those five setters return it while this term is on; the scan term has no share
+ * in the mix).  MVFIT_E_STATE also without mvfit_set_problems or without a scan set.  MVFIT_E_ARG when the set's num_bodies
+ * differs from B, for a negative or non-finite w_s2m, w_m2s or sigma, and when both weights are 0.  A refused call leaves
+ * the state as it was. */
+int mvfit_set_scan_term(mvfit_ctx* ctx, int enable, float w_s2m, float w_m2s, float sigma);
+
 /* ---- Term mix: the scene, silhouette and vertex-target terms together behind coll_loss_weight ----
  * With the mix on, a weight set with coll_loss_weight = w > 0 adds to problem j
  *   pen_j = w^2 * (scene * S_sc^2 + silhouette * L_sil + vertex_targets * L_vt),

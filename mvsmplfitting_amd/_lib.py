@@ -89,7 +89,7 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_set_silhouette_term', 'mvfit_set_silhouette_occluders', 'mvfit_silhouette_occluders_read',
            'mvfit_silhouette_hidden', 'mvfit_round_graph_info', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
            'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge',
-           'mvfit_camera_normal_eqs', 'mvfit_refine_cameras', 'mvfit_set_scans', 'mvfit_scan_loss']
+           'mvfit_camera_normal_eqs', 'mvfit_refine_cameras', 'mvfit_set_scans', 'mvfit_scan_loss', 'mvfit_set_scan_term']
 
 
 def load(path=None):
@@ -197,6 +197,8 @@ def load(path=None):
     lib.mvfit_set_scans.restype = C.c_int
     lib.mvfit_scan_loss.argtypes = [vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, vp, vp, vp, vp]
     lib.mvfit_scan_loss.restype = C.c_int
+    lib.mvfit_set_scan_term.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.mvfit_set_scan_term.restype = C.c_int
     lib.mvfit_set_term_mix.argtypes = [vp, C.POINTER(TermMix)]
     lib.mvfit_set_term_mix.restype = C.c_int
     lib.mvfit_term_mix_read.argtypes = [vp, vp]

@@ -99,5 +99,9 @@ int scan_set(ScanState& S, int nv, int nf, int N, int Pmax, const float* points,
 int scan_loss(ScanState& S, const int32_t* faces, const float* vertices, float w_s2m, float w_m2s, float sigma, bool exhaustive,
               float* loss, float* g_vertices, int32_t* nearest_face, int32_t* nearest_point, hipStream_t stream,
               std::string& err);
+// scan_loss's culled evaluation for the fit's chained rounds: kernel launches only (a capture records it as it is); gate [N] dev
+// or null - a body with gate 0 keeps everything it held; loss [N] and g_vertices [N][nv][3] dev, both written.
+int scan_round(ScanState& S, const int32_t* faces, const float* vertices, float w_s2m, float w_m2s, float sigma, const int* gate,
+               float* loss, float* g_vertices, hipStream_t stream, std::string& err);
 
 }  // namespace mvfit

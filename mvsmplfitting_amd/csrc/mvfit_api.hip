@@ -119,6 +119,11 @@ TermInputs mvfit::term_inputs(const mvfit_ctx* c) {
     in.mix.w_in = X.w_in; in.mix.w_out = X.w_out; in.mix.sigma = X.sigma;
     in.mix.g_verts = X.g_verts; in.mix.loss = X.loss; in.mix.part = X.part; in.mix.rec_scene = X.rec_scene; in.mix.rec_verts = X.rec_verts;
     in.mix.parts = X.parts; in.mix.sums = X.sums;
+    const ScanState& Z = c->scan;
+    const ScanTerm& zt = c->scant;
+    in.scan.on = Z.on; in.scan.term = zt.on; in.scan.ws = Z.ws.get(); in.scan.N = Z.N; in.scan.Pmax = Z.Pmax; in.scan.nf = Z.nf; in.scan.ns = Z.ns;
+    in.scan.faces = c->d_faces; in.scan.w_s2m = zt.w_s2m; in.scan.w_m2s = zt.w_m2s; in.scan.sigma = zt.sigma;
+    in.scan.g_verts = zt.g_verts; in.scan.loss = zt.loss; in.scan.part = zt.part;
     return in;
 }
 
@@ -234,6 +239,11 @@ void mvfit::free_term_mix(mvfit_ctx* c) {
     c->mix = TermMix{};
 }
 
+void mvfit::free_scan_term(mvfit_ctx* c) {
+    c->scanterm_mem.release();
+    c->scant = ScanTerm{};
+}
+
 void mvfit::free_vertex_targets(mvfit_ctx* c) {
     c->vtgt_mem.release();
     c->vtterm_mem.release();
@@ -256,6 +266,7 @@ static void free_problem_buffers(mvfit_ctx* c) {
     c->silt = SilTerm{};
     free_vertex_targets(c);             // and so do the vertex targets and their term
     free_term_mix(c);                   // and the term mix
+    free_scan_term(c);                  // and the scan term (the scan set is not tied to the batch: it stays)
 }
 
 extern "C" void mvfit_destroy(mvfit_ctx* c) {
@@ -356,6 +367,8 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the silhouette term uses the ctx's term slot: switch it off first");
     if (c->vt.term && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the vertex-target term uses the ctx's term slot: switch it off first");
+    if (c->scant.on && faces && num_faces != 0)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the scan term uses the ctx's term slot: switch it off first");
     if (c->mix.on && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the term mix uses the ctx's term slot (the one-person term is not part of it): switch it off first");
     HIP_OK(c, hipSetDevice(c->device));
@@ -444,8 +457,8 @@ bool mvfit::pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
 // the interpenetration term of a chained round behind its vertex pass: the steps of its plan (round_term.cpp decides which), each
 // one launch on the round's stream with no host work.  Everything a launcher takes is in the plan, but the model, the pose
 // operands and what the round itself brings: its vertices, gate, stream and the pass's tile keys of the box.
-hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, std::string& err, const float* verts,
-                              const int* gate, hipStream_t st, const unsigned long long* box_part) {
+hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, ScanState& scan, std::string& err,
+                              const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
     const int B = plan.B, nv = plan.nv;
     hipError_t e = hipSuccess;
     for (int i = 0; i < plan.n && e == hipSuccess; ++i) {
@@ -460,6 +473,10 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
         case STEP_MIX_COTANGENT:
             e = launch_term_mix_cotangent(nv, B, s.cot.lam_sil, s.cot.g_sil, s.cot.L_sil, s.cot.lam_vt, s.cot.g_vt, s.cot.L_vt, gate, s.cot.g,
                                           s.cot.L_v, s.cot.parts, s.cot.sums, st);
+            break;
+        case STEP_SCAN_EVAL:
+            if (scan_round(scan, s.scan.faces, verts, s.scan.w_s2m, s.scan.w_m2s, s.scan.sigma, gate, s.scan.loss, s.scan.g_verts, st, err))
+                e = hipErrorLaunchFailure;
             break;
         case STEP_PULLBACK:
             e = launch_silhouette_pullback(M, P, B, plan.Bpad, gate, s.pull.g_verts, s.pull.loss, s.pull.part, s.pull.rec, st);
@@ -484,7 +501,7 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
 }
 
 int mvfit::run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st) {
-    const hipError_t e = launch_term(plan_round_term(term_inputs(c)), c->M, c->P, c->sil, c->err, verts, gate, st, nullptr);
+    const hipError_t e = launch_term(plan_round_term(term_inputs(c)), c->M, c->P, c->sil, c->scan, c->err, verts, gate, st, nullptr);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s term launch: %s", term_name(c), hipGetErrorString(e));
     return MVFIT_OK;
 }

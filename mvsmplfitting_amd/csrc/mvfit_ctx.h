@@ -61,6 +61,17 @@ struct SilTerm {
     float* part = nullptr;             // slice partials of the pull-back (vjp_part_bytes)
 };
 
+// the scan term inside the fit (mvfit_set_scan_term): scalars and the buffers of a chained round, owned by
+// mvfit_ctx::scanterm_mem.  They are allocated by the first enable for the batch and keep their addresses while B stays; the
+// scan set itself (ScanState) is not tied to the batch.
+struct ScanTerm {
+    bool on = false;
+    float w_s2m = 1.f, w_m2s = 0.f, sigma = 0.f;
+    float* g_verts = nullptr;          // [B][nv][3] the round's vertex cotangent
+    float* loss = nullptr;             // [B] L_j of the last evaluation
+    float* part = nullptr;             // slice partials of the pull-back (vjp_part_bytes)
+};
+
 struct mvfit_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -74,6 +85,7 @@ struct mvfit_ctx {
     DevPool problem_mem, ring_mem, obst_mem, silterm_mem;
     DevPool vtgt_mem, vtterm_mem;      // the vertex-target set (re-made when (B, K) change) and its term's round buffers
     DevPool mix_mem;                   // the term mix's round buffers (mvfit_set_term_mix)
+    DevPool scanterm_mem;              // the scan term's round buffers (mvfit_set_scan_term)
     // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
     DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
     DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
@@ -94,6 +106,7 @@ struct mvfit_ctx {
     SilTerm silt;
     // scan set of the scan loss (mvfit_set_scans, scan_loss.hip): points, face records and work areas
     ScanState scan;
+    ScanTerm scant;
     // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
     VtxTargets vt;
     // the weighted sum of the scene, silhouette and vertex-target terms (mvfit_set_term_mix, term_mix.hip)
@@ -195,24 +208,28 @@ int ensure_sdf_buffers(mvfit_ctx* c);
 bool pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi);
 // the round's term: what launch_term needs is in the plan (round_term.h) - it never sees the ctx
 TermInputs term_inputs(const mvfit_ctx* c);
-hipError_t launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, std::string& err, const float* verts,
-                       const int* gate, hipStream_t st, const unsigned long long* box_part);
+hipError_t launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, ScanState& scan, std::string& err,
+                       const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part);
 int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st);
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
 void free_vertex_targets(mvfit_ctx* c);
 void free_term_mix(mvfit_ctx* c);
+void free_scan_term(mvfit_ctx* c);
 inline const char* term_name(const mvfit_ctx* c) { return term_kind_name(term_slot(term_inputs(c))); }
 // a term other than mvfit_set_sdf's is configured: it runs in chained rounds only and keeps no per-vertex samples
 inline bool round_term(const mvfit_ctx* c) { return term_slot(term_inputs(c)) != TERM_SDF; }
 
 // A data set a term reads went away (or is about to be re-made): its own term goes off, and so does a mix that gives it a share.
-enum TermSource { SRC_OBSTACLES = 0, SRC_MASKS, SRC_TARGETS };
-inline bool& term_flag(mvfit_ctx* c, TermSource src) { return src == SRC_OBSTACLES ? c->obst.on : src == SRC_MASKS ? c->silt.on : c->vt.term; }
+// The scan set has no share in the mix: SRC_SCANS stands behind the sources that have one.
+enum TermSource { SRC_OBSTACLES = 0, SRC_MASKS, SRC_TARGETS, SRC_SCANS };
+inline bool& term_flag(mvfit_ctx* c, TermSource src) {
+    return src == SRC_OBSTACLES ? c->obst.on : src == SRC_MASKS ? c->silt.on : src == SRC_TARGETS ? c->vt.term : c->scant.on;
+}
 inline void term_source_gone(mvfit_ctx* c, TermSource src) {
     const float share[] = {c->mix.scene, c->mix.silhouette, c->mix.vertex_targets};
     term_flag(c, src) = false;
-    if (share[src] > 0.f) c->mix.on = false;
+    if (src < SRC_SCANS && share[src] > 0.f) c->mix.on = false;
 }
 // the same around a re-make that can fail: a failure leaves no term behind, restore() after success brings both flags back
 struct TermSuspend {

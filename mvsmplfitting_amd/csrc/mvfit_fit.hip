@@ -76,7 +76,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         for (int r = 0; r < kGraphRounds && e == hipSuccess; ++r) {
             e = launch_vertex_pass(c->M, Pg, c->B, c->pb.verts, c->opt.pass_kernel, cs);
             if (e == hipSuccess && c->F.sdf_adj)
-                e = launch_term(term, c->M, c->P, c->sil, c->err, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
+                e = launch_term(term, c->M, c->P, c->sil, c->scan, c->err, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
             launch_fit_step(O.reuse_outer != 0, c->B, cs, c->M, c->pb.obs, c->V, SW, O, c->P, c->F);
         }
         hipError_t e2 = hipStreamEndCapture(cs, &g);
@@ -488,7 +488,7 @@ extern "C" int mvfit_fit(mvfit_ctx* c, const mvfit_weights* sw, const mvfit_lbfg
     const bool any_sdf = in.sdf_stages != 0;
     if (any_sdf && !c->sdf_num_faces && !round_term(c))
         return fail(c, MVFIT_E_STATE, "coll_loss_weight > 0 needs the SDF term's faces: call mvfit_set_sdf first");
-    if (round_term(c)) in.sdf_service = 0;      // the scene, silhouette and vertex-target terms and their mix run in chained rounds only (no service path for them)
+    if (round_term(c)) in.sdf_service = 0;      // the scene, silhouette, vertex-target and scan terms and the mix run in chained rounds only (no service path for them)
     if (any_sdf) {
         int rc = ensure_sdf_buffers(c);
         if (rc) return rc;

@@ -8,11 +8,12 @@
 namespace mvfit {
 
 TermKind term_slot(const TermInputs& in) {
-    return in.mix.on ? TERM_MIX : in.vt.term ? TERM_VERTEX_TARGET : in.silt.on ? TERM_SILHOUETTE : in.obst.on ? TERM_SCENE : TERM_SDF;
+    return in.mix.on ? TERM_MIX : in.vt.term ? TERM_VERTEX_TARGET : in.silt.on ? TERM_SILHOUETTE : in.scan.term ? TERM_SCAN :
+           in.obst.on ? TERM_SCENE : TERM_SDF;
 }
 
 const char* term_kind_name(TermKind kind) {
-    static const char* const names[] = {"sdf", "scene", "silhouette", "vertex-target", "mix"};
+    static const char* const names[] = {"sdf", "scene", "silhouette", "vertex-target", "mix", "scan"};
     return names[kind];
 }
 
@@ -41,6 +42,13 @@ struct Builder {
         VtEvalStep& s = add(STEP_VT_EVAL).vt;
         s.K = in.vt.K; s.targets = in.vt.targets; s.weights = in.vt.weights; s.partial = in.vt.partial;
         s.loss = in.vt.loss; s.g_verts = in.vt.g_verts;
+    }
+    void scan_eval() {
+        ScanEvalStep& s = add(STEP_SCAN_EVAL).scan;
+        s.ws = in.scan.ws; s.faces = in.scan.faces;
+        s.N = in.scan.N; s.Pmax = in.scan.Pmax; s.nf = in.scan.nf; s.ns = in.scan.ns;
+        s.w_s2m = in.scan.w_s2m; s.w_m2s = in.scan.w_m2s; s.sigma = in.scan.sigma;
+        s.loss = in.scan.loss; s.g_verts = in.scan.g_verts;
     }
     void pullback(const float* g_verts, const float* loss, float* part, SdfAdj* rec) {
         PullbackStep& s = add(STEP_PULLBACK).pull;
@@ -108,6 +116,11 @@ RoundTermPlan plan_round_term(const TermInputs& in, bool live) {
         b.sil_eval(in.silt.w_in, in.silt.w_out, in.silt.sigma);
         b.pullback(in.silt.g_verts, in.silt.loss, in.silt.part, in.sdf_adj);
         b.sums_at(in.silt.loss, sizeof(float));
+        break;
+    case TERM_SCAN:
+        b.scan_eval();
+        b.pullback(in.scan.g_verts, in.scan.loss, in.scan.part, in.sdf_adj);
+        b.sums_at(in.scan.loss, sizeof(float));
         break;
     case TERM_SCENE:
         b.scene(in.sdf_adj);

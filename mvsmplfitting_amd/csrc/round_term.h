@@ -58,15 +58,25 @@ struct TermInputs {
         SdfAdj *rec_scene = nullptr, *rec_verts = nullptr;
         float *parts = nullptr, *sums = nullptr;
     } mix;
+    struct {            // the scan set (ScanState), the scan term and its round buffers (ScanTerm)
+        bool on = false, term = false;
+        const void* ws = nullptr;
+        int N = 0, Pmax = 0, nf = 0, ns = 0;
+        const int32_t* faces = nullptr;
+        float w_s2m = 0.f, w_m2s = 0.f, sigma = 0.f;
+        float *g_verts = nullptr, *loss = nullptr, *part = nullptr;
+    } scan;
 };
 
-enum TermKind { TERM_SDF = 0, TERM_SCENE, TERM_SILHOUETTE, TERM_VERTEX_TARGET, TERM_MIX };
+enum TermKind { TERM_SDF = 0, TERM_SCENE, TERM_SILHOUETTE, TERM_VERTEX_TARGET, TERM_MIX, TERM_SCAN };
 
-// who holds the term slot: the mix, else the vertex-target term, the silhouette term, the obstacles, else mvfit_set_sdf's term
+// who holds the term slot: the mix, else the vertex-target term, the silhouette term, the scan term, the obstacles, else
+// mvfit_set_sdf's term
 TermKind term_slot(const TermInputs& in);
 const char* term_kind_name(TermKind kind);
 
-enum StepKind { STEP_SIL_EVAL = 1, STEP_VT_EVAL, STEP_MIX_COTANGENT, STEP_PULLBACK, STEP_SCENE, STEP_MIX_RECORD, STEP_SDF };
+enum StepKind { STEP_SIL_EVAL = 1, STEP_VT_EVAL, STEP_MIX_COTANGENT, STEP_PULLBACK, STEP_SCENE, STEP_MIX_RECORD, STEP_SDF,
+                STEP_SCAN_EVAL };
 
 // sil_round: the mask set's baked values (occluders only when they are set), the scalars, the round buffers it writes
 struct SilEvalStep {
@@ -122,6 +132,15 @@ struct SdfStep {
     void* cull;
 };
 
+// scan_round: the scan set's baked values (the workspace's layout follows from the sizes), the scalars, the round buffers it writes
+struct ScanEvalStep {
+    const void* ws;
+    const int32_t* faces;
+    int N, Pmax, nf, ns;
+    float w_s2m, w_m2s, sigma;
+    float *loss, *g_verts;
+};
+
 struct TermStep {
     int kind;           // StepKind
     union {
@@ -132,6 +151,7 @@ struct TermStep {
         SceneStep scene;
         MixRecordStep rec;
         SdfStep sdf;
+        ScanEvalStep scan;
     };
 };
 

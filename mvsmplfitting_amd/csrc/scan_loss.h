@@ -1,5 +1,5 @@
 // The scan set a ctx keeps between mvfit_set_scans and the loss calls (scan_loss.hip; driven by mvfit_scan.hip through
-// launchers.h: scan_set / scan_loss).
+// launchers.h: scan_set / scan_loss; the fit's rounds evaluate on the same set through scan_round).
 #pragma once
 #include <cstddef>
 #include <cstdint>

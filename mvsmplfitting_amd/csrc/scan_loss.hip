@@ -4,7 +4,7 @@
 // Prepared once per scan set (scan_set):
 //   scan_pack_kernel: point i of body n -> (x, y, z, w) when it takes part (i < count[n] and w > 0), else (NaN, NaN, NaN, 0);
 //       the point itself is read only when it takes part.
-// Per evaluation (scan_loss):
+// Per evaluation (scan_loss; scan_round inside the fit's chained rounds - the same kernels behind a per-body gate):
 //   scan_face_kernel: a thread per (body, face): the record (bounding sphere centre, padded radius | a | b - a | c - a), 64 B,
 //       and vertex a of every SCAN_SEED-th face in a compact list (the seed of the cull's bound).
 //   scan_s2m_kernel<CULL> (term S, the hot one): a workgroup owns 256 points of one body, the point in registers; the body's
@@ -19,6 +19,8 @@
 //       through LDS in tiles of SCAN_PT, same minimum.  Then g = w_m2s rho' 2 (v - p) + w_s2m 2^-e_n acc / 2^32 in float64,
 //       rounded and stored once; rho to one float64 partial per workgroup.
 //   scan_sum_kernel: a wave per body, the partials of each term in ascending order.
+//   scan_clear_kernel (scan_round only): zeroes the accumulators of the bodies the gate keeps - a kernel node where scan_loss
+//       has a memset, which a captured round graph must not hold.
 // No float atomics; nothing a body gets depends on the other bodies of the call or on its position in it.
 //
 // The cull.  sb is an upper bound of the distance from p to the surface: at first the distance to the nearest of the seed
@@ -105,6 +107,16 @@ __device__ __forceinline__ void scan_block_sum(double s, double* sh_d, double* o
     }
 }
 
+// The gate of the term inside the fit's chained rounds (scan_round): gate[body] == 0 - a finished problem, or a stage without
+// the term - ends the workgroup at once, so the body keeps its loss, gradient rows, partials and accumulators; a null pointer
+// keeps every body.  The read is uniform per workgroup (blockIdx.y).  The ungated instantiations carry an empty argument and
+// are the kernels as they were.
+template <bool GATED> struct ScanGate { __device__ __forceinline__ bool off(int) const { return false; } };
+template <> struct ScanGate<true> {
+    const int* gate;
+    __device__ __forceinline__ bool off(int body) const { return gate && !gate[body]; }
+};
+
 // ---------------------------------------------------------------------------------------------------------- prepared once
 // grid (ceil(Pmax / SCAN_NT), N)
 __global__ __launch_bounds__(SCAN_NT) void scan_pack_kernel(const float* __restrict__ pts, const float* __restrict__ wts, int Pmax,
@@ -122,9 +134,12 @@ __global__ __launch_bounds__(SCAN_NT) void scan_pack_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------- per evaluation
 // grid (ceil(nf / SCAN_NT), N): rec[(n nf + f) 4 + {0..3}] = (centre, padded radius), (a, 0), (ab, 0), (ac, 0);
 // seed[n ns + f / SCAN_SEED] = (a, 0) for f % SCAN_SEED == 0
+template <bool GATED>
 __global__ __launch_bounds__(SCAN_NT) void scan_face_kernel(const float* __restrict__ verts, int nv, const int32_t* __restrict__ faces,
-                                                            int nf, int ns, float4* __restrict__ rec, float4* __restrict__ seed) {
+                                                            int nf, int ns, float4* __restrict__ rec, float4* __restrict__ seed,
+                                                            ScanGate<GATED> G) {
     const int f = blockIdx.x * SCAN_NT + threadIdx.x, n = blockIdx.y;
+    if (G.off(n)) return;
     if (f >= nf) return;
     const float* vb = verts + (size_t)n * nv * 3;
     const float *pa = vb + (size_t)faces[f * 3] * 3, *pb = vb + (size_t)faces[f * 3 + 1] * 3, *pc = vb + (size_t)faces[f * 3 + 2] * 3;
@@ -150,19 +165,27 @@ __global__ __launch_bounds__(SCAN_NT) void scan_face_kernel(const float* __restr
     if (f % SCAN_SEED == 0) seed[(size_t)n * ns + f / SCAN_SEED] = o[1];
 }
 
+// grid (ceil(3 nv / SCAN_NT), N): acc[n][nv][3] = 0 for the bodies the gate keeps
+__global__ __launch_bounds__(SCAN_NT) void scan_clear_kernel(unsigned long long* __restrict__ acc, int nv, ScanGate<true> G) {
+    const int i = blockIdx.x * SCAN_NT + threadIdx.x, n = blockIdx.y;
+    if (G.off(n)) return;
+    if (i < nv * 3) acc[(size_t)n * nv * 3 + i] = 0ull;
+}
+
 // grid (ceil(Pmax / SCAN_NT), N): 256 points of body n against its nf face records.
 // acc[(n nv + vertex) 3 + axis] += round(2^32 (2^e_n w_p) rho'(m) 2 d[axis] b_k), e_n = expo[n] (scan_set: the body's largest
 // weight scaled into [1, 2)); partS[n gridDim.x + blockIdx.x] = sum of w_p rho.
-template <bool CULL>
+template <bool CULL, bool GATED>
 __global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restrict__ pk, const int* __restrict__ count,
                                                            const int* __restrict__ expo, int Pmax,
                                                            const float4* __restrict__ rec, const float4* __restrict__ seed,
                                                            int nf, int ns, const int32_t* __restrict__ faces, int nv, float sigma,
                                                            unsigned long long* __restrict__ acc, double* __restrict__ partS,
-                                                           int32_t* __restrict__ nearest) {
+                                                           int32_t* __restrict__ nearest, ScanGate<GATED> G) {
     __shared__ __attribute__((aligned(16))) float4 sh[SCAN_FT * 4];
     __shared__ double sh_d[SCAN_NT / 64];
     const int tid = threadIdx.x, n = blockIdx.y, i = blockIdx.x * SCAN_NT + tid;
+    if (G.off(n)) return;                                            // (uniform)
     const bool inside = i < Pmax;
     if (blockIdx.x * SCAN_NT >= count[n]) {                          // (uniform) no point of this workgroup takes part
         if (inside && nearest) nearest[(size_t)n * Pmax + i] = -1;
@@ -248,16 +271,17 @@ __global__ __launch_bounds__(SCAN_NT) void scan_s2m_kernel(const float4* __restr
 
 // grid (ceil(nv / SCAN_NT), N): thread = (body n, vertex j).  SEARCH: the nearest participating point (term M).  Either way
 // the vertex's gradient is finished here: g = w_m2s rho' 2 (v - p) + w_s2m 2^-e_n acc / 2^32.
-template <bool SEARCH>
+template <bool SEARCH, bool GATED>
 __global__ __launch_bounds__(SCAN_NT) void scan_m2s_kernel(const float* __restrict__ verts, int nv, const float4* __restrict__ pk,
                                                            const int* __restrict__ count, const int* __restrict__ expo, int Pmax,
                                                            float w_s2m, float w_m2s,
                                                            float sigma, const long long* __restrict__ acc,
                                                            float* __restrict__ g_verts, double* __restrict__ partM,
-                                                           int32_t* __restrict__ nearest) {
+                                                           int32_t* __restrict__ nearest, ScanGate<GATED> G) {
     __shared__ __attribute__((aligned(16))) float4 sh[SEARCH ? SCAN_PT : 1];
     __shared__ double sh_d[SCAN_NT / 64];
     const int tid = threadIdx.x, n = blockIdx.y, j = blockIdx.x * SCAN_NT + tid;
+    if (G.off(n)) return;                                            // (uniform)
     const bool live = j < nv;
     const float* pv = verts + ((size_t)n * nv + (live ? j : 0)) * 3;
     const float x[3] = {pv[0], pv[1], pv[2]};
@@ -303,9 +327,11 @@ __global__ __launch_bounds__(SCAN_NT) void scan_m2s_kernel(const float* __restri
 }
 
 // grid (N), one wave: loss[n] = float32(w_s2m S_n + w_m2s M_n); a term whose partials are null is left out
+template <bool GATED>
 __global__ __launch_bounds__(64) void scan_sum_kernel(const double* __restrict__ partS, int nblkP, const double* __restrict__ partM,
-                                                      int nblkV, float w_s2m, float w_m2s, float* __restrict__ loss) {
+                                                      int nblkV, float w_s2m, float w_m2s, float* __restrict__ loss, ScanGate<GATED> G) {
     const int n = blockIdx.x, lane = threadIdx.x;
+    if (G.off(n)) return;
     double tot = 0.0;
     if (partS) {
         double s = 0.0;
@@ -403,29 +429,68 @@ int scan_loss(ScanState& S, const int32_t* faces, const float* vertices, float w
     unsigned long long* acc = termS && g_vertices ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
     if (termS) {
         if (acc) SCAN_HIP(hipMemsetAsync(acc, 0, (size_t)N * nv * 24, stream));
-        hipLaunchKernelGGL(scan_face_kernel, dim3(scan_blocks(nf), N), dim3(SCAN_NT), 0, stream, vertices, nv, faces, nf, S.ns, rec,
-                           seed);
+        hipLaunchKernelGGL(scan_face_kernel<false>, dim3(scan_blocks(nf), N), dim3(SCAN_NT), 0, stream, vertices, nv, faces, nf, S.ns,
+                           rec, seed, ScanGate<false>{});
         if (exhaustive)
-            hipLaunchKernelGGL(scan_s2m_kernel<false>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
-                               (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face);
+            hipLaunchKernelGGL((scan_s2m_kernel<false, false>), dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
+                               (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face,
+                               ScanGate<false>{});
         else
-            hipLaunchKernelGGL(scan_s2m_kernel<true>, dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
-                               (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face);
+            hipLaunchKernelGGL((scan_s2m_kernel<true, false>), dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
+                               (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, nearest_face,
+                               ScanGate<false>{});
     } else if (nearest_face) {
         SCAN_HIP(hipMemsetAsync(nearest_face, 0xff, (size_t)N * Pmax * 4, stream));
     }
     if (termM)
-        hipLaunchKernelGGL(scan_m2s_kernel<true>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
-                           w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, nearest_point);
+        hipLaunchKernelGGL((scan_m2s_kernel<true, false>), dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
+                           w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, nearest_point,
+                           ScanGate<false>{});
     else {
         if (g_vertices)
-            hipLaunchKernelGGL(scan_m2s_kernel<false>, dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
-                               w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM,
-                               (int32_t*)nullptr);
+            hipLaunchKernelGGL((scan_m2s_kernel<false, false>), dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo,
+                               Pmax, w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM,
+                               (int32_t*)nullptr, ScanGate<false>{});
         if (nearest_point) SCAN_HIP(hipMemsetAsync(nearest_point, 0xff, (size_t)N * nv * 4, stream));
     }
-    hipLaunchKernelGGL(scan_sum_kernel, dim3(N), dim3(64), 0, stream, termS ? (const double*)partS : nullptr, nblkP,
-                       termM ? (const double*)partM : nullptr, nblkV, w_s2m, w_m2s, loss);
+    hipLaunchKernelGGL(scan_sum_kernel<false>, dim3(N), dim3(64), 0, stream, termS ? (const double*)partS : nullptr, nblkP,
+                       termM ? (const double*)partM : nullptr, nblkV, w_s2m, w_m2s, loss, ScanGate<false>{});
+    SCAN_HIP(hipGetLastError());
+    return MVFIT_OK;
+}
+
+// One evaluation for the fit's chained rounds: scan_loss's sequence (culled search, loss and gradient, no nearest outputs) with
+// the gated kernels.  No host work, no memset and no copy, so a stream capture records it as it is - kernel nodes only: the
+// accumulators are cleared by scan_clear_kernel.  Per body the loss and the gradient are scan_loss's bits at the same vertices.
+int scan_round(ScanState& S, const int32_t* faces, const float* vertices, float w_s2m, float w_m2s, float sigma, const int* gate,
+               float* loss, float* g_vertices, hipStream_t stream, std::string& err) {
+    const int N = S.N, Pmax = S.Pmax, nv = S.nv, nf = S.nf, nblkP = scan_blocks(Pmax), nblkV = scan_blocks(nv);
+    unsigned char* const ws = S.ws.as<unsigned char>();
+    const float4* pk = reinterpret_cast<const float4*>(ws + S.o_pk);
+    const int* count = reinterpret_cast<const int*>(ws + S.o_cnt);
+    const int* expo = count + N;
+    float4* rec = reinterpret_cast<float4*>(ws + S.o_rec);
+    float4* seed = reinterpret_cast<float4*>(ws + S.o_seed);
+    double* partS = reinterpret_cast<double*>(ws + S.o_partS);
+    double* partM = reinterpret_cast<double*>(ws + S.o_partM);
+    const bool termS = w_s2m > 0.f, termM = w_m2s > 0.f;
+    unsigned long long* acc = termS ? reinterpret_cast<unsigned long long*>(ws + S.o_acc) : nullptr;
+    const ScanGate<true> G{gate};
+    if (termS) {
+        hipLaunchKernelGGL(scan_clear_kernel, dim3(scan_blocks(nv * 3), N), dim3(SCAN_NT), 0, stream, acc, nv, G);
+        hipLaunchKernelGGL(scan_face_kernel<true>, dim3(scan_blocks(nf), N), dim3(SCAN_NT), 0, stream, vertices, nv, faces, nf, S.ns,
+                           rec, seed, G);
+        hipLaunchKernelGGL((scan_s2m_kernel<true, true>), dim3(nblkP, N), dim3(SCAN_NT), 0, stream, pk, count, expo, Pmax,
+                           (const float4*)rec, (const float4*)seed, nf, S.ns, faces, nv, sigma, acc, partS, (int32_t*)nullptr, G);
+    }
+    if (termM)
+        hipLaunchKernelGGL((scan_m2s_kernel<true, true>), dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
+                           w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, (int32_t*)nullptr, G);
+    else
+        hipLaunchKernelGGL((scan_m2s_kernel<false, true>), dim3(nblkV, N), dim3(SCAN_NT), 0, stream, vertices, nv, pk, count, expo, Pmax,
+                           w_s2m, w_m2s, sigma, reinterpret_cast<const long long*>(acc), g_vertices, partM, (int32_t*)nullptr, G);
+    hipLaunchKernelGGL(scan_sum_kernel<true>, dim3(N), dim3(64), 0, stream, termS ? (const double*)partS : nullptr, nblkP,
+                       termM ? (const double*)partM : nullptr, nblkV, w_s2m, w_m2s, loss, G);
     SCAN_HIP(hipGetLastError());
     return MVFIT_OK;
 }

@@ -128,6 +128,7 @@ class MvFit:
         self._vt_term = False
         self._mix = None                         # the shares of set_term_mix while it is on
         self._scan_shape = None                  # (N, Pmax) of set_scans while a scan set is present
+        self._scan_term = False
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -230,6 +231,7 @@ class MvFit:
             self._sil_term = False               # (and switches the silhouette term off)
             self._vt_term = False                # (and clears the vertex targets with their term)
             self._mix = None                     # (and switches the term mix off)
+            self._scan_term = False              # (and the scan term; the scan set stays)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -574,14 +576,32 @@ class MvFit:
             w = _f32(np.asarray(w))
             if w.shape != (N, Pmax):
                 raise MvFitError('weights must be [%d, %d], got %r' % (N, Pmax, tuple(w.shape)))
-        self._check(self._lib.mvfit_set_scans(self._ctx, N, Pmax, p.data_ptr(), cnt.ctypes.data_as(_lib._ip),
-                                              w.ctypes.data_as(_lib._fp) if w is not None else None))
+        rc = self._lib.mvfit_set_scans(self._ctx, N, Pmax, p.data_ptr(), cnt.ctypes.data_as(_lib._ip),
+                                       w.ctypes.data_as(_lib._fp) if w is not None else None)
+        if rc and self._scan_term and (N != self.B or rc != -1):
+            self._scan_term = False              # (a set that fails, or does not fit an enabled term, switches the term off)
+        self._check(rc)
         self._scan_shape = (N, Pmax)
 
     def clear_scans(self):
         """Remove the scan set of set_scans."""
         self._check(self._lib.mvfit_set_scans(self._ctx, 0, 0, None, None, None))
         self._scan_shape = None
+        self._scan_term = False                  # (no scans, no term: the C side switches it off)
+
+    def set_scan_term(self, w_s2m=1.0, w_m2s=0.0, sigma=0.0):
+        """Make the scan loss of the current scan set a term of closure() and fit() (include/mvfit.h:mvfit_set_scan_term): a
+        stage with coll_loss_weight w > 0 adds w^2 * L_j to problem j, L_j = scan_loss(w_s2m, w_m2s, sigma) of the trial
+        point's vertices (scan body j is problem j), with its gradient through the model.  fit() runs such stages as chained
+        rounds.  Needs set_problems and a scan set of B bodies; excludes set_sdf's term, scene obstacles, the silhouette and
+        vertex-target terms and the term mix.  A second call with other scalars replaces them."""
+        self._check(self._lib.mvfit_set_scan_term(self._ctx, 1, float(w_s2m), float(w_m2s), float(sigma)))
+        self._scan_term = True
+
+    def clear_scan_term(self):
+        """Switch the term of set_scan_term off (the scan set stays)."""
+        self._check(self._lib.mvfit_set_scan_term(self._ctx, 0, 0.0, 0.0, 0.0))
+        self._scan_term = False
 
     def scan_loss(self, vertices, w_s2m=1.0, w_m2s=0.0, sigma=0.0, need_grad=True, return_nearest=False, search='auto'):
         """The scan loss of the scan set at vertices[N,Nv,3], translation included (include/mvfit.h:mvfit_scan_loss): w_s2m
@@ -973,9 +993,9 @@ class MvFit:
     def sdf_term_read(self):
         """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
         (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set; so does the silhouette term
-        (set_silhouette_term) and the vertex-target term (set_vertex_target_term), whose S is the loss L_j itself, and the
-        term mix (set_term_mix), whose S is the weighted sum of its parts."""
-        smp = None if (self._obstacles or self._sil_term or self._vt_term or self._mix) else torch.empty(self.B, self.nv, 4, device=self.device)
+        (set_silhouette_term), the vertex-target term (set_vertex_target_term) and the scan term (set_scan_term), whose S is
+        the loss L_j itself, and the term mix (set_term_mix), whose S is the weighted sum of its parts."""
+        smp = None if (self._obstacles or self._sil_term or self._vt_term or self._mix or self._scan_term) else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S

@@ -1,6 +1,7 @@
 """The scan loss - measured 3-D surface points against the posed body and back - as a differentiable PyTorch module, depth maps
-turned into such points, and a small driver that refines a fit with it (include/mvfit.h:mvfit_set_scans / mvfit_scan_loss;
-csrc/scan_loss.hip).
+turned into such points, and two drivers that refine a fit with it: refine_to_scan (a torch L-BFGS on shape, scale and
+translation) and refine_fit (the term inside the engine's own fit rounds, moving pose, shape and translation together with the
+keypoint term and the priors) (include/mvfit.h:mvfit_set_scans / mvfit_scan_loss / mvfit_set_scan_term; csrc/scan_loss.hip).
 
 Keypoints leave limb girth and the body's depth along the viewing rays almost free; a depth camera, a multi-view-stereo point
 cloud or a registered scan pins both down.  A scan has no correspondences with the model, so the loss searches them at every
@@ -18,8 +19,8 @@ backward scales it by each body's incoming gradient.  Once differentiable: there
 
 Distances are in the unit of the vertices (metres for SMPL), sigma is in that unit, the loss in its square.
 
-Not built here: the term inside the engine's own fit rounds, a share for it in the term mix, a scans= option of the folder
-driver, normals (a point pulls the nearest surface whichever way it faces).
+Not built here: a share for the term in the term mix, a scans= option of the folder driver, normals (a point pulls the nearest
+surface whichever way it faces).
 """
 from __future__ import annotations
 
@@ -206,3 +207,47 @@ def refine_to_scan(layer, params, points, count=None, weights=None, *, free=('be
     report = dict(before=before.tolist(), after=after.tolist(), accepted=accepted.tolist(), scan_before=scan_before.tolist(),
                   scan_after=scan_after.tolist(), iterations=n_iter)
     return out, report
+
+
+def refine_fit(engine, params, stage, *, w_s2m=1.0, w_m2s=0.0, sigma=0.0, **fit_kwargs):
+    """One fit of the engine's B problems with the scan term inside the fit's rounds.
+
+    params [B,118] (set_problems and set_scans done: scan body j is problem j); ``stage``: one weight dict with
+    coll_loss_weight w > 0.  The objective of problem j is its closure loss under ``stage`` with the term on: the stage's
+    keypoint and prior terms + w^2 * scan_loss_j(w_s2m, w_m2s, sigma).
+
+      1. the term is switched on; one closure gives J(x_0) and the scan losses L(x_0);
+      2. x' = engine.fit(x_0, [stage], **fit_kwargs); one closure gives J(x'), L(x');
+      3. problem j keeps its row of x' iff J_j(x') < J_j(x_0); otherwise the row reverts to x_0 exactly;
+      4. the engine is left with the term cleared (also when something raises); the scan set stays.
+
+    Returns (params, report).  report: dict(before [B], after [B] = J of the returned rows, accepted [B] bool,
+    scan_before [B], scan_after [B] = L of the returned rows, n_closure [B] of the fit, loss [B] = after)."""
+    if float(stage.get('coll_loss_weight', 0.0)) <= 0.0:
+        raise ValueError('refine_fit: the stage needs coll_loss_weight > 0')
+    x0 = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, np.float32))
+    x0 = x0.to(engine.device).clone()
+
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+    def objective(x):
+        J = engine.closure(x, stage, want_grad=False)['loss']
+        return host(J).astype(np.float64), host(engine.sdf_term_read()[1]).astype(np.float64)
+
+    engine.set_scan_term(w_s2m=w_s2m, w_m2s=w_m2s, sigma=sigma)
+    try:
+        before, scan_before = objective(x0)
+        x1, st = engine.fit(x0, [stage], **fit_kwargs)
+        x1 = x1.to(x0.dtype)
+        after, scan_after = objective(x1)
+        accepted = after < before
+        for j in np.flatnonzero(~accepted):
+            x1[int(j)] = x0[int(j)]
+        after = np.where(accepted, after, before)
+        scan_after = np.where(accepted, scan_after, scan_before)
+        report = dict(before=before, after=after, accepted=accepted, scan_before=scan_before, scan_after=scan_after,
+                      n_closure=host(st['n_closure']), loss=after.copy())
+        return x1, report
+    finally:
+        engine.clear_scan_term()
