@@ -662,24 +662,28 @@ int mvfit_scan_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float
  * buffers (12 B Nv + 4 bytes of cotangent and loss, 2112 ceil(Nv / 32) bytes of pull-back partials per problem of the batch
  * rounded up to 32) are allocated by the first enable and keep their addresses while B stays.
  * One term slot per ctx: MVFIT_E_STATE while mvfit_set_sdf's term, scene obstacles, the silhouette term, the vertex-target
- * term or the term mix are configured (and those five setters return it while this term is on; the scan term has no share
- * in the mix).  MVFIT_E_STATE also without mvfit_set_problems or without a scan set.  MVFIT_E_ARG when the set's num_bodies
+ * term or the term mix are configured (and those five setters return it while this term is on; next to other terms the scan
+ * loss runs as a share of the mix, mvfit_term_mix::scan).  MVFIT_E_STATE also without mvfit_set_problems or without a scan set.  MVFIT_E_ARG when the set's num_bodies
  * differs from B, for a negative or non-finite w_s2m, w_m2s or sigma, and when both weights are 0.  A refused call leaves
  * the state as it was. */
 int mvfit_set_scan_term(mvfit_ctx* ctx, int enable, float w_s2m, float w_m2s, float sigma);
 
-/* ---- Term mix: the scene, silhouette and vertex-target terms together behind coll_loss_weight ----
+/* ---- Term mix: the scene, silhouette, vertex-target and scan terms together behind coll_loss_weight ----
  * With the mix on, a weight set with coll_loss_weight = w > 0 adds to problem j
- *   pen_j = w^2 * (scene * S_sc^2 + silhouette * L_sil + vertex_targets * L_vt),
- * S_sc what the scene term's record holds against the frozen obstacles (mvfit_set_scene_obstacles), L_sil and L_vt exactly
- * loss[j] of mvfit_silhouette_loss(num_bodies = B, sil_w_in, sil_w_out, sil_sigma) and of mvfit_vertex_target_loss at the
- * trial point's vertices; the gradient is the same weighted sum of the three terms' gradients.  The shares are >= 0 and at
+ *   pen_j = w^2 * (scene * S_sc^2 + silhouette * L_sil + vertex_targets * L_vt + scan * L_scan),
+ * S_sc what the scene term's record holds against the frozen obstacles (mvfit_set_scene_obstacles), L_sil, L_vt and L_scan
+ * exactly loss[j] of mvfit_silhouette_loss(num_bodies = B, sil_w_in, sil_w_out, sil_sigma), of mvfit_vertex_target_loss and
+ * of mvfit_scan_loss(scan_w_s2m, scan_w_m2s, scan_sigma, search = 0) at the trial point's vertices (scan body n is problem
+ * n); the gradient is the same weighted sum of the four terms' gradients.  The shares are >= 0 and at
  * least two are > 0 (a single term keeps its own setter); a component with share 0 is never evaluated and its buffers are
  * never read.  The one-person SDF term of mvfit_set_sdf is NOT part of the mix.
  * Arithmetic (csrc/term_mix.hip; reproducible by a NumPy restatement).  The vertex terms share ONE dense pull-back: its
- * cotangent is, per float, g = fl32(silhouette * g_sil) + fl32(vertex_targets * g_vt) - two rounded products, one rounded add,
- * nothing fused - and its loss L_v = float32(double(silhouette) * L_sil + double(vertex_targets) * L_vt); with one vertex term
+ * cotangent is, per float, g = (fl32(silhouette * g_sil) + fl32(vertex_targets * g_vt)) + fl32(scan * g_scan) - rounded products,
+ * rounded adds in this order, nothing fused, a component with share 0 left out and not added as 0 - and its loss L_v =
+ * float32((double(silhouette) * L_sil + double(vertex_targets) * L_vt) + double(scan) * L_scan); with one vertex term
  * live, only that product is formed, and with its share equal to 1 the term's own buffers go to the pull-back unchanged.
+ * A problem whose scan body has no participating points (at scan_w_m2s = 0) has L_scan = 0 and an all-zero g_scan: it adds
+ * exactly 0 to L_v and an exactly zero cotangent.
  * With scene = 0 the pull-back writes the closure's record.  With scene > 0 the scene term and the pull-back write records
  * (S_sc, a_sc) and (S_v, a_v) of their own, merged per problem in float64, every operation rounded on its own:
  *   Q = scene * (S_sc * S_sc) + S_v * S_v ;  S = float32(sqrt(Q)) ;
@@ -688,43 +692,57 @@ int mvfit_set_scan_term(mvfit_ctx* ctx, int enable, float w_s2m, float w_m2s, fl
  * the loss and gradient bits it has without any term; a problem's numbers do not depend on B, on its position in the batch
  * or on the other problems (beyond its scene's frozen obstacles).
  * mvfit_closure and mvfit_fit both honour the mix.  mvfit_fit runs the stages that carry it as chained rounds (pass ->
- * silhouette evaluation -> target kernel -> cotangent mix -> pull-back -> scene term -> record merge -> step kernel, every
+ * silhouette evaluation -> target kernel -> scan evaluation -> cotangent mix -> pull-back -> scene term -> record merge -> step kernel, every
  * kernel skipping finished problems); stages without it in front keep their single-launch phase.  MVFIT_F_SPARSE_VERTS is
  * ignored while the mix is on.
  * State.  While the mix is on, mvfit_set_silhouette_term(enable), mvfit_set_vertex_target_term(enable) and mvfit_set_sdf(faces)
- * return MVFIT_E_STATE.  Obstacles and targets may be re-frozen and the mask set replaced (same shapes: the captured round
- * graph is kept; other shapes, other shares or other silhouette scalars rebuild it).  Removing a data set whose share is > 0
- * switches the mix off, as does a replacing set that fails and mvfit_set_problems with another B.  Obstacles being set does
+ * and mvfit_set_scan_term(enable) return MVFIT_E_STATE.  Obstacles and targets may be re-frozen and the mask and scan sets
+ * replaced (same shapes: the captured round graph is kept; other shapes, other shares or other silhouette or scan scalars
+ * rebuild it).  Removing a data set whose share is > 0 switches the mix off, as does a replacing set that fails, a scan set
+ * with num_bodies != B (MVFIT_E_ARG) and mvfit_set_problems with another B.  A mix with scan = 0 is untouched by any scan
+ * call; mvfit_scan_loss stays available and returns its own bits between rounds.  Obstacles being set does
  * not by itself make the scene term run under the mix: only scene > 0 does.  With the mix off every other entry behaves as
  * it does without this one.  The round's buffers (those of the live single terms, 12 B Nv bytes of mixed cotangent, the
  * pull-back partials and two records per problem) are allocated by the first enable and keep their addresses while B stays.
  * mvfit_sdf_term_read: sums returns sum_k share_k * part_k per problem (float64, rounded once; penalty = w^2 * sums);
  * samples: MVFIT_E_UNSUPPORTED.
- * MVFIT_E_ARG: size < sizeof(mvfit_term_mix), a negative or non-finite share, fewer than two shares > 0, bad silhouette
- * scalars (as mvfit_set_silhouette_term), a mask set whose image_body lies outside [0, B).  MVFIT_E_STATE: without
- * mvfit_set_problems, while mvfit_set_sdf's term or a single term's own setter is on, or when a share > 0 has no data set. */
+ * MVFIT_E_ARG: size neither MVFIT_TERM_MIX_SIZE_V1 (the layout up to vertex_targets: the scan fields read as 0) nor
+ * sizeof(mvfit_term_mix), a negative or non-finite share, fewer than two shares > 0, bad silhouette scalars (as
+ * mvfit_set_silhouette_term) or scan scalars (as mvfit_set_scan_term), a mask set whose image_body lies outside [0, B), a
+ * scan set whose num_bodies differs from B.  MVFIT_E_STATE: without mvfit_set_problems, while mvfit_set_sdf's term or a
+ * single term's own setter is on, or when a share > 0 has no data set.  A refused call leaves the state as it was. */
+#define MVFIT_TERM_MIX_SIZE_V1 28u
 typedef struct mvfit_term_mix {
-    uint32_t size;                 /* sizeof(mvfit_term_mix) of the caller */
+    uint32_t size;                 /* sizeof(mvfit_term_mix) of the caller, or MVFIT_TERM_MIX_SIZE_V1 */
     float scene;                   /* share >= 0; > 0 needs obstacles (mvfit_set_scene_obstacles) */
     float silhouette;              /* share >= 0; > 0 needs a mask set (mvfit_set_silhouettes) */
     float sil_w_in, sil_w_out, sil_sigma;
     float vertex_targets;          /* share >= 0; > 0 needs a target set (mvfit_set_vertex_targets) */
+    float scan;                    /* share >= 0; > 0 needs a scan set of B bodies (mvfit_set_scans) */
+    float scan_w_s2m, scan_w_m2s, scan_sigma;
 } mvfit_term_mix;
 int mvfit_set_term_mix(mvfit_ctx* ctx, const mvfit_term_mix* mix /* NULL: off */);
 /* parts[B,3] dev out: S_sc^2 (the float64 square of the scene record's S, rounded once), L_sil, L_vt of the last evaluation,
  * unweighted; 0 for a share of 0.  MVFIT_E_STATE while the mix is off. */
 int mvfit_term_mix_read(mvfit_ctx* ctx, float* parts);
+/* parts[B,4] dev out: the same three and L_scan. */
+int mvfit_term_mix_read4(mvfit_ctx* ctx, float* parts);
 /* The mix's two kernels on the caller's device buffers, for checks against a restatement of the arithmetic above (B and Nv
  * are the ctx's; nothing of the ctx's state is read or changed).
  * mvfit_term_mix_cotangent: g[B,Nv,3] and L_v[B] from g_sil / g_vt [B,Nv,3] and L_sil / L_vt [B]; the buffers of a component
  * with share 0 are never read (NULL is fine).  Buffers at addresses that are no multiple of 8 take the 4-byte-load form of the
  * kernel: the same bits.  MVFIT_E_ARG: a negative or non-finite share, both 0, a null buffer of a live component.
+ * mvfit_term_mix_cotangent3: the same with the scan as third component, g_scan [B,Nv,3] and L_scan [B]; any of the three may
+ * be live, and with scan = 0 it returns the bits of mvfit_term_mix_cotangent.
  * mvfit_term_mix_merge: rec[B,R] from the records rec_scene / rec_verts [B,R], R = MVFIT_TERM_RECORD_FLOATS floats each: S,
  * then the adjoint entries.  MVFIT_E_ARG: scene not finite and > 0, a null buffer.  Both: MVFIT_E_STATE without
  * mvfit_set_problems. */
 #define MVFIT_TERM_RECORD_FLOATS 516
 int mvfit_term_mix_cotangent(mvfit_ctx* ctx, float silhouette, const float* g_sil, const float* L_sil, float vertex_targets,
                              const float* g_vt, const float* L_vt, float* g, float* L_v);
+int mvfit_term_mix_cotangent3(mvfit_ctx* ctx, float silhouette, const float* g_sil, const float* L_sil, float vertex_targets,
+                              const float* g_vt, const float* L_vt, float scan, const float* g_scan, const float* L_scan, float* g,
+                              float* L_v);
 int mvfit_term_mix_merge(mvfit_ctx* ctx, float scene, const float* rec_scene, const float* rec_verts, float* rec);
 
 /* Per-frame initial guess, stage 1 (code/utils/init_guess.py:80-83 -> code/utils/recompute3D.py:22-62): weighted linear

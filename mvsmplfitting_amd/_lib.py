@@ -67,9 +67,13 @@ class Options(C.Structure):
 
 
 class TermMix(C.Structure):
-    """mvfit_term_mix (include/mvfit.h): the shares of the scene, silhouette and vertex-target terms in one fit."""
+    """mvfit_term_mix (include/mvfit.h): the shares of the scene, silhouette, vertex-target and scan terms in one fit."""
     _fields_ = [('size', C.c_uint32), ('scene', C.c_float), ('silhouette', C.c_float), ('sil_w_in', C.c_float),
-                ('sil_w_out', C.c_float), ('sil_sigma', C.c_float), ('vertex_targets', C.c_float)]
+                ('sil_w_out', C.c_float), ('sil_sigma', C.c_float), ('vertex_targets', C.c_float), ('scan', C.c_float),
+                ('scan_w_s2m', C.c_float), ('scan_w_m2s', C.c_float), ('scan_sigma', C.c_float)]
+
+
+TERM_MIX_SIZE_V1 = 28         # MVFIT_TERM_MIX_SIZE_V1: the layout up to vertex_targets
 
 
 class CameraRefineOpts(C.Structure):
@@ -89,6 +93,7 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_set_silhouette_term', 'mvfit_set_silhouette_occluders', 'mvfit_silhouette_occluders_read',
            'mvfit_silhouette_hidden', 'mvfit_round_graph_info', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
            'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge',
+           'mvfit_term_mix_read4', 'mvfit_term_mix_cotangent3',
            'mvfit_camera_normal_eqs', 'mvfit_refine_cameras', 'mvfit_set_scans', 'mvfit_scan_loss', 'mvfit_set_scan_term']
 
 
@@ -205,6 +210,10 @@ def load(path=None):
     lib.mvfit_term_mix_read.restype = C.c_int
     lib.mvfit_term_mix_cotangent.argtypes = [vp, C.c_float, vp, vp, C.c_float, vp, vp, vp, vp]
     lib.mvfit_term_mix_cotangent.restype = C.c_int
+    lib.mvfit_term_mix_read4.argtypes = [vp, vp]
+    lib.mvfit_term_mix_read4.restype = C.c_int
+    lib.mvfit_term_mix_cotangent3.argtypes = [vp, C.c_float, vp, vp, C.c_float, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.mvfit_term_mix_cotangent3.restype = C.c_int
     lib.mvfit_term_mix_merge.argtypes = [vp, C.c_float, vp, vp, vp]
     lib.mvfit_term_mix_merge.restype = C.c_int
     lib.mvfit_full_pose.argtypes = [vp, vp, C.c_uint32, vp]

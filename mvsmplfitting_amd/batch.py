@@ -44,6 +44,8 @@ from .silhouette import refine_fit, refine_fit_occluded
 from .calibrate import camera_matrices, refine_rig
 from .joint_refine import refine_joint
 from .temporal import smooth_sequences
+from .scan import points_from_depth
+from .scan import refine_fit as scan_refine_fit
 
 
 # pose format -> the model kind whose joint tensor it maps (reference code/utils/utils.py:441-457 smpl_to_annotation)
@@ -267,17 +269,18 @@ def check_temporal(temporal, scene_collision=None, silhouettes=None):
 
 JOINT_PARTS = dict(scene_collision=dict(grid_size=32, robustifier=0.05, scale_factor=0.2),
                    silhouettes=dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31),
-                   temporal=dict())
+                   temporal=dict(),
+                   scans=dict(root=None, depth_root=None, w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1, mask_root=None))
 
 
-def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouettes=None, temporal=None):
+def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouettes=None, temporal=None, scans=None):
     """fit_folder's ``joint`` option with the defaults filled in, or ValueError."""
     if not isinstance(joint, dict) or 'weight' not in joint:
         raise ValueError("joint: a dict with at least 'weight' (the mixed term's coll_loss_weight) and two parts")
     unknown = set(joint) - {'weight', 'sweeps'} - set(JOINT_PARTS)
     if unknown:
         raise ValueError('joint: unknown keys %s' % sorted(unknown))
-    for name, single in (('scene_collision', scene_collision), ('silhouettes', silhouettes), ('temporal', temporal)):
+    for name, single in (('scene_collision', scene_collision), ('silhouettes', silhouettes), ('temporal', temporal), ('scans', scans)):
         if single is not None:
             raise ValueError('joint and %s: the joint refinement takes the place of the single ones - name its parts inside joint' % name)
     if is_seq:
@@ -289,7 +292,8 @@ def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouet
         raise ValueError('joint: sweeps must be >= 1')
     parts = [k for k in JOINT_PARTS if joint.get(k) is not None]
     if len(parts) < 2:
-        raise ValueError('joint: at least two of scene_collision, silhouettes and temporal must be given (a single part has an option of its own)')
+        raise ValueError('joint: at least two of scene_collision, silhouettes and temporal must be given (a single part has an option of its own); '
+                         'scans counts as a fourth')
     for k in parts:
         part = joint[k]
         if not isinstance(part, dict) or 'share' not in part:
@@ -306,6 +310,8 @@ def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouet
             raise ValueError('joint: scene_collision: grid_size must be >= 2, robustifier and scale_factor > 0')
         if k == 'silhouettes' and (int(c['downscale']) < 1 or int(c['contour_stride']) < 1):
             raise ValueError('joint: silhouettes: downscale and contour_stride must be >= 1')
+        if k == 'scans':
+            _check_scan_values('joint: scans', c, multi)
         cfg[k] = c
     if 'scene_collision' in cfg and not multi:
         raise ValueError('joint: scene_collision refines the persons of a frame together: it needs persons= a list of ids or \'all\'')
@@ -317,6 +323,152 @@ def mask_path(mask_root, serial, camera, frame, person=None):
     person ``id`` of the multi-person path."""
     name = frame + '.png' if person is None else '%s_%03d.png' % (frame, int(person))
     return os.path.join(mask_root, serial, camera, name)
+
+
+SCAN_DEFAULTS = dict(root=None, depth_root=None, w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1, mask_root=None)
+
+
+def _check_scan_values(who, cfg, multi):
+    """what the ``scans`` option and the ``scans`` part of ``joint`` share: one source, the scalars, the sizes"""
+    if (cfg['root'] is None) == (cfg['depth_root'] is None):
+        raise ValueError('%s: exactly one of root (point files) and depth_root (depth maps) must be given' % who)
+    vals = [float(cfg[k]) for k in ('w_s2m', 'w_m2s', 'sigma')]
+    if any(not np.isfinite(v) or v < 0.0 for v in vals):
+        raise ValueError('%s: w_s2m, w_m2s and sigma must be finite and >= 0' % who)
+    if not (vals[0] > 0.0 or vals[1] > 0.0):
+        raise ValueError('%s: w_s2m and w_m2s are both 0' % who)
+    if int(cfg['max_points']) < 1 or int(cfg['stride']) < 1:
+        raise ValueError('%s: max_points and stride must be >= 1' % who)
+    if cfg['depth_root'] is not None and multi and cfg['mask_root'] is None:
+        raise ValueError('%s: depth maps of more than one person need mask_root: without masks every person would get everyone\'s points'
+                         % who)
+    if cfg['root'] is not None and cfg['mask_root'] is not None:
+        raise ValueError('%s: mask_root selects the pixels of depth maps: it goes with depth_root' % who)
+
+
+def check_scans(scans, is_seq=False, multi=False, scene_collision=None, silhouettes=None, temporal=None, refine_cameras=None):
+    """fit_folder's ``scans`` option with the defaults filled in, or ValueError."""
+    if not isinstance(scans, dict) or 'weight' not in scans:
+        raise ValueError("scans: a dict with at least 'weight' (the term's coll_loss_weight, against metres squared) and one of "
+                         "'root' and 'depth_root'")
+    unknown = set(scans) - set(SCAN_DEFAULTS) - {'weight'}
+    if unknown:
+        raise ValueError('scans: unknown keys %s' % sorted(unknown))
+    if is_seq:
+        raise ValueError('scans is not available with is_seq=True')
+    if refine_cameras is not None:
+        raise ValueError('refine_cameras with scans is not built')
+    for name, single in (('scene_collision', scene_collision), ('silhouettes', silhouettes), ('temporal', temporal)):
+        if single is not None:
+            raise ValueError('scans and %s both use the fit\'s one term slot: choose one (they combine inside joint)' % name)
+    cfg = dict(SCAN_DEFAULTS, **scans)
+    if not float(cfg['weight']) > 0.0 or not np.isfinite(float(cfg['weight'])):
+        raise ValueError('scans: weight must be > 0')
+    _check_scan_values('scans', cfg, multi)
+    return cfg
+
+
+def scan_path(root, serial, frame, person=None, camera=None):
+    """The scan file of one frame.  Point files (camera None): `<root>/<serial>/<frame>.npy`, or `<frame>_<id:03d>.npy` for
+    person ``id`` of the multi-person path.  Depth maps: `<depth_root>/<serial>/<camera>/<frame>.npy`, one per view, shared by the
+    persons of the frame (their masks tell them apart)."""
+    if camera is not None:
+        return os.path.join(root, serial, camera, frame + '.npy')
+    name = frame + '.npy' if person is None else '%s_%03d.npy' % (frame, int(person))
+    return os.path.join(root, serial, name)
+
+
+def subsample_rows(P, max_points):
+    """The rows kept of P > max_points: floor(i * P / max_points), scan.points_from_depth's rule."""
+    return np.floor(np.arange(int(max_points)) * (P / float(max_points))).astype(np.int64)
+
+
+def load_serial_scans(cfg, serial, cams, frames, problems, rig):
+    """The scan set of one serial's problems for MvFit.set_scans: (points float32 [N,Pmax,3], count int32 [N], weights float32
+    [N,Pmax] or None, found = [(problem, path)]).
+
+    problems, cams, rig as for load_serial_masks.  ``root``: every problem's own file of world points [P,3], or [P,4] with a
+    weight >= 0 in the last column (io_formats.read_points).  ``depth_root``: the problem's points are scan.points_from_depth
+    over its views in rig order (a view without a depth file contributes nothing), with ``stride``, masked by the person's
+    mask file where ``mask_root`` is given and the file exists.  A problem without a file gets count 0 and pays nothing; more
+    than max_points points keep the rows subsample_rows names; Pmax is the serial's largest count (at least 1).  ValueError: no
+    file at all in the serial, a file of another shape or dtype, a negative or non-finite weight, a depth map or mask whose
+    size differs from the others of its problem."""
+    cap = int(cfg['max_points'])
+    per, wts, found = [], [], []
+    if cfg['root'] is not None:
+        for n, (f, person) in enumerate(problems):
+            path = scan_path(cfg['root'], serial, frames[f][0], person)
+            if not os.path.isfile(path):
+                per.append(np.zeros((0, 3), np.float32))
+                wts.append(None)
+                continue
+            pts, w = iof.read_points(path)
+            if len(pts) > cap:
+                keep = subsample_rows(len(pts), cap)
+                pts, w = pts[keep], (None if w is None else w[keep])
+            per.append(pts)
+            wts.append(w)
+            found.append((n, path))
+        example = scan_path(cfg['root'], serial, frames[problems[0][0]][0], problems[0][1])
+        where = cfg['root']
+    else:
+        R, t, f_, c = (np.asarray(a, np.float32) for a in rig)
+        for n, (f, person) in enumerate(problems):
+            views, depth, masks = [], [], []
+            for v, cam in enumerate(cams):
+                path = scan_path(cfg['depth_root'], serial, frames[f][0], camera=cam)
+                if not os.path.isfile(path):
+                    continue
+                d = iof.read_depth(path)
+                if depth and d.shape != depth[0].shape:
+                    raise ValueError('scans: the depth maps of serial %s frame %s differ in size: %s is %s, another %s'
+                                     % (serial, frames[f][0], path, d.shape, depth[0].shape))
+                m = np.ones(d.shape, np.uint8)
+                if cfg['mask_root'] is not None:
+                    mp = mask_path(cfg['mask_root'], serial, cam, frames[f][0], person)
+                    if os.path.isfile(mp):
+                        m = iof.read_mask(mp)
+                        if m.shape != d.shape:
+                            raise ValueError('scans: mask %s is %s, its depth map %s is %s' % (mp, m.shape, path, d.shape))
+                views.append(v)
+                depth.append(d)
+                masks.append(m)
+                found.append((n, path))
+            if not views:
+                per.append(np.zeros((0, 3), np.float32))
+            else:
+                vv = np.array(views)
+                per.append(points_from_depth(np.stack(depth), (R[vv], t[vv], f_[vv], c[vv]), mask=np.stack(masks),
+                                             stride=int(cfg['stride']), max_points=cap))
+            wts.append(None)
+        example = scan_path(cfg['depth_root'], serial, frames[problems[0][0]][0], camera=cams[0])
+        where = cfg['depth_root']
+    if not found:
+        raise ValueError('scans: serial %s has no scan file under %s (looked for e.g. %s)' % (serial, where, example))
+    count = np.array([len(p) for p in per], np.int32)
+    Pmax = max(int(count.max()), 1)
+    points = np.zeros((len(per), Pmax, 3), np.float32)
+    weights = np.ones((len(per), Pmax), np.float32) if any(w is not None for w in wts) else None
+    for n, p in enumerate(per):
+        points[n, :len(p)] = p
+        if wts[n] is not None:
+            weights[n, :len(p)] = wts[n]
+    return points, count, weights, found
+
+
+def refine_serial_scans(eng, xf, stage, cfg, serial, cams, frames, problems, rig):
+    """The scan refinement of one serial's fitted problems (scan.refine_fit: the scan term inside the engine's fit) against the
+    scan set of load_serial_scans, with coll_loss_weight = cfg['weight'].  Returns (params, report): refine_fit's report plus
+    points = the count per problem; the engine is left without scan set and term."""
+    points, count, weights, _ = load_serial_scans(cfg, serial, cams, frames, problems, rig)
+    eng.set_scans(points, count=count, weights=weights)
+    try:
+        out, report = scan_refine_fit(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), w_s2m=float(cfg['w_s2m']),
+                                      w_m2s=float(cfg['w_m2s']), sigma=float(cfg['sigma']))
+    finally:
+        eng.clear_scans()
+    return out, dict(report, points=count.copy())
 
 
 def silhouette_workspace_bytes(M, H, W, Nv):
@@ -394,7 +546,7 @@ def refine_serial_joint(eng, xf, stage, cfg, serial, cams, frames, problems, rig
     """The joint refinement of one serial's fitted problems (joint_refine.refine_joint: the term mix inside the engine's fit)
     with the parts of ``cfg`` (check_joint).  problems, cams, rig as for load_serial_masks; scene_sizes: problems per frame
     (frame-major rows); seq_id / frame_idx: every problem's track and its position in the serial's frame list.  Returns
-    (params, report); the engine is left without mask set, mix, targets and obstacles."""
+    (params, report); the engine is left without mask set, scan set, mix, targets and obstacles."""
     shares, kw = {}, {}
     sil = cfg.get('silhouettes')
     if 'scene_collision' in cfg:
@@ -411,21 +563,31 @@ def refine_serial_joint(eng, xf, stage, cfg, serial, cams, frames, problems, rig
         kw.update(w_in=float(sil['w_in']), w_out=float(sil['w_out']), sigma=float(sil['sigma']))
         masks, body, per_image, found = load_serial_masks(sil, serial, cams, frames, problems, rig, num_verts)
         eng.set_silhouettes(masks, body, per_image, contour_stride=int(sil['contour_stride']))
+    scn, count = cfg.get('scans'), None
     try:
+        if scn is not None:
+            shares['scan'] = float(scn['share'])
+            kw.update(scan_w_s2m=float(scn['w_s2m']), scan_w_m2s=float(scn['w_m2s']), scan_sigma=float(scn['sigma']))
+            points, count, weights, _ = load_serial_scans(scn, serial, cams, frames, problems, rig)
+            eng.set_scans(points, count=count, weights=weights)
         out, report = refine_joint(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), shares=shares,
                                    sweeps=int(cfg['sweeps']), **kw)
     finally:
+        if scn is not None:
+            eng.clear_scans()
         if sil is not None:
             eng.clear_silhouettes()
     if found is not None:
         report = dict(report, images=[(int(n), int(v)) for n, v, _ in found], mask_size=tuple(masks.shape[1:]))
+    if count is not None:
+        report = dict(report, points=count.copy())
     return out, report
 
 
 CAMERA_REFINE_DEFAULTS = dict(sweeps=2, anchor=0, free='extrinsics', min_points=34)
 
 
-def check_refine_cameras(cfg, is_seq=False, use_3d=False, scene_collision=None, silhouettes=None, temporal=None, joint=None):
+def check_refine_cameras(cfg, is_seq=False, use_3d=False, scene_collision=None, silhouettes=None, temporal=None, joint=None, scans=None):
     """The refine_cameras option of fit_folder -> its dict with the defaults filled in; ValueError for what is not built."""
     if not isinstance(cfg, dict):
         raise ValueError('refine_cameras: a dict with any of the keys %s' % sorted(CAMERA_REFINE_DEFAULTS))
@@ -433,7 +595,8 @@ def check_refine_cameras(cfg, is_seq=False, use_3d=False, scene_collision=None, 
     if unknown:
         raise ValueError('refine_cameras: unknown keys %s' % sorted(unknown))
     for name, on in (('is_seq', is_seq), ('use_3d', use_3d), ('scene_collision', scene_collision is not None),
-                     ('silhouettes', silhouettes is not None), ('temporal', temporal is not None), ('joint', joint is not None)):
+                     ('silhouettes', silhouettes is not None), ('temporal', temporal is not None), ('joint', joint is not None),
+                     ('scans', scans is not None)):
         if on:
             raise ValueError('refine_cameras with %s is not built' % name)
     out = dict(CAMERA_REFINE_DEFAULTS, **cfg)
@@ -461,7 +624,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
                save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
-               silhouettes=None, temporal=None, joint=None, refine_cameras=None):
+               silhouettes=None, temporal=None, joint=None, refine_cameras=None, scans=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -532,6 +695,22 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     part), ``timing`` a 'joint' entry, and ``final_loss`` is the report's loss.  ValueError together with any of the three
     single options, with is_seq=True, for a scene part without persons=, fewer than two parts, unknown keys and non-positive
     numbers.
+    scans: None, or dict(weight=..., root=... | depth_root=..., w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1,
+    mask_root=None) - after the serial's batched keypoint fit its problems are refined against depth data by scan.refine_fit
+    (the scan term inside the engine's fit) with the last stage's weights plus coll_loss_weight = weight (against metres
+    squared); a problem keeps the refined row only if its objective fell.  Exactly one source: ``root`` holds world points,
+    `<root>/<serial>/<frame>.npy` for persons=0 and `<frame>_<id:03d>.npy` on the multi-person path, float [P,3] in metres, or
+    [P,4] with a weight >= 0 in the last column; ``depth_root`` holds camera-space z in metres at the camera file's
+    resolution, `<depth_root>/<serial>/<camera>/<frame>.npy` float [H,W], unprojected by scan.points_from_depth over the
+    problem's views in rig order with ``stride`` and masked by `mask_path(mask_root, ...)` where mask_root is given and the
+    file exists (required with more than one person).  A problem without a file has no points and pays nothing; a serial with no
+    file at all is a ValueError that names an example path, and so are files of another shape or dtype and negative or
+    non-finite weights.  More than max_points points per problem keep rows floor(i * P / max_points).  `.npy` only: depth PNGs
+    and `.ply` files are not built.  ValueError before any engine is created with is_seq, with refine_cameras and next to a
+    single scene_collision, silhouettes or temporal (they combine inside ``joint``).  The serial's result gains ``scan_report``
+    (refine_fit's, plus points = the count per problem), ``timing`` a 'scan' entry, and ``final_loss`` is the refined
+    objective.  Inside ``joint``, ``scans=dict(share=..., root= | depth_root=, ...)`` with the same keys is a fourth part: at
+    least two of the four.
     refine_cameras: None, or dict(sweeps=2, anchor=0, free='extrinsics', min_points=34) - after the serial's batched fit the
     rig is refined against the fitted bodies of the serial's whole batch and the bodies are refitted under it, with the last
     stage (calibrate.refine_rig; anchor: the view kept as the camera file gives it, or None).  Single-person and persons=
@@ -573,8 +752,10 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
     sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision, multi) if silhouettes is not None else None
     tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
-    joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal) if joint is not None else None
-    cam_cfg = (check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint)
+    scan_cfg = (check_scans(scans, is_seq, multi, scene_collision, silhouettes, temporal, refine_cameras)
+                if scans is not None else None)
+    joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal, scans) if joint is not None else None
+    cam_cfg = (check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint, scans)
                if refine_cameras is not None else None)
     if associate is not None and associate is not False:
         if not multi:
@@ -763,6 +944,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             xf = xr.to(xf.dtype)
             final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
             _t = _tick('silhouette', _t)
+        scan_report = None
+        if scan_cfg is not None:
+            xr, scan_report = refine_serial_scans(eng, xf, stages_for(bool(has.all()))[-1], scan_cfg, serial, cams, frames,
+                                                  [(int(f), int(p)) for f, p in prob], rig)
+            xf = xr.to(xf.dtype)
+            final = torch.as_tensor(scan_report['loss'], dtype=final.dtype, device=final.device)
+            _t = _tick('scan', _t)
         temporal_report = None
         if tmp_cfg is not None:
             # a person's track: frame_idx = position in the serial's frame list, so an absence breaks the chain
@@ -813,6 +1001,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
             out['scene_report'] = scene_report
         if silhouette_report is not None:
             out['silhouette_report'] = silhouette_report
+        if scan_report is not None:
+            out['scan_report'] = scan_report
         if temporal_report is not None:
             out['temporal_report'] = temporal_report
         if joint_report is not None:
@@ -923,6 +1113,13 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                 xf = xr.to(xf.dtype)
                 final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
                 _t = _tick('silhouette', _t)
+            scan_report = None
+            if scan_cfg is not None:
+                xr, scan_report = refine_serial_scans(eng, xf, stages_for(bool(has.all()))[-1], scan_cfg, serial, cams, frames,
+                                                      [(f, None) for f in range(F)], rig)
+                xf = xr.to(xf.dtype)
+                final = torch.as_tensor(scan_report['loss'], dtype=final.dtype, device=final.device)
+                _t = _tick('scan', _t)
             temporal_report = None
             if tmp_cfg is not None:
                 if has.all():
@@ -972,6 +1169,8 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                                    used_3d=has.copy(), views_per_frame=vmask.sum(1))
             if silhouette_report is not None:
                 results[serial]['silhouette_report'] = silhouette_report
+            if scan_report is not None:
+                results[serial]['scan_report'] = scan_report
             if temporal_report is not None:
                 results[serial]['temporal_report'] = temporal_report
             if joint_report is not None:
@@ -993,4 +1192,5 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
 
 __all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
            'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes',
-           'check_joint', 'load_serial_masks', 'refine_serial_joint', 'check_refine_cameras', 'refine_serial_cameras']
+           'check_joint', 'load_serial_masks', 'refine_serial_joint', 'check_refine_cameras', 'refine_serial_cameras',
+           'check_scans', 'scan_path', 'subsample_rows', 'load_serial_scans', 'refine_serial_scans']

@@ -119,6 +119,7 @@ TermInputs mvfit::term_inputs(const mvfit_ctx* c) {
     in.mix.w_in = X.w_in; in.mix.w_out = X.w_out; in.mix.sigma = X.sigma;
     in.mix.g_verts = X.g_verts; in.mix.loss = X.loss; in.mix.part = X.part; in.mix.rec_scene = X.rec_scene; in.mix.rec_verts = X.rec_verts;
     in.mix.parts = X.parts; in.mix.sums = X.sums;
+    in.mix.scan = X.scan; in.mix.scan_w_s2m = X.scan_w_s2m; in.mix.scan_w_m2s = X.scan_w_m2s; in.mix.scan_sigma = X.scan_sigma;
     const ScanState& Z = c->scan;
     const ScanTerm& zt = c->scant;
     in.scan.on = Z.on; in.scan.term = zt.on; in.scan.ws = Z.ws.get(); in.scan.N = Z.N; in.scan.Pmax = Z.Pmax; in.scan.nf = Z.nf; in.scan.ns = Z.ns;
@@ -471,8 +472,8 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
             e = launch_vertex_target(verts, nv, B, s.vt.K, s.vt.targets, s.vt.weights, gate, s.vt.partial, s.vt.loss, s.vt.g_verts, st);
             break;
         case STEP_MIX_COTANGENT:
-            e = launch_term_mix_cotangent(nv, B, s.cot.lam_sil, s.cot.g_sil, s.cot.L_sil, s.cot.lam_vt, s.cot.g_vt, s.cot.L_vt, gate, s.cot.g,
-                                          s.cot.L_v, s.cot.parts, s.cot.sums, st);
+            e = launch_term_mix_cotangent(nv, B, s.cot.lam_sil, s.cot.g_sil, s.cot.L_sil, s.cot.lam_vt, s.cot.g_vt, s.cot.L_vt, s.cot.lam_scan,
+                                          s.cot.g_scan, s.cot.L_scan, gate, s.cot.g, s.cot.L_v, s.cot.parts, s.cot.sums, st);
             break;
         case STEP_SCAN_EVAL:
             if (scan_round(scan, s.scan.faces, verts, s.scan.w_s2m, s.scan.w_m2s, s.scan.sigma, gate, s.scan.loss, s.scan.g_verts, st, err))
@@ -486,8 +487,8 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
                                   s.scene.null_box, s.scene.entries, s.scene.rec, st);
             break;
         case STEP_MIX_RECORD:
-            e = launch_term_mix_record(B, s.rec.lam_sc, s.rec.rec_scene, s.rec.rec_verts, s.rec.lam_sil, s.rec.L_sil, s.rec.lam_vt, s.rec.L_vt, gate,
-                                       s.rec.rec, s.rec.parts, s.rec.sums, st);
+            e = launch_term_mix_record(B, s.rec.lam_sc, s.rec.rec_scene, s.rec.rec_verts, s.rec.lam_sil, s.rec.L_sil, s.rec.lam_vt, s.rec.L_vt,
+                                       s.rec.lam_scan, s.rec.L_scan, gate, s.rec.rec, s.rec.parts, s.rec.sums, st);
             break;
         case STEP_SDF:
             e = launch_sdf_term(M, P, verts, B, B, s.sdf.faces, s.sdf.num_faces, s.sdf.grid, gate, s.sdf.box, static_cast<float4*>(s.sdf.samp),

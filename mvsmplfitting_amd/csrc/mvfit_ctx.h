@@ -109,7 +109,7 @@ struct mvfit_ctx {
     ScanTerm scant;
     // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
     VtxTargets vt;
-    // the weighted sum of the scene, silhouette and vertex-target terms (mvfit_set_term_mix, term_mix.hip)
+    // the weighted sum of the scene, silhouette, vertex-target and scan terms (mvfit_set_term_mix, term_mix.hip)
     TermMix mix;
     // ---- model ----
     DevModel M{};
@@ -216,20 +216,20 @@ void free_obstacles(mvfit_ctx* c);
 void free_vertex_targets(mvfit_ctx* c);
 void free_term_mix(mvfit_ctx* c);
 void free_scan_term(mvfit_ctx* c);
+int ensure_scan_round(mvfit_ctx* c);        // mvfit_scan.hip: the scan term's round buffers, for its own setter and for the mix
 inline const char* term_name(const mvfit_ctx* c) { return term_kind_name(term_slot(term_inputs(c))); }
 // a term other than mvfit_set_sdf's is configured: it runs in chained rounds only and keeps no per-vertex samples
 inline bool round_term(const mvfit_ctx* c) { return term_slot(term_inputs(c)) != TERM_SDF; }
 
 // A data set a term reads went away (or is about to be re-made): its own term goes off, and so does a mix that gives it a share.
-// The scan set has no share in the mix: SRC_SCANS stands behind the sources that have one.
 enum TermSource { SRC_OBSTACLES = 0, SRC_MASKS, SRC_TARGETS, SRC_SCANS };
 inline bool& term_flag(mvfit_ctx* c, TermSource src) {
     return src == SRC_OBSTACLES ? c->obst.on : src == SRC_MASKS ? c->silt.on : src == SRC_TARGETS ? c->vt.term : c->scant.on;
 }
 inline void term_source_gone(mvfit_ctx* c, TermSource src) {
-    const float share[] = {c->mix.scene, c->mix.silhouette, c->mix.vertex_targets};
+    const float share[] = {c->mix.scene, c->mix.silhouette, c->mix.vertex_targets, c->mix.scan};
     term_flag(c, src) = false;
-    if (src < SRC_SCANS && share[src] > 0.f) c->mix.on = false;
+    if (share[src] > 0.f) c->mix.on = false;
 }
 // the same around a re-make that can fail: a failure leaves no term behind, restore() after success brings both flags back
 struct TermSuspend {

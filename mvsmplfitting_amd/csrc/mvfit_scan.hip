@@ -11,7 +11,7 @@ extern "C" int mvfit_set_scans(mvfit_ctx* c, int num_bodies, int max_points, con
         HIP_OK(c, hipStreamSynchronize(c->stream));
         c->scan.on = false;
         c->scan.ws.reset();
-        term_source_gone(c, SRC_SCANS);          // no scans: no term
+        term_source_gone(c, SRC_SCANS);          // no scans: no term and no mix that uses them
         return MVFIT_OK;
     }
     if (!c->num_faces) return fail(c, MVFIT_E_STATE, "mvfit_set_scans: the model was created without (valid) faces");
@@ -32,8 +32,13 @@ extern "C" int mvfit_set_scans(mvfit_ctx* c, int num_bodies, int max_points, con
     const int rc = scan_set(c->scan, c->nv, c->num_faces, num_bodies, max_points, points, count, weights, c->stream, c->err);
     // a set that replaces the one of an enabled term must fit the batch like the first (scan body n is problem n); a failed
     // or unfit set leaves no term behind.  A set of the same sizes keeps every address, and with it the captured round graph.
-    if (c->scant.on && (rc || num_bodies != c->B)) {
+    // The same holds for a mix that gives the scan a share.
+    const bool in_mix = c->mix.on && c->mix.scan > 0.f;
+    if ((c->scant.on || in_mix) && (rc || num_bodies != c->B)) {
         term_source_gone(c, SRC_SCANS);
+        if (!rc && in_mix)
+            return fail(c, MVFIT_E_ARG, "mvfit_set_scans: the set holds %d bodies, the ctx of the enabled term mix %d problems (the mix is "
+                        "switched off)", num_bodies, c->B);
         if (!rc)
             return fail(c, MVFIT_E_ARG, "mvfit_set_scans: the set holds %d bodies, the enabled scan term's ctx %d problems (the term is "
                         "switched off)", num_bodies, c->B);
@@ -42,8 +47,8 @@ extern "C" int mvfit_set_scans(mvfit_ctx* c, int num_bodies, int max_points, con
 }
 
 // the round buffers of the scan term (cotangent, loss, pull-back partials) for the current batch: allocated by the first
-// enable and kept while B stays
-static int ensure_scan_round(mvfit_ctx* c) {
+// enable - the term's own setter or the term mix - and kept while B stays
+int mvfit::ensure_scan_round(mvfit_ctx* c) {
     if (c->scant.part) return MVFIT_OK;
     HIP_OK(c, hipStreamSynchronize(c->stream));
     free_scan_term(c);                                       // (what an earlier call that failed half-way left)

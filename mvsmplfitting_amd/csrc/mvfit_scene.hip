@@ -451,7 +451,7 @@ extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
     return MVFIT_OK;
 }
 
-// The weighted sum of the scene, silhouette and vertex-target terms inside mvfit_fit / mvfit_closure (include/mvfit.h): state
+// The weighted sum of the scene, silhouette, vertex-target and scan terms inside mvfit_fit / mvfit_closure (include/mvfit.h): state
 // and buffers only - the rounds launch it (round_term.cpp plans the launches).
 extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
     if (!c) return MVFIT_E_ARG;
@@ -460,12 +460,17 @@ extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
         c->mix.on = false;
         return MVFIT_OK;
     }
-    if (mix->size < sizeof(mvfit_term_mix)) return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: size %u < %zu", mix->size, sizeof(mvfit_term_mix));
-    const float lam[3] = {mix->scene, mix->silhouette, mix->vertex_targets};
+    // exactly the layout before the scan share (its fields read as 0) or exactly this one
+    if (mix->size != MVFIT_TERM_MIX_SIZE_V1 && mix->size != sizeof(mvfit_term_mix))
+        return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: size %u is neither %u nor %zu", mix->size, (unsigned)MVFIT_TERM_MIX_SIZE_V1, sizeof(mvfit_term_mix));
+    const bool v1 = mix->size == MVFIT_TERM_MIX_SIZE_V1;
+    const float lam[4] = {mix->scene, mix->silhouette, mix->vertex_targets, v1 ? 0.f : mix->scan};
+    const float zw_s2m = v1 ? 0.f : mix->scan_w_s2m, zw_m2s = v1 ? 0.f : mix->scan_w_m2s, zsigma = v1 ? 0.f : mix->scan_sigma;
     int live = 0;
     for (float l : lam) {
         if (!std::isfinite(l) || l < 0.f)
-            return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: the shares (%g, %g, %g) must be finite and >= 0", (double)lam[0], (double)lam[1], (double)lam[2]);
+            return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: the shares (%g, %g, %g, %g) must be finite and >= 0", (double)lam[0], (double)lam[1],
+                        (double)lam[2], (double)lam[3]);
         live += l > 0.f;
     }
     if (live < 2)
@@ -474,6 +479,12 @@ extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
                          mix->sil_w_in < 0.f || mix->sil_w_out < 0.f))
         return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: sil_w_in = %g and sil_w_out = %g must be finite and >= 0, sil_sigma = %g finite",
                     (double)mix->sil_w_in, (double)mix->sil_w_out, (double)mix->sil_sigma);
+    if (lam[3] > 0.f) {                                      // (as mvfit_set_scan_term checks them)
+        if (!std::isfinite(zw_s2m) || !std::isfinite(zw_m2s) || !std::isfinite(zsigma) || zw_s2m < 0.f || zw_m2s < 0.f || zsigma < 0.f)
+            return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: scan_w_s2m = %g, scan_w_m2s = %g and scan_sigma = %g must be finite and >= 0",
+                        (double)zw_s2m, (double)zw_m2s, (double)zsigma);
+        if (!(zw_s2m > 0.f) && !(zw_m2s > 0.f)) return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: scan_w_s2m and scan_w_m2s are both 0");
+    }
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (c->sdf_num_faces)
         return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: mvfit_set_sdf's term uses the ctx's term slot and is not part of the mix: remove it first");
@@ -484,6 +495,9 @@ extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
     if (lam[2] > 0.f && !c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: vertex_targets > 0 needs a target set (mvfit_set_vertex_targets)");
     if (lam[1] > 0.f && (c->sil.body_min < 0 || c->sil.body_max >= c->B))
         return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: image_body holds %d .. %d, outside [0, %d)", c->sil.body_min, c->sil.body_max, c->B);
+    if (lam[3] > 0.f && !c->scan.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: scan > 0 needs a scan set (mvfit_set_scans)");
+    if (lam[3] > 0.f && c->scan.N != c->B)
+        return fail(c, MVFIT_E_ARG, "mvfit_set_term_mix: the scan set holds %d bodies, the ctx %d problems (scan body n is problem n)", c->scan.N, c->B);
     TermMix& X = c->mix;
     if (!X.sums) {
         HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -493,15 +507,17 @@ extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
         HIP_OK(c, c->mix_mem.alloc(&X.part, vjp_part_bytes(c->Bpad, c->nv)));
         HIP_OK(c, c->mix_mem.alloc(&X.rec_scene, (size_t)c->B * sizeof(SdfAdj), true));
         HIP_OK(c, c->mix_mem.alloc(&X.rec_verts, (size_t)c->B * sizeof(SdfAdj), true));
-        HIP_OK(c, c->mix_mem.alloc(&X.parts, (size_t)c->B * 3 * sizeof(float), true));
+        HIP_OK(c, c->mix_mem.alloc(&X.parts, (size_t)c->B * 4 * sizeof(float), true));
         HIP_OK(c, c->mix_mem.alloc(&X.sums, (size_t)c->B * sizeof(float), true));      // last: a mix with sums is complete
     }
     X.on = false;                                            // (a failed allocation below leaves no mix behind)
     if (lam[1] > 0.f) { if (const int rc = ensure_sil_round(c)) return rc; }
     if (lam[2] > 0.f) { if (const int rc = ensure_vt_round(c)) return rc; }
+    if (lam[3] > 0.f) { if (const int rc = ensure_scan_round(c)) return rc; }
     if (const int rc = ensure_sdf_buffers(c)) return rc;     // the record slot (SdfAdj) per problem
-    X.scene = lam[0]; X.silhouette = lam[1]; X.vertex_targets = lam[2];
+    X.scene = lam[0]; X.silhouette = lam[1]; X.vertex_targets = lam[2]; X.scan = lam[3];
     X.w_in = mix->sil_w_in; X.w_out = mix->sil_w_out; X.sigma = mix->sil_sigma;
+    X.scan_w_s2m = zw_s2m; X.scan_w_m2s = zw_m2s; X.scan_sigma = zsigma;
     X.on = true;
     return MVFIT_OK;
 }
@@ -518,8 +534,27 @@ extern "C" int mvfit_term_mix_cotangent(mvfit_ctx* c, float silhouette, const fl
     if (!g || !L_v || (sil && (!g_sil || !L_sil)) || (vt && (!g_vt || !L_vt)))
         return fail(c, MVFIT_E_ARG, "mvfit_term_mix_cotangent: null buffer of a live component or of the result");
     HIP_OK(c, hipSetDevice(c->device));
-    const hipError_t e = launch_term_mix_cotangent(c->nv, c->B, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt, nullptr, g, L_v,
-                                                   nullptr, nullptr, c->stream);
+    const hipError_t e = launch_term_mix_cotangent(c->nv, c->B, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt, 0.f, nullptr, nullptr,
+                                                   nullptr, g, L_v, nullptr, nullptr, c->stream);
+    if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "term-mix cotangent launch: %s", hipGetErrorString(e));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_term_mix_cotangent3(mvfit_ctx* c, float silhouette, const float* g_sil, const float* L_sil, float vertex_targets,
+                                         const float* g_vt, const float* L_vt, float scan, const float* g_scan, const float* L_scan,
+                                         float* g, float* L_v) {
+    if (!c) return MVFIT_E_ARG;
+    if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
+    const bool sil = silhouette > 0.f, vt = vertex_targets > 0.f, sn = scan > 0.f;
+    if (!std::isfinite(silhouette) || !std::isfinite(vertex_targets) || !std::isfinite(scan) || silhouette < 0.f || vertex_targets < 0.f ||
+        scan < 0.f || (!sil && !vt && !sn))
+        return fail(c, MVFIT_E_ARG, "mvfit_term_mix_cotangent3: the shares (%g, %g, %g) must be finite and >= 0, one of them > 0",
+                    (double)silhouette, (double)vertex_targets, (double)scan);
+    if (!g || !L_v || (sil && (!g_sil || !L_sil)) || (vt && (!g_vt || !L_vt)) || (sn && (!g_scan || !L_scan)))
+        return fail(c, MVFIT_E_ARG, "mvfit_term_mix_cotangent3: null buffer of a live component or of the result");
+    HIP_OK(c, hipSetDevice(c->device));
+    const hipError_t e = launch_term_mix_cotangent(c->nv, c->B, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt, scan, g_scan, L_scan,
+                                                   nullptr, g, L_v, nullptr, nullptr, c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "term-mix cotangent launch: %s", hipGetErrorString(e));
     return MVFIT_OK;
 }
@@ -534,7 +569,8 @@ extern "C" int mvfit_term_mix_merge(mvfit_ctx* c, float scene, const float* rec_
         return fail(c, MVFIT_E_ARG, "mvfit_term_mix_merge: record buffers must be 4-byte aligned");
     HIP_OK(c, hipSetDevice(c->device));
     const hipError_t e = launch_term_mix_record(c->B, scene, reinterpret_cast<const SdfAdj*>(rec_scene), reinterpret_cast<const SdfAdj*>(rec_verts),
-                                                0.f, nullptr, 0.f, nullptr, nullptr, reinterpret_cast<SdfAdj*>(rec), nullptr, nullptr, c->stream);
+                                                0.f, nullptr, 0.f, nullptr, 0.f, nullptr, nullptr, reinterpret_cast<SdfAdj*>(rec), nullptr, nullptr,
+                                                c->stream);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "term-mix record launch: %s", hipGetErrorString(e));
     return MVFIT_OK;
 }
@@ -544,7 +580,18 @@ extern "C" int mvfit_term_mix_read(mvfit_ctx* c, float* parts) {
     if (!parts) return fail(c, MVFIT_E_ARG, "mvfit_term_mix_read: null parts");
     if (!c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_term_mix_read: the term mix is off (mvfit_set_term_mix)");
     HIP_OK(c, hipSetDevice(c->device));
-    HIP_OK(c, hipMemcpyAsync(parts, c->mix.parts, (size_t)c->B * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    // the first three of a problem's four parts
+    HIP_OK(c, hipMemcpy2DAsync(parts, 3 * sizeof(float), c->mix.parts, 4 * sizeof(float), 3 * sizeof(float), (size_t)c->B, hipMemcpyDeviceToDevice,
+                               c->stream));
+    return MVFIT_OK;
+}
+
+extern "C" int mvfit_term_mix_read4(mvfit_ctx* c, float* parts) {
+    if (!c) return MVFIT_E_ARG;
+    if (!parts) return fail(c, MVFIT_E_ARG, "mvfit_term_mix_read4: null parts");
+    if (!c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_term_mix_read4: the term mix is off (mvfit_set_term_mix)");
+    HIP_OK(c, hipSetDevice(c->device));
+    HIP_OK(c, hipMemcpyAsync(parts, c->mix.parts, (size_t)c->B * 4 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return MVFIT_OK;
 }
 

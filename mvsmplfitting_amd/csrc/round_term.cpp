@@ -43,11 +43,12 @@ struct Builder {
         s.K = in.vt.K; s.targets = in.vt.targets; s.weights = in.vt.weights; s.partial = in.vt.partial;
         s.loss = in.vt.loss; s.g_verts = in.vt.g_verts;
     }
-    void scan_eval() {
+    // the evaluation writes the scan term's round buffers, whoever asks for it
+    void scan_eval(float w_s2m, float w_m2s, float sigma) {
         ScanEvalStep& s = add(STEP_SCAN_EVAL).scan;
         s.ws = in.scan.ws; s.faces = in.scan.faces;
         s.N = in.scan.N; s.Pmax = in.scan.Pmax; s.nf = in.scan.nf; s.ns = in.scan.ns;
-        s.w_s2m = in.scan.w_s2m; s.w_m2s = in.scan.w_m2s; s.sigma = in.scan.sigma;
+        s.w_s2m = w_s2m; s.w_m2s = w_m2s; s.sigma = sigma;
         s.loss = in.scan.loss; s.g_verts = in.scan.g_verts;
     }
     void pullback(const float* g_verts, const float* loss, float* part, SdfAdj* rec) {
@@ -65,18 +66,21 @@ struct Builder {
     // term into a record of its own and the merge of the two records
     void mix() {
         const auto& X = in.mix;
-        const bool sil = X.silhouette > 0.f, vt = X.vertex_targets > 0.f, sc = X.scene > 0.f;
+        const bool sil = X.silhouette > 0.f, vt = X.vertex_targets > 0.f, scan = X.scan > 0.f, sc = X.scene > 0.f;
         if (sil) sil_eval(X.w_in, X.w_out, X.sigma);
         if (vt) vt_eval();
+        if (scan) scan_eval(X.scan_w_s2m, X.scan_w_m2s, X.scan_sigma);
         const float *g = X.g_verts, *L = X.loss;
         // one live vertex term with share 1: its own buffers go to the pull-back as they are
-        if (sil && !vt && X.silhouette == 1.f) { g = in.silt.g_verts; L = in.silt.loss; }
-        else if (vt && !sil && X.vertex_targets == 1.f) { g = in.vt.g_verts; L = in.vt.loss; }
+        if (sil && !vt && !scan && X.silhouette == 1.f) { g = in.silt.g_verts; L = in.silt.loss; }
+        else if (vt && !sil && !scan && X.vertex_targets == 1.f) { g = in.vt.g_verts; L = in.vt.loss; }
+        else if (scan && !sil && !vt && X.scan == 1.f) { g = in.scan.g_verts; L = in.scan.loss; }
         else {
             MixCotangentStep& s = add(STEP_MIX_COTANGENT).cot;
             s.lam_sil = X.silhouette; s.lam_vt = X.vertex_targets;
             if (sil) { s.g_sil = in.silt.g_verts; s.L_sil = in.silt.loss; }
             if (vt) { s.g_vt = in.vt.g_verts; s.L_vt = in.vt.loss; }
+            if (scan) { s.lam_scan = X.scan; s.g_scan = in.scan.g_verts; s.L_scan = in.scan.loss; }
             s.g = X.g_verts; s.L_v = X.loss;
             if (!sc) { s.parts = X.parts; s.sums = X.sums; }       // (with a scene share the record merge writes them)
         }
@@ -88,6 +92,7 @@ struct Builder {
             s.rec_scene = X.rec_scene; s.rec_verts = X.rec_verts;
             if (sil) s.L_sil = in.silt.loss;
             if (vt) s.L_vt = in.vt.loss;
+            if (scan) { s.lam_scan = X.scan; s.L_scan = in.scan.loss; }
             s.rec = in.sdf_adj; s.parts = X.parts; s.sums = X.sums;
         }
         sums_at(X.sums, sizeof(float));                              // the weighted sum of the parts: penalty = w^2 sums
@@ -118,7 +123,7 @@ RoundTermPlan plan_round_term(const TermInputs& in, bool live) {
         b.sums_at(in.silt.loss, sizeof(float));
         break;
     case TERM_SCAN:
-        b.scan_eval();
+        b.scan_eval(in.scan.w_s2m, in.scan.w_m2s, in.scan.sigma);
         b.pullback(in.scan.g_verts, in.scan.loss, in.scan.part, in.sdf_adj);
         b.sums_at(in.scan.loss, sizeof(float));
         break;

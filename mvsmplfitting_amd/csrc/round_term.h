@@ -57,6 +57,8 @@ struct TermInputs {
         float *g_verts = nullptr, *loss = nullptr, *part = nullptr;
         SdfAdj *rec_scene = nullptr, *rec_verts = nullptr;
         float *parts = nullptr, *sums = nullptr;
+        float scan = 0.f;               // the scan share, and the scan term's scalars of a mix with one
+        float scan_w_s2m = 0.f, scan_w_m2s = 0.f, scan_sigma = 0.f;
     } mix;
     struct {            // the scan set (ScanState), the scan term and its round buffers (ScanTerm)
         bool on = false, term = false;
@@ -97,6 +99,8 @@ struct MixCotangentStep {
     float lam_sil, lam_vt;
     const float *g_sil, *L_sil, *g_vt, *L_vt;
     float *g, *L_v, *parts, *sums;
+    float lam_scan;
+    const float *g_scan, *L_scan;
 };
 // launch_silhouette_pullback: a vertex cotangent and its loss -> a record
 struct PullbackStep {
@@ -121,6 +125,8 @@ struct MixRecordStep {
     const float *L_sil, *L_vt;
     SdfAdj* rec;
     float *parts, *sums;
+    float lam_scan;
+    const float* L_scan;
 };
 // launch_sdf_term (the tile keys of the box come with the round's pass, not with the plan)
 struct SdfStep {
@@ -155,7 +161,7 @@ struct TermStep {
     };
 };
 
-constexpr int kMaxTermSteps = 6;
+constexpr int kMaxTermSteps = 7;
 
 // Zero-filled, then assigned field by field: the bytes are a function of the fields (they are the graph key), and a plan of
 // all zeros is the round without a term.

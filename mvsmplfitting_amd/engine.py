@@ -580,6 +580,8 @@ class MvFit:
                                        w.ctypes.data_as(_lib._fp) if w is not None else None)
         if rc and self._scan_term and (N != self.B or rc != -1):
             self._scan_term = False              # (a set that fails, or does not fit an enabled term, switches the term off)
+        if rc and self._mix_scan() and (N != self.B or rc != -1):
+            self._mix = None                     # (and a mix that gives the scan a share)
         self._check(rc)
         self._scan_shape = (N, Pmax)
 
@@ -588,6 +590,11 @@ class MvFit:
         self._check(self._lib.mvfit_set_scans(self._ctx, 0, 0, None, None, None))
         self._scan_shape = None
         self._scan_term = False                  # (no scans, no term: the C side switches it off)
+        if self._mix_scan():
+            self._mix = None                     # (and no mix that uses them)
+
+    def _mix_scan(self):
+        return bool(self._mix) and len(self._mix) > 3 and self._mix[3] > 0
 
     def set_scan_term(self, w_s2m=1.0, w_m2s=0.0, sigma=0.0):
         """Make the scan loss of the current scan set a term of closure() and fit() (include/mvfit.h:mvfit_set_scan_term): a
@@ -687,28 +694,32 @@ class MvFit:
         self._vt_term = False
 
     # ------------------------------------------------------------------ term mix (include/mvfit.h:mvfit_set_term_mix)
-    def set_term_mix(self, scene=0.0, silhouette=0.0, vertex_targets=0.0, w_in=1.0, w_out=1.0, sigma=0.0):
-        """Make a weighted sum of the scene, silhouette and vertex-target terms the term of closure() and fit()
+    def set_term_mix(self, scene=0.0, silhouette=0.0, vertex_targets=0.0, w_in=1.0, w_out=1.0, sigma=0.0, scan=0.0, scan_w_s2m=1.0,
+                     scan_w_m2s=0.0, scan_sigma=0.0):
+        """Make a weighted sum of the scene, silhouette, vertex-target and scan terms the term of closure() and fit()
         (include/mvfit.h:mvfit_set_term_mix): a stage with coll_loss_weight w > 0 adds w^2 * (scene * S_sc^2 + silhouette *
-        L_sil + vertex_targets * L_vt) to every problem.  At least two shares > 0, each with its data set in place
-        (set_scene_obstacles / set_silhouettes / set_vertex_targets); w_in, w_out, sigma are the silhouette term's."""
+        L_sil + vertex_targets * L_vt + scan * L_scan) to every problem.  At least two shares > 0, each with its data set in
+        place (set_scene_obstacles / set_silhouettes / set_vertex_targets / set_scans with B bodies); w_in, w_out, sigma are
+        the silhouette term's scalars, scan_w_s2m, scan_w_m2s, scan_sigma the scan term's."""
         m = _lib.TermMix(C.sizeof(_lib.TermMix), float(scene), float(silhouette), float(w_in), float(w_out), float(sigma),
-                         float(vertex_targets))
+                         float(vertex_targets), float(scan), float(scan_w_s2m), float(scan_w_m2s), float(scan_sigma))
         rc = self._lib.mvfit_set_term_mix(self._ctx, C.byref(m))
         if rc not in (0, -1, -3):                # (a failed allocation leaves no mix; a refusal keeps the one in place)
             self._mix = None
         self._check(rc)
-        self._mix = (float(scene), float(silhouette), float(vertex_targets))
+        self._mix = (float(scene), float(silhouette), float(vertex_targets)) + ((float(scan),) if float(scan) > 0 else ())
 
     def clear_term_mix(self):
         """Switch the mix of set_term_mix off (the data sets stay)."""
         self._check(self._lib.mvfit_set_term_mix(self._ctx, None))
         self._mix = None
 
-    def term_mix_read(self):
-        """[B,3]: S_sc^2, L_sil, L_vt of the mix's last evaluation, unweighted (0 for a share of 0)."""
-        parts = torch.empty(self.B, 3, device=self.device)
-        self._check(self._lib.mvfit_term_mix_read(self._ctx, parts.data_ptr()))
+    def term_mix_read(self, scan=False):
+        """[B,3]: S_sc^2, L_sil, L_vt of the mix's last evaluation, unweighted (0 for a share of 0); scan=True: [B,4], with
+        L_scan behind them (include/mvfit.h:mvfit_term_mix_read4)."""
+        parts = torch.empty(self.B, 4 if scan else 3, device=self.device)
+        read = self._lib.mvfit_term_mix_read4 if scan else self._lib.mvfit_term_mix_read
+        self._check(read(self._ctx, parts.data_ptr()))
         return parts
 
     def term_mix_cotangent(self, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt):
@@ -719,6 +730,16 @@ class MvFit:
         L = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_term_mix_cotangent(self._ctx, float(silhouette), ptr(g_sil), ptr(L_sil), float(vertex_targets),
                                                        ptr(g_vt), ptr(L_vt), g.data_ptr(), L.data_ptr()))
+        return g, L
+
+    def term_mix_cotangent3(self, silhouette, g_sil, L_sil, vertex_targets, g_vt, L_vt, scan, g_scan, L_scan):
+        """term_mix_cotangent with the scan as third component (include/mvfit.h:mvfit_term_mix_cotangent3)."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        g = torch.empty(self.B, self.nv, 3, device=self.device)
+        L = torch.empty(self.B, device=self.device)
+        self._check(self._lib.mvfit_term_mix_cotangent3(self._ctx, float(silhouette), ptr(g_sil), ptr(L_sil), float(vertex_targets),
+                                                        ptr(g_vt), ptr(L_vt), float(scan), ptr(g_scan), ptr(L_scan), g.data_ptr(),
+                                                        L.data_ptr()))
         return g, L
 
     def term_mix_merge(self, scene, rec_scene, rec_verts):

@@ -190,6 +190,30 @@ def read_mask(path):
         return np.asarray(ImageOps.exif_transpose(im).convert('L'), dtype=np.uint8)
 
 
+def read_points(path):
+    """A scan's point file (.npy) -> (points float32 [P,3] in world coordinates, weights float32 [P] or None): a float array
+    [P,3], or [P,4] with a weight >= 0 in the last column.  ValueError for another shape or dtype and for a negative or
+    non-finite weight."""
+    a = np.load(path, allow_pickle=False)
+    if a.ndim != 2 or a.shape[1] not in (3, 4) or not np.issubdtype(a.dtype, np.floating):
+        raise ValueError('%s: a point file holds a float array [P,3] or [P,4], not %s %r' % (path, a.dtype, a.shape))
+    if a.shape[1] == 3:
+        return np.ascontiguousarray(a, np.float32), None
+    w = a[:, 3].astype(np.float32)
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError('%s: the weights (last column) must be finite and >= 0' % path)
+    return np.ascontiguousarray(a[:, :3], np.float32), w
+
+
+def read_depth(path):
+    """A depth map (.npy) -> float32 [H,W], camera-space z; a pixel without a measurement holds 0, a negative value, inf or NaN.
+    ValueError for another shape or dtype."""
+    a = np.load(path, allow_pickle=False)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.floating):
+        raise ValueError('%s: a depth map holds a float array [H,W], not %s %r' % (path, a.dtype, a.shape))
+    return np.ascontiguousarray(a, np.float32)
+
+
 def downscale_mask(mask, k):
     """mask [H, W] (non-zero = on) at 1/k of the resolution: low-res pixel (y, x) covers the block rows k y .. k y + k - 1,
     columns likewise, cut at the image's edge, and is on (1) when at least half of the pixels the block HAS are on.  k = 1
@@ -229,5 +253,5 @@ def save_image(path, rgb, quality=95):
     return path
 
 
-__all__ = ['read_image', 'image_size', 'save_image', 'read_mask', 'downscale_mask', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'read_people', 'read_people3d', 'problem_tensors', 'result_dict',
+__all__ = ['read_image', 'image_size', 'save_image', 'read_mask', 'read_points', 'read_depth', 'downscale_mask', 'load_camera_para', 'read_keypoints', 'read_joints3d', 'read_people', 'read_people3d', 'problem_tensors', 'result_dict',
            'save_result_pkl', 'save_obj']

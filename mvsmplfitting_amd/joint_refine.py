@@ -1,11 +1,11 @@
 """Joint refinement with several terms in one fit: the scene collision term against the other bodies of the scene, the
-silhouette term against the engine's mask set and the vertex-target term against the bodies of the neighbouring frames,
-mixed behind one weight (include/mvfit.h:mvfit_set_term_mix).
+silhouette term against the engine's mask set, the vertex-target term against the bodies of the neighbouring frames and the
+scan term against the engine's scan set, mixed behind one weight (include/mvfit.h:mvfit_set_term_mix).
 
 Run one after another, the three refinements (scene_fit.refine_scenes, silhouette.refine_fit, temporal.smooth_sequences)
 each undo part of what the one before achieved.  Here every sweep is ONE fit of
 
-    loss_j = f_j + w^2 (l_sc S_sc,j^2 + l_sil L_sil,j + l_t L_vt,j)
+    loss_j = f_j + w^2 (l_sc S_sc,j^2 + l_sil L_sil,j + l_t L_vt,j + l_scan L_scan,j)
 
 with the obstacles and the neighbours frozen where the sweep started - a Jacobi sweep, as in the two single drivers.  The
 frozen problems count every pair of consecutive frames twice (temporal.py), so the joint energy of a set g of problems is
@@ -15,7 +15,7 @@ frozen problems count every pair of consecutive frames twice (temporal.py), so t
 the scene part counted as refine_scenes counts it.  Freezing couples the problems of one scene and the consecutive frames
 of one sequence, and nothing else: the accept rule works on the connected components of that graph.  A component keeps a
 sweep only if its E fell with everything re-frozen at the new bodies; otherwise its rows revert exactly, which is what makes
-E non-increasing.
+E non-increasing.  The scan part is a problem's own, like the silhouette's: it links no problems and needs no correction in E.
 
 Not built: per-problem shares, sequence mode, the one-person SDF term in the mix."""
 import numpy as np
@@ -24,6 +24,7 @@ import torch
 from .temporal import neighbour_table
 
 SHARE_KEYS = ('scene', 'silhouette', 'temporal')
+SCAN_KEY = 'scan'                       # the optional fourth share
 
 
 def _np(t):
@@ -66,25 +67,29 @@ def problem_groups(B, scene_sizes=None, nbr=None):
 
 
 def check_shares(shares):
-    """shares -> (scene, silhouette, temporal) floats; ValueError for unknown keys, negative or non-finite values and fewer
-    than two shares > 0."""
-    unknown = sorted(set(shares) - set(SHARE_KEYS))
+    """shares -> (scene, silhouette, temporal) floats, or (scene, silhouette, temporal, scan) when ``shares`` has the key
+    'scan'; ValueError for unknown keys, negative or non-finite values and fewer than two shares > 0."""
+    keys = SHARE_KEYS + ((SCAN_KEY,) if SCAN_KEY in shares else ())
+    unknown = sorted(set(shares) - set(SHARE_KEYS) - {SCAN_KEY})
     if unknown:
-        raise ValueError('refine_joint: unknown shares %r (known: %s)' % (unknown, ', '.join(SHARE_KEYS)))
-    lam = tuple(float(shares.get(k, 0.0)) for k in SHARE_KEYS)
+        raise ValueError('refine_joint: unknown shares %r (known: %s)' % (unknown, ', '.join(SHARE_KEYS + (SCAN_KEY,))))
+    lam = tuple(float(shares.get(k, 0.0)) for k in keys)
     if any(not np.isfinite(v) or v < 0.0 for v in lam):
-        raise ValueError('refine_joint: the shares must be finite and >= 0, got %r' % (dict(zip(SHARE_KEYS, lam)),))
+        raise ValueError('refine_joint: the shares must be finite and >= 0, got %r' % (dict(zip(keys, lam)),))
     if sum(v > 0.0 for v in lam) < 2:
         raise ValueError('refine_joint: at least two shares must be > 0 (a single term has a driver of its own)')
     return lam
 
 
 def refine_joint(engine, params, stage, *, shares, scene_sizes=None, seq_id=None, frame_idx=None, sweeps=3, grid_size=32,
-                 scale_factor=0.2, robustifier=0.05, w_in=1.0, w_out=1.0, sigma=0.0, **fit_kwargs):
+                 scale_factor=0.2, robustifier=0.05, w_in=1.0, w_out=1.0, sigma=0.0, scan_w_s2m=1.0, scan_w_m2s=0.0, scan_sigma=0.0,
+                 **fit_kwargs):
     """params [B,118] of the engine's B problems (set_problems done); ``stage``: one weight dict with coll_loss_weight = w >
     0; ``shares`` = dict(scene=, silhouette=, temporal=), at least two > 0.  scene > 0 needs ``scene_sizes`` (consecutive
     problems per scene), temporal > 0 needs ``seq_id`` and ``frame_idx`` (temporal.neighbour_table), silhouette > 0 needs the
-    mask set on the engine already (set_silhouettes; w_in, w_out, sigma are the term's scalars).
+    mask set on the engine already (set_silhouettes; w_in, w_out, sigma are the term's scalars).  ``shares`` may also name
+    scan: scan > 0 needs the scan set of B bodies on the engine already (set_scans; scan_w_s2m, scan_w_m2s, scan_sigma are the
+    term's scalars); parts0, parts and parts_problem then have a fourth column, L_scan, and the scan set stays like the masks.
 
       1. freeze obstacles and neighbour targets at x_0; one closure and term_mix_read give E(x_0);
       2. per sweep: x' = engine.fit(x_k, [stage]); re-freeze at vertices(x'); one closure gives E(x'); group g is accepted
@@ -100,7 +105,10 @@ def refine_joint(engine, params, stage, *, shares, scene_sizes=None, seq_id=None
     w = float(stage.get('coll_loss_weight', 0.0))
     if w <= 0.0:
         raise ValueError('refine_joint: the stage needs coll_loss_weight > 0')
-    lam_sc, lam_sil, lam_t = check_shares(shares)
+    lam = check_shares(shares)
+    lam_sc, lam_sil, lam_t = lam[:3]
+    with_scan = len(lam) > 3 and lam[3] > 0.0
+    lam_scan = lam[3] if with_scan else 0.0
     B = engine.B
     sizes = None
     if lam_sc > 0.0:
@@ -136,20 +144,24 @@ def refine_joint(engine, params, stage, *, shares, scene_sizes=None, seq_id=None
         if lam_t > 0.0:
             engine.set_vertex_targets(v[rows], a)
         if not state['mix']:
-            engine.set_term_mix(scene=lam_sc, silhouette=lam_sil, vertex_targets=lam_t, w_in=w_in, w_out=w_out, sigma=sigma)
+            if with_scan:
+                engine.set_term_mix(scene=lam_sc, silhouette=lam_sil, vertex_targets=lam_t, w_in=w_in, w_out=w_out, sigma=sigma,
+                                    scan=lam_scan, scan_w_s2m=scan_w_s2m, scan_w_m2s=scan_w_m2s, scan_sigma=scan_sigma)
+            else:                            # (exactly the call of a mix without the share)
+                engine.set_term_mix(scene=lam_sc, silhouette=lam_sil, vertex_targets=lam_t, w_in=w_in, w_out=w_out, sigma=sigma)
             state['mix'] = True
 
     def objective(xx):
         """(loss [B] tensor, parts [B,3], E [G]) with everything as frozen."""
         loss = engine.closure(xx, stage, want_grad=False)['loss']
-        parts = _np(engine.term_mix_read()).astype(np.float64)
+        parts = _np(engine.term_mix_read(scan=True) if with_scan else engine.term_mix_read()).astype(np.float64)
         return loss, parts, sums(_np(loss).astype(np.float64) - 0.5 * w * w * lam_t * parts[:, 2])
 
     try:
         freeze(x)
         loss, parts, E = objective(x)
         gparts = sums(parts)
-        report = dict(group=group.copy(), shares=dict(zip(SHARE_KEYS, (lam_sc, lam_sil, lam_t))), E0=E.copy(),
+        report = dict(group=group.copy(), shares=dict(zip(SHARE_KEYS + ((SCAN_KEY,) if len(lam) > 3 else ()), lam)), E0=E.copy(),
                       parts0=gparts.copy(), params0=_np(x).copy(), sweeps=[])
         for k in range(int(sweeps)):
             x_new, st = engine.fit(x, [stage], **fit_kwargs)

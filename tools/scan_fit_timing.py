@@ -1,6 +1,6 @@
 """Timing of the scan term inside the fit (include/mvfit.h:mvfit_set_scan_term) and of the op alone.
 
-  python tools/scan_fit_timing.py [--reps 30] [--bodies 32] [--views 8] [--points 8192] [--rounds 96] [--only-rounds]
+  python tools/scan_fit_timing.py [--reps 30] [--bodies 32] [--views 8] [--points 8192] [--rounds 96] [--only-rounds] [--mix]
 
 Workload: ``bodies`` synthetic bodies x ``views`` cameras (the bodies of tools/vertex_target_fit_timing.py), every problem with
 ``points`` scan points of weight 1 on a noisy copy of its own surface (5 mm) and every problem live; w_s2m = 1, w_m2s = 0,
@@ -11,6 +11,9 @@ sigma = 0.  Medians of ``reps`` after a warm-up, from device events:
                   rounds with weight 0 (vertex pass and step kernel alone).  The call's fixed part (initialisation, results,
                   one host wait per replay) is inside both.
   op              scan_loss with the gradient (culled search), 20 calls inside one pair of events.
+--mix adds the same rounds with the scan as a share of the term mix (mvfit_set_term_mix) beside the scene term - the bodies
+paired into scenes of two, obstacles frozen at the start: with scan share 1 (the scan buffers go to the pull-back as they are)
+and with scan share 2 at weight w / sqrt(2) (the same penalty through the cotangent kernel).
 --only-rounds runs the two round fits alone: the run to put under rocprofv3 --kernel-trace --stats for the per-kernel split
 (no counters in that run).  Run every invocation under a time limit of its own."""
 import argparse
@@ -60,6 +63,7 @@ def main():
     ap.add_argument('--points', type=int, default=8192)
     ap.add_argument('--rounds', type=int, default=96)
     ap.add_argument('--only-rounds', action='store_true')
+    ap.add_argument('--mix', action='store_true')
     a = ap.parse_args()
     N, V, P = a.bodies, a.views, a.points
     rounds = max(24, a.rounds // 24 * 24)
@@ -107,6 +111,18 @@ def main():
     print(fmt % (('chained round with the term',) + stats(per[w]) + (a.reps,)))
     print('the term adds %.3f ms per round (medians)' % (stats(per[w])[0] - stats(per[0.0])[0]))
     eng.clear_scan_term()
+    if a.mix:
+        if N % 2:
+            raise SystemExit('--mix pairs the bodies into scenes of two: --bodies must be even')
+        eng.set_scene_obstacles(v0, [2] * (N // 2), grid_size=32, scale_factor=0.2, robustifier=0.05)
+        for share, weight, what in ((1.0, w, 'scan share 1: pass-through'), (2.0, w / np.sqrt(2.0), 'scan share 2: cotangent kernel')):
+            eng.set_term_mix(scene=1.0, scan=share)
+            capped_fit(weight)
+            capped_fit(weight)
+            pm = [timed(lambda: capped_fit(weight)) / rounds for _ in range(a.reps)]
+            print(fmt % (('chained round, mix scene + scan (%s)' % what,) + stats(pm) + (a.reps,)))
+        eng.clear_term_mix()
+        eng.clear_scene_obstacles()
     if not a.only_rounds:
         calls = 20
         loss, g = torch.empty(N, device=eng.device), torch.empty_like(v0)
