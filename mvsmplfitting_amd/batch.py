@@ -26,7 +26,9 @@ the data weight 500 / H refers to (non_linear_solver.py:150,177) is an argument.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
+import time
 import warnings
 from concurrent.futures import ThreadPoolExecutor
 
@@ -217,6 +219,21 @@ def render_serial_images(eng: MvFit, verts, joints, jobs, out_folder, pool, scen
 
 SILHOUETTE_DEFAULTS = dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31, occlusion=None)
 OCCLUSION_DEFAULTS = dict(margin=0.02, sweeps=2)
+SCAN_DEFAULTS = dict(root=None, depth_root=None, w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1, mask_root=None)
+
+
+def check_scene_collision(cfg, is_seq=False, multi=True):
+    """fit_folder's ``scene_collision`` option, or ValueError (its defaults are scene_fit.refine_scenes' own)."""
+    if not multi:
+        raise ValueError('scene_collision refines the persons of a frame together: it needs persons= a list of ids or \'all\'')
+    if is_seq:
+        raise ValueError('scene_collision is not available with is_seq=True')
+    if not isinstance(cfg, dict) or 'weight' not in cfg:
+        raise ValueError("scene_collision: a dict with at least 'weight' (the collision term's coll_loss_weight)")
+    unknown = set(cfg) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
+    if unknown:
+        raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
+    return cfg
 
 
 def check_silhouettes(silhouettes, is_seq=False, scene_collision=None, multi=True):
@@ -268,9 +285,9 @@ def check_temporal(temporal, scene_collision=None, silhouettes=None):
 
 
 JOINT_PARTS = dict(scene_collision=dict(grid_size=32, robustifier=0.05, scale_factor=0.2),
-                   silhouettes=dict(w_in=1.0, w_out=1.0, sigma=0.0, contour_stride=1, downscale=1, max_mask_bytes=2 ** 31),
+                   silhouettes={k: v for k, v in SILHOUETTE_DEFAULTS.items() if k != 'occlusion'},      # (not built under joint)
                    temporal=dict(),
-                   scans=dict(root=None, depth_root=None, w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1, mask_root=None))
+                   scans=dict(SCAN_DEFAULTS))
 
 
 def check_joint(joint, is_seq=False, multi=False, scene_collision=None, silhouettes=None, temporal=None, scans=None):
@@ -323,9 +340,6 @@ def mask_path(mask_root, serial, camera, frame, person=None):
     person ``id`` of the multi-person path."""
     name = frame + '.png' if person is None else '%s_%03d.png' % (frame, int(person))
     return os.path.join(mask_root, serial, camera, name)
-
-
-SCAN_DEFAULTS = dict(root=None, depth_root=None, w_s2m=1.0, w_m2s=0.0, sigma=0.05, max_points=8192, stride=1, mask_root=None)
 
 
 def _check_scan_values(who, cfg, multi):
@@ -620,6 +634,320 @@ def refine_serial_cameras(eng, xf, stage, cfg, serial, rig, gt_xy, conf, intris,
     return xr, report, (ex, K)
 
 
+@dataclasses.dataclass
+class SerialProblems:
+    """One serial's problems as fit_serial takes them, from either path; row n of every array is problem n."""
+    serial: str
+    cams: list                   # camera folder names, view v = rig row v
+    frames: list                 # list_frames' [(frame name, [json path or None per camera])]
+    V: int
+    prob: list                   # [(frame index, person id or None)]
+    pf: np.ndarray               # [N] frame index
+    pp: np.ndarray | None        # [N] person id; None: the single-person path
+    kp: np.ndarray               # [N, V, 17, 3] (u, v, confidence)
+    vmask: np.ndarray            # [N, V] the views that list the problem
+    ann: np.ndarray | None       # [N, 17, 4] 3-D annotation (x, y, z, confidence)
+    has: np.ndarray              # [N] the problems that carry one
+    scales: np.ndarray | None    # [N, 1] fixed scale
+    shapes: np.ndarray | None    # [N, 10] fixed shape
+    jobs: list | None            # render_serial_images' jobs (save_images)
+    association: dict | None = None
+
+
+@dataclasses.dataclass
+class FitContext:
+    """What one fit_folder call hands to every serial: the engine, the checked settings, where the files go, the clock."""
+    eng: MvFit
+    model: dict
+    extris: np.ndarray
+    intris: np.ndarray
+    jw: np.ndarray               # [17] joint weights
+    flags: int
+    use_vposer: bool
+    use_hip: bool
+    use_3d: bool
+    is_seq: bool
+    stages_for: object           # with_3d -> stage list
+    want: list | None            # the person ids asked for; None: all
+    associate: dict | None
+    fix_scale: object
+    fix_shape: object
+    options: dict                # the checked refinement options by name; None: not asked for
+    result_folder: str
+    mesh_folder: str | None      # None: no meshes
+    image_root: str | None
+    image_folder: str | None     # None: no overlays
+    timing: dict | None
+    pool: ThreadPoolExecutor | None
+    t: float                     # start of the step being timed
+
+
+def _tick(ctx, key):
+    if ctx.timing is not None:
+        torch.cuda.synchronize(ctx.eng.device)
+        ctx.timing[key] = ctx.timing.get(key, 0.0) + (time.time() - ctx.t)
+    ctx.t = time.time()
+
+
+def per_problem(val, pp, width, name, dtype=np.float32):
+    """fix_scale / fix_shape as one row per problem (None: not fixed)."""
+    if val is None:
+        return None
+    if isinstance(val, dict):
+        missing = sorted(set(pp.tolist()) - set(val))
+        if missing:
+            raise ValueError('%s holds no value for persons %s' % (name, missing))
+        return np.stack([np.asarray(val[int(p)], dtype).reshape(width) for p in pp])
+    return np.tile(np.asarray(val, dtype).reshape(1, width), (len(pp), 1))
+
+
+def overlay_jobs(image_root, serial, cams, frames, which):
+    """render_serial_images' jobs of the frames ``which``: the views that had a keypoint file in the frame (main.py:44-66);
+    a missing image is a ValueError, before the fit."""
+    return [(f, v, image_path(image_root, serial, cams[v], frames[f][0]), (serial, frames[f][0], cams[v]))
+            for f in which for v in range(len(cams)) if frames[f][1][v] is not None]
+
+
+def single_person_problems(ctx, serial, cams, frames):
+    """persons=0: person 0 of every frame of the serial."""
+    V, F = len(cams), len(frames)
+    kp, vmask = load_serial(frames, V, return_mask=True)
+    jobs = overlay_jobs(ctx.image_root, serial, cams, frames, range(F)) if ctx.image_folder is not None else None
+    if not vmask.any(1).all():
+        raise ValueError('serial %s: frames %s have no keypoint file in any camera folder'
+                         % (serial, [frames[f][0] for f in np.flatnonzero(~vmask.any(1))]))
+    ann, has = load_serial_joints3d(frames) if ctx.use_3d else (None, np.zeros(F, bool))
+    one = np.zeros(F, np.int64)
+    # (the one fixed scale reaches the initial guess as the caller's double; per person it is a float32 row)
+    return SerialProblems(serial, cams, frames, V, [(f, None) for f in range(F)], np.arange(F), None, kp, vmask, ann, has,
+                          per_problem(ctx.fix_scale, one, 1, 'fix_scale', np.float64),
+                          per_problem(ctx.fix_shape, one, 10, 'fix_shape'), jobs)
+
+
+def persons_problems(ctx, serial, cams, frames):
+    """persons= a list or 'all': every (frame, person) pair that a view lists, frame-major in ascending id order; None when no
+    requested person occurs in the serial."""
+    V, F = len(cams), len(frames)
+    association = None
+    if ctx.associate is not None:
+        _tick(ctx, 'read')
+        ids_all, kpp, pmask, association = assoc.associate_serial(ctx.eng, frames, ctx.extris, ctx.intris, **ctx.associate)
+        _tick(ctx, 'associate')
+    else:
+        ids_all, kpp, pmask = load_serial_people(frames, V)
+    col = {p: i for i, p in enumerate(ids_all)}
+    ids = [p for p in (ids_all if ctx.want is None else ctx.want) if p in col]
+    prob = [(f, p) for f in range(F) for p in ids if pmask[f, col[p]].any()]
+    empty = sorted(set(range(F)) - {f for f, _ in prob})
+    if empty:
+        warnings.warn('serial %s: frames %s list none of the persons %s in any view; skipped'
+                      % (serial, [frames[f][0] for f in empty], 'all' if ctx.want is None else ctx.want), RuntimeWarning)
+    if not prob:
+        return None
+    pf, pp = np.array([f for f, _ in prob]), np.array([p for _, p in prob])
+    jobs = overlay_jobs(ctx.image_root, serial, cams, frames, sorted(set(pf.tolist()))) if ctx.image_folder is not None else None
+    ann, has = None, np.zeros(len(prob), bool)
+    if ctx.use_3d:
+        j3p, hasp = load_serial_people3d(frames, ids_all)
+        ann = np.stack([j3p[f, col[p]] for f, p in prob])
+        has = np.array([hasp[f, col[p]] for f, p in prob])
+    return SerialProblems(serial, cams, frames, V, prob, pf, pp, np.stack([kpp[f, col[p]] for f, p in prob]),
+                          np.stack([pmask[f, col[p]] for f, p in prob]), ann, has, per_problem(ctx.fix_scale, pp, 1, 'fix_scale'),
+                          per_problem(ctx.fix_shape, pp, 10, 'fix_shape'), jobs, association)
+
+
+def serial_refinements(ctx, sp, rig, gt_xy, conf, intris, has):
+    """The refinements the call asks for, in the order they run on a serial's fitted problems: [(name, timing key, result key,
+    targets, run)].  run(eng, xf, sp) -> (params, report[, what the result holds under 'cameras']); ``targets``: the 3-D
+    targets are set before it when every problem carries them (after a fit in one group they are still in place).  Every one
+    runs with the last stage's weights.  A frame is a scene (the problems are frame-major); a person id is a track whose
+    frame_idx is the position in the serial's frame list, so an absence breaks the chain; persons=0 is one track."""
+    N, o = len(sp.prob), ctx.options
+    problems = [(int(f), None if p is None else int(p)) for f, p in sp.prob]
+    if sp.pp is None:
+        seq_id, frame_idx, sizes = np.zeros(N, np.int64), np.arange(N), None
+    else:
+        seq_id, frame_idx, sizes = sp.pp, sp.pf, [int((sp.pf == f).sum()) for f in sorted(set(sp.pf.tolist()))]
+
+    def last(with_3d=True):
+        return ctx.stages_for(with_3d and bool(has.all()))[-1]
+    table = []
+    if o['scene_collision'] is not None:
+        sc = dict(o['scene_collision'])
+        weight = float(sc.pop('weight'))
+        table.append(('scene collision', 'refine', 'scene_report', False,
+                      lambda eng, xf, sp: refine_scenes(eng, xf, sizes, dict(last(), coll_loss_weight=weight), **sc)))
+    if o['silhouettes'] is not None:
+        table.append(('silhouettes', 'silhouette', 'silhouette_report', False,
+                      lambda eng, xf, sp: refine_serial_silhouettes(eng, xf, last(), o['silhouettes'], sp.serial, sp.cams, sp.frames,
+                                                                    problems, rig, eng.nv)))
+    if o['scans'] is not None:
+        table.append(('scans', 'scan', 'scan_report', False,
+                      lambda eng, xf, sp: refine_serial_scans(eng, xf, last(), o['scans'], sp.serial, sp.cams, sp.frames, problems, rig)))
+    if o['temporal'] is not None:
+        table.append(('temporal', 'temporal', 'temporal_report', True,
+                      lambda eng, xf, sp: smooth_sequences(eng, xf, dict(last(), coll_loss_weight=float(o['temporal']['weight'])),
+                                                           seq_id, frame_idx, sweeps=int(o['temporal']['sweeps']))))
+    if o['joint'] is not None:
+        table.append(('joint', 'joint', 'joint_report', True,
+                      lambda eng, xf, sp: refine_serial_joint(eng, xf, last(), o['joint'], sp.serial, sp.cams, sp.frames, problems, rig,
+                                                              eng.nv, sizes, seq_id, frame_idx)))
+    if o['refine_cameras'] is not None:
+        table.append(('cameras', 'cameras', 'camera_report', False,
+                      lambda eng, xf, sp: refine_serial_cameras(eng, xf, last(False), o['refine_cameras'], sp.serial, rig, gt_xy, conf,
+                                                                intris, ctx.result_folder)))
+    return table
+
+
+def fit_serial(ctx, sp):
+    """One serial's problems from the engine's set_problems to the overlays -> the serial's result dict of fit_folder."""
+    eng, N, single = ctx.eng, len(sp.prob), sp.pp is None
+    F, kp, pf, ann = len(sp.frames), sp.kp, sp.pf, sp.ann
+    ex, it = np.asarray(ctx.extris[:sp.V], np.float64), np.asarray(ctx.intris[:sp.V], np.float64)
+    rig = (ex[:, :3, :3].astype(np.float32), ex[:, :3, 3].astype(np.float32),
+           it[:, 0, 0].astype(np.float32), it[:, :2, 2].astype(np.float32))
+    gt_xy = kp[..., :2].copy()
+    conf = kp[..., 2] * ctx.jw[None, None, :]
+    eng.set_problems(rig, gt_xy, conf)
+    _tick(ctx, 'read')
+    # 3-D joint targets (non_linear_solver.py:86-99) and the initial alignment to them instead of the triangulation
+    # (init_guess.py:84-85) - decided PER PROBLEM like the reference (:68-69): problems with an annotation are fitted with
+    # the 3-D term, the others without it (two batched fits when a serial mixes both)
+    has = sp.has
+    if ctx.is_seq and has.any() and not has.all():
+        warnings.warn('serial %s: %d of %d %s carry no 3-D annotation; the is_seq chain runs on one objective - '
+                      'fitting the whole serial from the 2-D keypoints only'
+                      % (sp.serial, int((~has).sum()), N, 'frames' if single else 'problems'))
+        has = np.zeros(N, bool)
+    mixed = bool(has.any() and not has.all())
+    c3 = None
+    if has.any():
+        c3 = ann[:, :, 3].copy()
+        if not ctx.use_hip:
+            c3[:, 11] = c3[:, 12] = 0.0
+    # one init_guess_batch per distinct fixed scale (one call when everybody shares it); in a mixed serial the annotated
+    # problems are then aligned to their 3-D joints and the rest keep the triangulation / depth guess
+    guess = None
+    for rows, with_3d in [(np.arange(N), bool(has.all()))] + ([(np.flatnonzero(has), True)] if mixed else []):
+        groups = [rows] if sp.scales is None else [rows[sp.scales[rows, 0] == v_] for v_ in np.unique(sp.scales[rows, 0])]
+        for g in groups:
+            if g.size < N:
+                eng.set_problems(rig, gt_xy[g], conf[g])
+            r = init_guess_batch(eng, ex, it, kp[g], est_scale=sp.scales is None,
+                                 fixed_scale=None if sp.scales is None else float(sp.scales[g[0], 0]),
+                                 joints3d=ann[g][:, :, :3].astype(np.float64) if with_3d else None, view_mask=sp.vmask[g])
+            if g.size == N:
+                guess = r
+            else:
+                if guess is None:
+                    guess = {k: torch.zeros((N,) + tuple(r[k].shape[1:]), dtype=r[k].dtype, device=r[k].device) for k in r}
+                idx = torch.as_tensor(g, device=eng.device)
+                for k in r:
+                    guess[k][idx] = r[k]
+                eng.set_problems(rig, gt_xy, conf)
+    x0 = initial_params(guess, ctx.use_vposer)
+    if sp.shapes is not None:
+        x0[:, 0:10] = torch.as_tensor(sp.shapes, device=x0.device)
+    _tick(ctx, 'init_guess')
+
+    if ctx.is_seq and single:
+        t3 = (ann[None, :, :, :3], c3[None]) if has.all() else None
+        xs, st = fit_sequences(eng, rig, gt_xy[None], conf[None], x0[None], ctx.stages_for(has.all()), joints3d=t3)
+        xf, final, ncl = xs[0], st['final_loss'][0], st['n_closure'][0]
+        restarted = st['restarted'][0]
+        eng.set_problems(rig, gt_xy, conf)                  # back to the whole serial for the outputs below
+    elif ctx.is_seq:
+        # the persons are the sequences; a person's chain runs over the frames they are in
+        seq = sorted(set(sp.pp.tolist()))
+        row = {p: s_ for s_, p in enumerate(seq)}
+        S = len(seq)
+        ps = np.array([row[p] for p in sp.pp.tolist()])
+        present = np.zeros((S, F), bool)
+        present[ps, pf] = True
+        gt_s = np.zeros((S, F) + gt_xy.shape[1:], np.float32)
+        conf_s = np.zeros((S, F) + conf.shape[1:], np.float32)
+        gt_s[ps, pf], conf_s[ps, pf] = gt_xy, conf
+        x0_s = torch.zeros(S, F, x0.shape[1], dtype=x0.dtype, device=x0.device)
+        x0_s[torch.as_tensor(ps), torch.as_tensor(pf)] = x0
+        t3 = None
+        if has.all():
+            a3, c3_s = np.zeros((S, F, 17, 3), np.float32), np.zeros((S, F, 17), np.float32)
+            a3[ps, pf], c3_s[ps, pf] = ann[:, :, :3], c3
+            t3 = (a3, c3_s)
+        xs, st = fit_sequences(eng, rig, gt_s, conf_s, x0_s, ctx.stages_for(has.all()), joints3d=t3, present=present)
+        si, fi = torch.as_tensor(ps, device=xs.device), torch.as_tensor(pf, device=xs.device)
+        xf = xs[si, fi].to(x0.dtype)
+        final, ncl = st['final_loss'][si, fi], st['n_closure'][si, fi]
+        restarted = st['restarted'][ps, pf]
+        eng.set_problems(rig, gt_xy, conf)
+    else:
+        xf = torch.empty_like(x0)
+        final = torch.empty(N, device=eng.device)
+        ncl = torch.zeros(N, dtype=torch.int32, device=eng.device)
+        for sel, with_3d in ((np.flatnonzero(has), True), (np.flatnonzero(~has), False)):
+            if sel.size == 0:
+                continue
+            if sel.size < N:
+                eng.set_problems(rig, gt_xy[sel], conf[sel])
+            if with_3d:
+                eng.set_joints3d(ann[sel][:, :, :3], c3[sel])
+            idx = torch.as_tensor(sel, device=eng.device)
+            xs_, st = eng.fit(x0[idx], ctx.stages_for(with_3d))
+            xf[idx], final[idx], ncl[idx] = xs_.to(xf.dtype), st['final_loss'].to(final.dtype), st['n_closure'].to(ncl.dtype)
+        if mixed:
+            eng.set_problems(rig, gt_xy, conf)
+        restarted = np.ones(N, bool)
+    _tick(ctx, 'fit')
+
+    reports = {}
+    for _, timing_key, result_key, targets, run in serial_refinements(ctx, sp, rig, gt_xy, conf, it, has):
+        if targets and has.all():
+            eng.set_joints3d(ann[:, :, :3], c3)
+        xr, report, *extra = run(eng, xf, sp)
+        xf = xr.to(xf.dtype)
+        final = torch.as_tensor(report['loss'], dtype=final.dtype, device=final.device)
+        reports[result_key] = report
+        if extra:
+            reports['cameras'] = extra[0]
+        _tick(ctx, timing_key)
+
+    pid = np.zeros(N, np.int64) if single else sp.pp
+    full = eng.full_pose(xf, flags=ctx.flags & ~_lib.F_USE_3D).cpu().numpy()
+    xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
+    res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if ctx.use_vposer else None) for n in range(N)]
+    files = [iof.save_result_pkl(ctx.result_folder, sp.serial, sp.frames[pf[n]][0], res[n], person_id=int(pid[n])) for n in range(N)]
+    if ctx.mesh_folder is not None or ctx.image_folder is not None:
+        # the body of the SAVED parameters: zeroed feet / hands, model(global_orient, transl, body_pose, betas)
+        # (utils.py:866-874); its joints are the keypoints save_images draws
+        xm = xf_h.copy()
+        xm[:, 13:82] = np.stack([r['body_pose'][0] for r in res])
+        verts_d, joints_d = eng.vertices(xm, flags=ctx.flags & ~_lib.F_VPOSER)
+    if ctx.mesh_folder is not None:
+        verts = verts_d.cpu().numpy()
+        for n in range(N):
+            d = os.path.join(ctx.mesh_folder, sp.serial, sp.frames[pf[n]][0])
+            os.makedirs(d, exist_ok=True)
+            iof.save_obj(os.path.join(d, '%03d.obj' % int(pid[n])), verts[n], ctx.model['faces'])
+    out = dict(frames=[fr[0] for fr in sp.frames], params=xf_h, final_loss=final_h, n_closure=ncl.cpu().numpy(), files=files,
+               init=x0.cpu().numpy(), restarted=restarted, used_3d=has.copy(), views_per_frame=sp.vmask.sum(1))
+    if not single:
+        out.update(problem_frame=pf, problem_person=sp.pp, persons=sorted(set(sp.pp.tolist())))
+    out.update(reports)
+    if sp.association is not None:
+        out['association'] = sp.association
+    _tick(ctx, 'write')
+    if ctx.image_folder is not None:
+        scene = None
+        if not single:
+            palette = np.asarray(SCENE_PALETTE, np.float32)
+            scene = {f: (np.flatnonzero(pf == f).tolist(), palette[sp.pp[pf == f] % 7]) for f in set(pf.tolist())}
+        out['images'] = render_serial_images(eng, verts_d, joints_d, sp.jobs, ctx.image_folder, ctx.pool, scene=scene)
+        _tick(ctx, 'render')
+    return out
+
+
+
+
 def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, image_height=1536.0, is_seq=False,
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
@@ -720,14 +1048,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     'cameras' entry, and ``final_loss`` is the report's loss.  The next serial starts from the camera file again.  Not built,
     ValueError before any engine work: together with is_seq, use_3d, scene_collision, silhouettes, temporal or joint; also
     for unknown keys."""
-    import time as _time
-
-    def _tick(key, t0):
-        if timing is not None:
-            torch.cuda.synchronize(eng.device)
-            timing[key] = timing.get(key, 0.0) + (_time.time() - t0)
-        return _time.time()
-    _t = _time.time()
+    t0 = time.time()
     model_type = 'smpllsp' if model.get('kp_regressor') is not None else 'smpl'
     if pose_format not in POSE_FORMATS:
         raise ValueError('Unknown pose format: {}'.format(pose_format))
@@ -740,23 +1061,15 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         if isinstance(persons, (str, bool)):
             raise ValueError("persons: an id, a list of ids or 'all', not %r" % (persons,))
         want = sorted({int(p) for p in (persons if isinstance(persons, (list, tuple, set, np.ndarray)) else [persons])})
-    if scene_collision is not None:
-        if not multi:
-            raise ValueError('scene_collision refines the persons of a frame together: it needs persons= a list of ids or \'all\'')
-        if is_seq:
-            raise ValueError('scene_collision is not available with is_seq=True')
-        if not isinstance(scene_collision, dict) or 'weight' not in scene_collision:
-            raise ValueError("scene_collision: a dict with at least 'weight' (the collision term's coll_loss_weight)")
-        unknown = set(scene_collision) - {'weight', 'sweeps', 'grid_size', 'robustifier', 'scale_factor'}
-        if unknown:
-            raise ValueError('scene_collision: unknown keys %s' % sorted(unknown))
-    sil_cfg = check_silhouettes(silhouettes, is_seq, scene_collision, multi) if silhouettes is not None else None
-    tmp_cfg = check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None
-    scan_cfg = (check_scans(scans, is_seq, multi, scene_collision, silhouettes, temporal, refine_cameras)
-                if scans is not None else None)
-    joint_cfg = check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal, scans) if joint is not None else None
-    cam_cfg = (check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint, scans)
-               if refine_cameras is not None else None)
+    options = dict(
+        scene_collision=check_scene_collision(scene_collision, is_seq, multi) if scene_collision is not None else None,
+        silhouettes=check_silhouettes(silhouettes, is_seq, scene_collision, multi) if silhouettes is not None else None,
+        temporal=check_temporal(temporal, scene_collision, silhouettes) if temporal is not None else None,
+        scans=(check_scans(scans, is_seq, multi, scene_collision, silhouettes, temporal, refine_cameras)
+               if scans is not None else None),
+        joint=check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal, scans) if joint is not None else None,
+        refine_cameras=(check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint, scans)
+                        if refine_cameras is not None else None))
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -772,425 +1085,60 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
         fix_scale = fix_scale[0] if isinstance(fix_scale, dict) else fix_scale
         fix_shape = fix_shape[0] if isinstance(fix_shape, dict) else fix_shape
     extris, intris = iof.load_camera_para(cam_file)
-    use_vposer = vposer is not None
-    flags = _lib.F_VPOSER if use_vposer else 0
+    flags = _lib.F_VPOSER if vposer is not None else 0
     if fix_scale is not None:
         flags |= _lib.F_FIX_SCALE
     if fix_shape is not None:
         flags |= _lib.F_FIX_SHAPE
-    user_stages = stages
-    own = engine is None
     eng = engine if engine is not None else MvFit(model, vposer=vposer, device=device)
     jw = np.ones(17, np.float32)
     if pose_format != 'lsp14' or not use_hip:                      # data_parser.py:353-356
         jw[11] = jw[12] = 0.0
+
     def stages_for(with_3d):
-        if user_stages is None:
+        if stages is None:
             return stage_weights(float(image_height), flags=flags | (_lib.F_USE_3D if with_3d else 0))
         # caller's stage list: the 3-D term follows the group being fitted (annotated frames carry it, the others
         # must not run it against absent targets), whatever the caller's flag words say
         out = []
-        for st_ in user_stages:
+        for st_ in stages:
             st_ = dict(st_)
             f_ = int(st_.get('flags', 0))
             st_['flags'] = (f_ | _lib.F_USE_3D) if with_3d else (f_ & ~_lib.F_USE_3D)
             out.append(st_)
         return out
-
-    def per_problem(val, pp, width, name):
-        """fix_scale / fix_shape as one row per problem (None: not fixed)."""
-        if val is None:
-            return None
-        if isinstance(val, dict):
-            missing = sorted(set(pp.tolist()) - set(val))
-            if missing:
-                raise ValueError('%s holds no value for persons %s' % (name, missing))
-            return np.stack([np.asarray(val[int(p)], np.float32).reshape(width) for p in pp])
-        return np.tile(np.asarray(val, np.float32).reshape(1, width), (len(pp), 1))
-
-    def fit_people(serial, cams, frames, V):
-        """The multi-person path of one serial -> its result dict, or None when no requested person occurs."""
-        nonlocal _t
-        F = len(frames)
-        association = None
-        if associate is not None:
-            _t = _tick('read', _t)
-            ids_all, kpp, pmask, association = assoc.associate_serial(eng, frames, extris, intris, **associate)
-            _t = _tick('associate', _t)
-        else:
-            ids_all, kpp, pmask = load_serial_people(frames, V)
-        col = {p: i for i, p in enumerate(ids_all)}
-        ids = [p for p in (ids_all if want is None else want) if p in col]
-        prob = [(f, p) for f in range(F) for p in ids if pmask[f, col[p]].any()]
-        empty = sorted(set(range(F)) - {f for f, _ in prob})
-        if empty:
-            warnings.warn('serial %s: frames %s list none of the persons %s in any view; skipped'
-                          % (serial, [frames[f][0] for f in empty], 'all' if want is None else want), RuntimeWarning)
-        if not prob:
-            return None
-        N = len(prob)
-        pf, pp = np.array([f for f, _ in prob]), np.array([p for _, p in prob])
-        kp = np.stack([kpp[f, col[p]] for f, p in prob])
-        vmask = np.stack([pmask[f, col[p]] for f, p in prob])
-        if save_images:
-            jobs = [(f, v, image_path(image_root, serial, cams[v], frames[f][0]), (serial, frames[f][0], cams[v]))
-                    for f in sorted(set(pf.tolist())) for v in range(V) if frames[f][1][v] is not None]
-        ex, it = np.asarray(extris[:V], np.float64), np.asarray(intris[:V], np.float64)
-        rig = (ex[:, :3, :3].astype(np.float32), ex[:, :3, 3].astype(np.float32),
-               it[:, 0, 0].astype(np.float32), it[:, :2, 2].astype(np.float32))
-        gt_xy = kp[..., :2].copy()
-        conf = kp[..., 2] * jw[None, None, :]
-        eng.set_problems(rig, gt_xy, conf)
-        _t = _tick('read', _t)
-        ann, has = np.zeros((N, 17, 4), np.float32), np.zeros(N, bool)
-        if use_3d:
-            j3p, hasp = load_serial_people3d(frames, ids_all)
-            ann = np.stack([j3p[f, col[p]] for f, p in prob])
-            has = np.array([hasp[f, col[p]] for f, p in prob])
-        if is_seq and has.any() and not has.all():
-            warnings.warn('serial %s: %d of %d problems carry no 3-D annotation; the is_seq chain runs on one objective - '
-                          'fitting the whole serial from the 2-D keypoints only' % (serial, int((~has).sum()), N))
-            has[:] = False
-        c3 = None
-        if has.any():
-            c3 = ann[:, :, 3].copy()
-            if not use_hip:
-                c3[:, 11] = c3[:, 12] = 0.0
-        scales = per_problem(fix_scale, pp, 1, 'fix_scale')
-        shapes = per_problem(fix_shape, pp, 10, 'fix_shape')
-        guess = {}
-
-        def guess_rows(rows, with_3d):
-            # one init_guess_batch per distinct fixed scale: one call when everybody shares it
-            groups = [rows] if scales is None else [rows[scales[rows, 0] == v_] for v_ in np.unique(scales[rows, 0])]
-            for g in groups:
-                if g.size < N:
-                    eng.set_problems(rig, gt_xy[g], conf[g])
-                r = init_guess_batch(eng, ex, it, kp[g], est_scale=scales is None,
-                                     fixed_scale=None if scales is None else float(scales[g[0], 0]),
-                                     joints3d=ann[g][:, :, :3].astype(np.float64) if with_3d else None,
-                                     view_mask=None if with_3d else vmask[g])
-                idx = torch.as_tensor(g, device=eng.device)
-                for k in ('global_orient', 'transl', 'scale', 'joints3d', 'rot'):
-                    if k not in guess:
-                        guess[k] = torch.zeros((N,) + tuple(r[k].shape[1:]), dtype=r[k].dtype, device=r[k].device)
-                    guess[k][idx] = r[k]
-                if g.size < N:
-                    eng.set_problems(rig, gt_xy, conf)
-        guess_rows(np.arange(N), bool(has.all()))
-        if has.any() and not has.all():
-            guess_rows(np.flatnonzero(has), True)
-        x0 = initial_params(guess, use_vposer)
-        if shapes is not None:
-            x0[:, 0:10] = torch.as_tensor(shapes, device=x0.device)
-        _t = _tick('init_guess', _t)
-        xf = torch.empty_like(x0)
-        final = torch.empty(N, device=eng.device)
-        ncl = torch.zeros(N, dtype=torch.int32, device=eng.device)
-        if is_seq:
-            # the persons are the sequences; a person's chain runs over the frames they are in
-            seq = sorted(set(pp.tolist()))
-            row = {p: s_ for s_, p in enumerate(seq)}
-            S = len(seq)
-            ps = np.array([row[p] for p in pp.tolist()])
-            present = np.zeros((S, F), bool)
-            present[ps, pf] = True
-            gt_s = np.zeros((S, F) + gt_xy.shape[1:], np.float32)
-            conf_s = np.zeros((S, F) + conf.shape[1:], np.float32)
-            gt_s[ps, pf], conf_s[ps, pf] = gt_xy, conf
-            x0_s = torch.zeros(S, F, x0.shape[1], dtype=x0.dtype, device=x0.device)
-            x0_s[torch.as_tensor(ps), torch.as_tensor(pf)] = x0
-            t3 = None
-            if has.all():
-                a3, c3_s = np.zeros((S, F, 17, 3), np.float32), np.zeros((S, F, 17), np.float32)
-                a3[ps, pf], c3_s[ps, pf] = ann[:, :, :3], c3
-                t3 = (a3, c3_s)
-            xs, st = fit_sequences(eng, rig, gt_s, conf_s, x0_s, stages_for(has.all()), joints3d=t3, present=present)
-            si, fi = torch.as_tensor(ps, device=xs.device), torch.as_tensor(pf, device=xs.device)
-            xf = xs[si, fi].to(x0.dtype)
-            final, ncl = st['final_loss'][si, fi], st['n_closure'][si, fi]
-            restarted = st['restarted'][ps, pf]
-            eng.set_problems(rig, gt_xy, conf)
-        else:
-            for sel, with_3d in ((np.flatnonzero(has), True), (np.flatnonzero(~has), False)):
-                if sel.size == 0:
-                    continue
-                if sel.size < N:
-                    eng.set_problems(rig, gt_xy[sel], conf[sel])
-                if with_3d:
-                    eng.set_joints3d(ann[sel][:, :, :3], c3[sel])
-                idx = torch.as_tensor(sel, device=eng.device)
-                xs_, st = eng.fit(x0[idx], stages_for(with_3d))
-                xf[idx], final[idx], ncl[idx] = xs_.to(xf.dtype), st['final_loss'].to(final.dtype), st['n_closure'].to(ncl.dtype)
-            if has.any() and not has.all():
-                eng.set_problems(rig, gt_xy, conf)
-            restarted = np.ones(N, bool)
-        _t = _tick('fit', _t)
-        scene_report = None
-        if scene_collision is not None:
-            # a frame is a scene (the problems are frame-major); all N problems are set again, with their 3-D targets only
-            # when every problem carries them (they were then fitted as one group and the targets are still in place)
-            sc = dict(scene_collision)
-            st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(sc.pop('weight')))
-            sizes = [int((pf == f).sum()) for f in sorted(set(pf.tolist()))]
-            xr, scene_report = refine_scenes(eng, xf, sizes, st_, **sc)
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(scene_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('refine', _t)
-        silhouette_report = None
-        if sil_cfg is not None:
-            xr, silhouette_report = refine_serial_silhouettes(eng, xf, stages_for(bool(has.all()))[-1], sil_cfg, serial, cams,
-                                                              frames, [(int(f), int(p)) for f, p in prob], rig, eng.nv)
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('silhouette', _t)
-        scan_report = None
-        if scan_cfg is not None:
-            xr, scan_report = refine_serial_scans(eng, xf, stages_for(bool(has.all()))[-1], scan_cfg, serial, cams, frames,
-                                                  [(int(f), int(p)) for f, p in prob], rig)
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(scan_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('scan', _t)
-        temporal_report = None
-        if tmp_cfg is not None:
-            # a person's track: frame_idx = position in the serial's frame list, so an absence breaks the chain
-            if has.all():
-                eng.set_joints3d(ann[:, :, :3], c3)
-            st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(tmp_cfg['weight']))
-            xr, temporal_report = smooth_sequences(eng, xf, st_, pp, pf, sweeps=int(tmp_cfg['sweeps']))
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('temporal', _t)
-        joint_report = None
-        if joint_cfg is not None:
-            # a frame is a scene (the problems are frame-major), a person id a track over the serial's frame list
-            if has.all():
-                eng.set_joints3d(ann[:, :, :3], c3)
-            sizes = [int((pf == f).sum()) for f in sorted(set(pf.tolist()))]
-            xr, joint_report = refine_serial_joint(eng, xf, stages_for(bool(has.all()))[-1], joint_cfg, serial, cams, frames,
-                                                   [(int(f), int(p)) for f, p in prob], rig, eng.nv, sizes, pp, pf)
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('joint', _t)
-        camera_report = cameras = None
-        if cam_cfg is not None:
-            xr, camera_report, cameras = refine_serial_cameras(eng, xf, stages_for(False)[-1], cam_cfg, serial, rig, gt_xy, conf,
-                                                               it, result_folder)
-            xf = xr.to(xf.dtype)
-            final = torch.as_tensor(camera_report['loss'], dtype=final.dtype, device=final.device)
-            _t = _tick('cameras', _t)
-        full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
-        xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
-        res = [iof.result_dict(xf_h[n], loss=final_h[n], body_pose_decoded=full[n, 3:] if use_vposer else None)
-               for n in range(N)]
-        files = [iof.save_result_pkl(result_folder, serial, frames[pf[n]][0], res[n], person_id=int(pp[n])) for n in range(N)]
-        if save_meshes or save_images:
-            xm = xf_h.copy()
-            xm[:, 13:82] = np.stack([r['body_pose'][0] for r in res])
-            verts_d, joints_d = eng.vertices(xm, flags=flags & ~_lib.F_VPOSER)
-        if save_meshes:
-            verts = verts_d.cpu().numpy()
-            for n in range(N):
-                d = os.path.join(mesh_folder or os.path.join(result_folder, 'meshes'), serial, frames[pf[n]][0])
-                os.makedirs(d, exist_ok=True)
-                iof.save_obj(os.path.join(d, '%03d.obj' % int(pp[n])), verts[n], model['faces'])
-        out = dict(frames=[fr[0] for fr in frames], params=xf_h, final_loss=final_h, n_closure=ncl.cpu().numpy(), files=files,
-                   init=x0.cpu().numpy(), restarted=restarted, used_3d=has.copy(), views_per_frame=vmask.sum(1),
-                   problem_frame=pf, problem_person=pp, persons=sorted(set(pp.tolist())))
-        if scene_report is not None:
-            out['scene_report'] = scene_report
-        if silhouette_report is not None:
-            out['silhouette_report'] = silhouette_report
-        if scan_report is not None:
-            out['scan_report'] = scan_report
-        if temporal_report is not None:
-            out['temporal_report'] = temporal_report
-        if joint_report is not None:
-            out['joint_report'] = joint_report
-        if association is not None:
-            out['association'] = association
-        if camera_report is not None:
-            out['camera_report'], out['cameras'] = camera_report, cameras
-        _t = _tick('write', _t)
-        if save_images:
-            palette = np.asarray(SCENE_PALETTE, np.float32)
-            scene = {f: (np.flatnonzero(pf == f).tolist(), palette[pp[pf == f] % 7]) for f in set(pf.tolist())}
-            out['images'] = render_serial_images(eng, verts_d, joints_d, jobs,
-                                                 image_folder or os.path.join(result_folder, 'images'), pool, scene=scene)
-            _t = _tick('render', _t)
-        return out
-    results = {}
     if save_images and image_root is None:
         image_root = os.path.join(os.path.dirname(os.path.normpath(keyp_root)), 'images')
     pool = ThreadPoolExecutor(max_workers=IO_WORKERS) if save_images else None
+    ctx = FitContext(eng=eng, model=model, extris=extris, intris=intris, jw=jw, flags=flags, use_vposer=vposer is not None,
+                     use_hip=use_hip, use_3d=use_3d, is_seq=is_seq, stages_for=stages_for, want=want, associate=associate,
+                     fix_scale=fix_scale, fix_shape=fix_shape, options=options, result_folder=result_folder,
+                     mesh_folder=(mesh_folder or os.path.join(result_folder, 'meshes')) if save_meshes else None,
+                     image_root=image_root,
+                     image_folder=(image_folder or os.path.join(result_folder, 'images')) if save_images else None,
+                     timing=timing, pool=pool, t=t0)
+    results = {}
     try:
-        _t = _tick('read', _t)
+        _tick(ctx, 'read')
         for serial, cams, frames in list_frames(keyp_root):
             V, F = len(cams), len(frames)
             if F == 0 or V < 1:
                 continue
             if V > len(extris):
                 raise ValueError('serial %s has %d camera folders, the camera file %s holds %d cameras' % (serial, V, cam_file, len(extris)))
-            if multi:
-                r_ = fit_people(serial, cams, frames, V)
-                if r_ is not None:
-                    results[serial] = r_
-                continue
-            kp, vmask = load_serial(frames, V, return_mask=True)
-            if save_images:
-                # the views that had a keypoint file in the frame (main.py:44-66); a missing image fails before the fit
-                jobs = [(f, v, image_path(image_root, serial, cams[v], frames[f][0]), (serial, frames[f][0], cams[v]))
-                        for f in range(F) for v in range(V) if frames[f][1][v] is not None]
-            if not vmask.any(1).all():
-                raise ValueError('serial %s: frames %s have no keypoint file in any camera folder'
-                                 % (serial, [frames[f][0] for f in np.flatnonzero(~vmask.any(1))]))
-            ex, it = np.asarray(extris[:V], np.float64), np.asarray(intris[:V], np.float64)
-            rig = (ex[:, :3, :3].astype(np.float32), ex[:, :3, 3].astype(np.float32),
-                   it[:, 0, 0].astype(np.float32), it[:, :2, 2].astype(np.float32))
-            gt_xy = kp[..., :2].copy()
-            conf = kp[..., 2] * jw[None, None, :]
-            eng.set_problems(rig, gt_xy, conf)
-            _t = _tick('read', _t)
-            # 3-D joint targets (non_linear_solver.py:86-99) and the initial alignment to them instead of the triangulation
-            # (init_guess.py:84-85) - decided PER FRAME like the reference (:68-69): frames with an annotation are fitted with
-            # the 3-D term, the others without it (two batched fits when a serial mixes both)
-            ann, has = (load_serial_joints3d(frames) if use_3d else (None, np.zeros(F, bool)))
-            if is_seq and has.any() and not has.all():
-                warnings.warn('serial %s: %d of %d frames carry no 3-D annotation; the is_seq chain runs on one objective - '
-                              'fitting the whole serial from the 2-D keypoints only' % (serial, int((~has).sum()), F))
-                has[:] = False
-            c3 = None
-            if has.any():
-                c3 = ann[:, :, 3].copy()
-                if not use_hip:
-                    c3[:, 11] = c3[:, 12] = 0.0
-            j3_all = ann[:, :, :3].astype(np.float64) if has.all() else None
-            guess = init_guess_batch(eng, ex, it, kp, est_scale=fix_scale is None, fixed_scale=fix_scale, joints3d=j3_all,
-                                     view_mask=vmask)
-            if has.any() and not has.all():
-                # annotated frames: aligned to their 3-D joints; the rest keep the triangulation / depth guess
-                sel = np.flatnonzero(has)
-                eng.set_problems(rig, gt_xy[sel], conf[sel])
-                g3 = init_guess_batch(eng, ex, it, kp[sel], est_scale=fix_scale is None, fixed_scale=fix_scale,
-                                      joints3d=ann[sel][:, :, :3].astype(np.float64))
-                idx = torch.as_tensor(sel, device=eng.device)
-                for k in ('global_orient', 'transl', 'scale', 'joints3d', 'rot'):
-                    guess[k][idx] = g3[k]
-                eng.set_problems(rig, gt_xy, conf)
-            x0 = initial_params(guess, use_vposer, fixed_shape=fix_shape)
-            _t = _tick('init_guess', _t)
-
-            if is_seq:
-                if has.all():
-                    eng.set_joints3d(ann[:, :, :3], c3)
-                t3 = (ann[None, :, :, :3], c3[None]) if has.all() else None
-                xs, st = fit_sequences(eng, rig, gt_xy[None], conf[None], x0[None], stages_for(has.all()), joints3d=t3)
-                xf, final, ncl = xs[0], st['final_loss'][0], st['n_closure'][0]
-                restarted = st['restarted'][0]
-                eng.set_problems(rig, gt_xy, conf)                  # back to the whole serial for the outputs below
-            else:
-                xf = torch.empty_like(x0)
-                final = torch.empty(F, device=eng.device)
-                ncl = torch.zeros(F, dtype=torch.int32, device=eng.device)
-                for sel, with_3d in ((np.flatnonzero(has), True), (np.flatnonzero(~has), False)):
-                    if sel.size == 0:
-                        continue
-                    if sel.size < F:
-                        eng.set_problems(rig, gt_xy[sel], conf[sel])
-                    if with_3d:
-                        eng.set_joints3d(ann[sel][:, :, :3], c3[sel])
-                    idx = torch.as_tensor(sel, device=eng.device)
-                    xs_, st = eng.fit(x0[idx], stages_for(with_3d))
-                    xf[idx], final[idx], ncl[idx] = xs_.to(xf.dtype), st['final_loss'].to(final.dtype), st['n_closure'].to(ncl.dtype)
-                if has.any() and not has.all():
-                    eng.set_problems(rig, gt_xy, conf)
-                restarted = np.ones(F, bool)
-            _t = _tick('fit', _t)
-            silhouette_report = None
-            if sil_cfg is not None:
-                xr, silhouette_report = refine_serial_silhouettes(eng, xf, stages_for(bool(has.all()))[-1], sil_cfg, serial, cams,
-                                                                  frames, [(f, None) for f in range(F)], rig, eng.nv)
-                xf = xr.to(xf.dtype)
-                final = torch.as_tensor(silhouette_report['loss'], dtype=final.dtype, device=final.device)
-                _t = _tick('silhouette', _t)
-            scan_report = None
-            if scan_cfg is not None:
-                xr, scan_report = refine_serial_scans(eng, xf, stages_for(bool(has.all()))[-1], scan_cfg, serial, cams, frames,
-                                                      [(f, None) for f in range(F)], rig)
-                xf = xr.to(xf.dtype)
-                final = torch.as_tensor(scan_report['loss'], dtype=final.dtype, device=final.device)
-                _t = _tick('scan', _t)
-            temporal_report = None
-            if tmp_cfg is not None:
-                if has.all():
-                    eng.set_joints3d(ann[:, :, :3], c3)
-                st_ = dict(stages_for(bool(has.all()))[-1], coll_loss_weight=float(tmp_cfg['weight']))
-                xr, temporal_report = smooth_sequences(eng, xf, st_, np.zeros(F, np.int64), np.arange(F),
-                                                       sweeps=int(tmp_cfg['sweeps']))
-                xf = xr.to(xf.dtype)
-                final = torch.as_tensor(temporal_report['loss'], dtype=final.dtype, device=final.device)
-                _t = _tick('temporal', _t)
-            joint_report = None
-            if joint_cfg is not None:
-                if has.all():
-                    eng.set_joints3d(ann[:, :, :3], c3)
-                xr, joint_report = refine_serial_joint(eng, xf, stages_for(bool(has.all()))[-1], joint_cfg, serial, cams, frames,
-                                                       [(f, None) for f in range(F)], rig, eng.nv, None, np.zeros(F, np.int64),
-                                                       np.arange(F))
-                xf = xr.to(xf.dtype)
-                final = torch.as_tensor(joint_report['loss'], dtype=final.dtype, device=final.device)
-                _t = _tick('joint', _t)
-            camera_report = cameras = None
-            if cam_cfg is not None:
-                xr, camera_report, cameras = refine_serial_cameras(eng, xf, stages_for(False)[-1], cam_cfg, serial, rig, gt_xy,
-                                                                   conf, it, result_folder)
-                xf = xr.to(xf.dtype)
-                final = torch.as_tensor(camera_report['loss'], dtype=final.dtype, device=final.device)
-                _t = _tick('cameras', _t)
-            full = eng.full_pose(xf, flags=flags & ~_lib.F_USE_3D).cpu().numpy()
-            xf_h, final_h = xf.cpu().numpy(), final.cpu().numpy()
-            res = [iof.result_dict(xf_h[f], loss=final_h[f], body_pose_decoded=full[f, 3:] if use_vposer else None)
-                   for f in range(F)]
-            files = [iof.save_result_pkl(result_folder, serial, frames[f][0], res[f]) for f in range(F)]
-            if save_meshes or save_images:
-                # the body of the SAVED parameters: zeroed feet / hands, model(global_orient, transl, body_pose, betas)
-                # (utils.py:866-874); its joints are the keypoints save_images draws
-                xm = xf_h.copy()
-                xm[:, 13:82] = np.stack([r['body_pose'][0] for r in res])
-                verts_d, joints_d = eng.vertices(xm, flags=flags & ~_lib.F_VPOSER)
-            if save_meshes:
-                verts = verts_d.cpu().numpy()
-                for f in range(F):
-                    d = os.path.join(mesh_folder or os.path.join(result_folder, 'meshes'), serial, frames[f][0])
-                    os.makedirs(d, exist_ok=True)
-                    iof.save_obj(os.path.join(d, '000.obj'), verts[f], model['faces'])
-            results[serial] = dict(frames=[fr[0] for fr in frames], params=xf_h, final_loss=final_h,
-                                   n_closure=ncl.cpu().numpy(), files=files, init=x0.cpu().numpy(), restarted=restarted,
-                                   used_3d=has.copy(), views_per_frame=vmask.sum(1))
-            if silhouette_report is not None:
-                results[serial]['silhouette_report'] = silhouette_report
-            if scan_report is not None:
-                results[serial]['scan_report'] = scan_report
-            if temporal_report is not None:
-                results[serial]['temporal_report'] = temporal_report
-            if joint_report is not None:
-                results[serial]['joint_report'] = joint_report
-            if camera_report is not None:
-                results[serial]['camera_report'], results[serial]['cameras'] = camera_report, cameras
-            _t = _tick('write', _t)
-            if save_images:
-                results[serial]['images'] = render_serial_images(
-                    eng, verts_d, joints_d, jobs, image_folder or os.path.join(result_folder, 'images'), pool)
-                _t = _tick('render', _t)
+            sp = (persons_problems if multi else single_person_problems)(ctx, serial, cams, frames)
+            if sp is not None:
+                results[serial] = fit_serial(ctx, sp)
     finally:
         if pool is not None:
             pool.shutdown()
-        if own:
+        if engine is None:
             eng.close()
     return results
 
 
-__all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'image_path', 'render_serial_images', 'POSE_FORMATS',
+__all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_people3d', 'fit_folder', 'fit_serial', 'SerialProblems',
+           'FitContext', 'single_person_problems', 'persons_problems', 'check_scene_collision', 'image_path', 'render_serial_images', 'POSE_FORMATS',
            'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes',
            'check_joint', 'load_serial_masks', 'refine_serial_joint', 'check_refine_cameras', 'refine_serial_cameras',
            'check_scans', 'scan_path', 'subsample_rows', 'load_serial_scans', 'refine_serial_scans']
