@@ -1041,6 +1041,25 @@ __device__ __forceinline__ double loss_combine(const DevModel& M, ClosureLds& L,
     return total;
 }
 
+// a workgroup-uniform count behind an opaque copy: what is compared against it is compared again where it is used and is
+// not hoisted out of the round loop (loss_and_keypoint_grad: the selects of the view sums)
+__device__ __forceinline__ int opaque_uniform(int n) {
+    asm volatile("" : "+s"(n));
+    return n;
+}
+// sum of the first n (1 <= n <= N <= MVFIT_MAX_VIEWS) views' parts of one keypoint word, ascending from +0: N loads at
+// unconditional addresses, then the selects, then N adds (loss_and_keypoint_grad says why a selected +0 changes no word)
+template <int N>
+__device__ __forceinline__ float view_sum(const float* part, int n) {
+    float r[N];
+#pragma unroll
+    for (int vv = 0; vv < N; ++vv) r[vv] = part[vv * (NKP * 3)];
+    float s = 0.f + r[0];                                  // (there is no problem without a view: mvfit_set_problems)
+#pragma unroll
+    for (int vv = 1; vv < N; ++vv) s += vv < n ? r[vv] : 0.f;
+    return s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // E4: SMPLifyLoss.forward (fitting.py:290-415, no SDF term) + gradient w.r.t. keypoints / priors.
 // Returns the total loss (same value in every thread).  Ends with __syncthreads.
@@ -1188,20 +1207,61 @@ __device__ __forceinline__ double loss_and_keypoint_grad(const DevModel& M, Clos
     double total = 0.0;
     if constexpr (!DEFER) total = loss_combine<false>(M, L, V, W, tid == 0);
     const bool use_3d = (W.flags & MVFIT_F_USE_3D) != 0;
+    // The sums below are taken over a count only known at run time (V views, ndw waves), in ascending order.  Written as
+    // `if (vv < V) s += part[vv]` each term became a basic block of its own - branch, one LDS read, a full wait, the add -
+    // behind a predicate hoisted out of the round loop and spilled: V serialised LDS round trips on the wave every other
+    // wave waits for.  Now: every row the array has is read first, at unconditional addresses (rows >= V hold whatever LDS
+    // held and never enter arithmetic), then selected - `vv < V ? value : 0.f` -, then added in the same order on the same
+    // lane.  No word changes: the running sum starts at +0 and in round-to-nearest a sum is -0 only when both addends are
+    // -0, so s is never -0 and s + (+0) is s bit for bit; the first add, 0.f + p0, stays and still turns a -0 part into +0.
+    // (E6's cells and the no-wrap triangular products rest on the same argument.)  The count is made opaque once per call:
+    // the selects' predicates are then compared where they are used, not kept - sixteen SGPR pairs - across the round.
+#ifdef MVFIT_DEBUG_HOOKS
+    const bool sums_serial = (__builtin_amdgcn_readfirstlane(L.M.stream_late) & 4) != 0;   // the test's switch: the loops as they were
+#else
+    constexpr bool sums_serial = false;
+#endif
     if (want_grad && tid < 3) {
         float s = 0.f;
-        for (int w = 0; w < ndw; ++w) s += L.red_f[w][tid];
-        if (use_3d) for (int k = 0; k < NKP; ++k) s += L.gkp3[k][tid];
+        if (sums_serial) {
+            for (int w = 0; w < ndw; ++w) s += L.red_f[w][tid];
+            if (use_3d) for (int k = 0; k < NKP; ++k) s += L.gkp3[k][tid];
+        } else {
+            constexpr int NDW_MAX = (MVFIT_MAX_VIEWS * NKP + 63) >> 6;
+            static_assert(NDW_MAX <= STEP_NW, "red_f has a row per wave");
+            const int n = opaque_uniform(ndw);
+            float r[NDW_MAX];
+#pragma unroll
+            for (int w = 0; w < NDW_MAX; ++w) r[w] = L.red_f[w][tid];
+            s += r[0];                                                         // (V >= 1: wave 0 always holds data-term threads)
+#pragma unroll
+            for (int w = 1; w < NDW_MAX; ++w) s += w < n ? r[w] : 0.f;
+            if (use_3d) {                                                      // uniform: one batch of NKP loads
+                float q[NKP];
+#pragma unroll
+                for (int k = 0; k < NKP; ++k) q[k] = L.gkp3[k][tid];
+#pragma unroll
+                for (int k = 0; k < NKP; ++k) s += q[k];
+            }
+        }
         L.gtau[tid] = s;                                                       // g_tau = sum_k g_kp
     }
     if (want_grad && tid >= 64 && tid < 64 + NKP * 3) {
-        // g_kp[k][a] = sum over views, ascending (independent loads; the adjoint's first phase reads it
-        // after its own barrier)
+        // g_kp[k][a] = sum over views, ascending (the adjoint's first phase reads it after its own barrier)
         const int i = tid - 64;
+        const float* part = &L.gkp_part[0][0][0] + i;
         float s = 0.f;
+        if (sums_serial) {
 #pragma unroll
-        for (int vv = 0; vv < MVFIT_MAX_VIEWS; ++vv) if (vv < V) s += (&L.gkp_part[vv][0][0])[i];
-        if (use_3d) s += (&L.gkp3[0][0])[i];
+            for (int vv = 0; vv < MVFIT_MAX_VIEWS; ++vv) if (vv < V) s += part[vv * (NKP * 3)];
+            if (use_3d) s += (&L.gkp3[0][0])[i];
+        } else {
+            const int n = opaque_uniform(V);
+            const float p3 = (&L.gkp3[0][0])[i];                               // (selected away without use_3d)
+            if (n <= MVFIT_MAX_VIEWS / 2) s = view_sum<MVFIT_MAX_VIEWS / 2>(part, n);   // uniform: a batch of 8 or of 16
+            else s = view_sum<MVFIT_MAX_VIEWS>(part, n);
+            if (use_3d) s += p3;
+        }
         (&L.gkp[0][0])[i] = s;
     }
     return total;

@@ -95,7 +95,8 @@ struct ModelLds {
     // else reads in that case (the image itself always holds the dense wT)
     // stream_late: always 0 in the image the host builds; the -DMVFIT_DEBUG_HOOKS build sets bit 0 on request (MVFIT_BWD_STREAM_LATE)
     // and only that build's kernels read it: every wave of the adjoint's transposed stream then loads inside E7; bit 1
-    // (MVFIT_FWD_STREAM_LATE): every wave of the forward stream loads inside E2
+    // (MVFIT_FWD_STREAM_LATE): every wave of the forward stream loads inside E2; bit 2 (MVFIT_VIEW_SUMS_SERIAL): E4 sums the
+    // views' keypoint gradients and g_tau's parts in loops of conditional reads, the form before the batched loads
     int sel_sparse, e6_cells, stream_late, spad2;
 };
 constexpr int E6_NZ = 4;                                // padded entries per E6 cell

@@ -52,6 +52,7 @@ static void upload_model(mvfit_ctx* c, const HostModel& h) {
         if (debug_hook("MVFIT_E6_DENSE") != 0) lds.e6_cells = 0;          // (hooks build only) E6 on the dense rows of wT
         if (debug_hook("MVFIT_BWD_STREAM_LATE") != 0) lds.stream_late |= 1;   // (hooks build only) E7's stream loads in-slot on every wave
         if (debug_hook("MVFIT_FWD_STREAM_LATE") != 0) lds.stream_late |= 2;   // (hooks build only) E2's forward stream likewise
+        if (debug_hook("MVFIT_VIEW_SUMS_SERIAL") != 0) lds.stream_late |= 4;  // (hooks build only) E4's view sums as loops of conditional reads
         memcpy(img.data(), &lds, sizeof(ModelLds));
         memcpy(img.data() + sizeof(ModelLds), h.e6_cells.data(), std::min<size_t>(h.e6_cells.size() * 2, NJ * E6_ROW_BYTES));
         M.mlds = reinterpret_cast<const ModelLds*>(dev_upload(c, img));
