@@ -668,6 +668,59 @@ int mvfit_scan_loss(mvfit_ctx* ctx, const float* vertices, int num_bodies, float
  * the state as it was. */
 int mvfit_set_scan_term(mvfit_ctx* ctx, int enable, float w_s2m, float w_m2s, float sigma);
 
+/* ---- Surface landmark term: named points of the body's surface against the pixels they were seen at and against measured
+ * 3-D positions, with the gradient on the vertices (csrc/landmark.hip).  The reference has no such term (its body model
+ * knows foot keypoints as surface vertices, its fitter drops the detector's foot points): this contract is the project's own.
+ *
+ * mvfit_set_landmarks keeps the landmark table, once per ctx and independent of the problems: 1 <= L <= MVFIT_LANDMARKS_MAX
+ * landmarks, each an affine combination of up to MVFIT_LANDMARK_NNZ vertices, vertex_ids[L,4] int32 and weights[L,4] float32
+ * (host).  A slot of weight 0 is never read and its id may be anything; every other slot has an id in [0, Nv) and a finite
+ * weight, else MVFIT_E_ARG (the table in place stays).  Landmark l lies at p_l = sum_k w_lk V[vid_lk], in fp32 from 0 in
+ * ascending k.  L = 0 or a NULL pointer clears the table, the targets and the term; so does a new table (the
+ * targets belong to the table they were set for).
+ *
+ * mvfit_set_landmark_targets copies the targets of the current batch (B and V of mvfit_set_problems, whose cameras the term
+ * uses): xy[B,V,L,2], conf[B,V,L] and, both or neither, xyz[B,L,3], conf3[B,L] (device or host).  Every confidence is finite
+ * and >= 0 (MVFIT_E_ARG, the set in place stays); an entry of confidence 0 is never read and may hold NaN.  A second set at
+ * the same (B, V, L, with or without 3-D) keeps every buffer address, so a captured round graph stays valid.  xy = NULL
+ * clears the targets and switches the term off.  MVFIT_E_STATE without a table or without mvfit_set_problems;
+ * mvfit_set_problems with another B or V clears the targets and the term and keeps the table.
+ *
+ * mvfit_landmark_loss evaluates at vertices[B,Nv,3] (device): loss[B] and, unless NULL, g_vertices[B,Nv,3] (device).
+ *   L_b = sum_v sum_l conf_bvl^2 (g(u_bvlx - xy_bvlx; rho) + g(u_bvly - xy_bvly; rho))
+ *       + sum_l w3d conf3_bl^2 ((g(p_blx - xyz_blx; rho3d) + g(p_bly - xyz_bly; rho3d)) + g(p_blz - xyz_blz; rho3d)),
+ *   g(r; s) = s^2 r^2 / (r^2 + s^2) for s > 0 (the reference's GMoF, utils/utils.py:435-438), r^2 for s == 0,
+ *   u = f (R p + t)_xy / (R p + t)_z + c in fp32 exactly as the closure's keypoint term computes it (no rule about depth:
+ * bodies are in front of their cameras).  There is no data_weight inside.  Each item is an fp32 value; the items of a lane
+ * are added in float64 in ascending (v, l), the 3-D items after them, the lanes through a fixed reduction network, and the
+ * total is rounded to fp32 once.  The gradient is dense: a landmark's point gradient sums its views in ascending order, then
+ * the 3-D part; a vertex's gradient sums w_lk g_l over its (landmark, slot) entries in ascending order; rows of vertices no
+ * landmark uses are written as zero, whatever the buffer held.  No atomics: a problem's bits are the same alone, in any
+ * batch, at any buffer alignment and from run to run; a problem whose confidences are all zero gets L = 0 and an exactly zero
+ * gradient.  MVFIT_E_STATE without a table or targets; MVFIT_E_ARG for a null vertices or loss and for a negative or
+ * non-finite rho, w3d or rho3d. */
+#define MVFIT_LANDMARKS_MAX 256
+#define MVFIT_LANDMARK_NNZ 4
+int mvfit_set_landmarks(mvfit_ctx* ctx, int L, const int32_t* vertex_ids, const float* weights);
+int mvfit_set_landmark_targets(mvfit_ctx* ctx, const float* xy, const float* conf, const float* xyz, const float* conf3);
+int mvfit_landmark_loss(mvfit_ctx* ctx, const float* vertices, float rho, float w3d, float rho3d, float* loss, float* g_vertices);
+
+/* The landmark loss as a term of the fit (enable != 0; 0 switches it off and ignores the scalars).  While it is on, a weight
+ * set with coll_loss_weight = w > 0 adds w^2 * L_j to problem j, L_j exactly loss[j] of mvfit_landmark_loss(rho, w3d, rho3d)
+ * at the trial point's vertices; its gradient is w^2 times the pull-back of that call's g_vertices through the fp32 model
+ * (the adjoint mvfit_vertices_backward computes).  The form, the record and the L < FLT_MIN rule are the silhouette term's:
+ * a problem whose confidences are all zero keeps the loss and gradient bits it has without the term.
+ * mvfit_closure and mvfit_fit both honour the term.  mvfit_fit runs the stages that carry it as chained rounds (pass ->
+ * landmark kernel -> dense pull-back -> record -> step kernel, the term's kernel skipping finished problems); stages without
+ * it in front keep their single-launch phase.  MVFIT_F_SPARSE_VERTS is ignored while the term is active.
+ * mvfit_sdf_term_read returns L_j in sums; samples: MVFIT_E_UNSUPPORTED.  The targets may be replaced while the term is on;
+ * the captured round graph is kept when their sizes are the same.  The round's buffers are the vertex-target term's.
+ * One term slot per ctx: MVFIT_E_STATE while mvfit_set_sdf's term, scene obstacles, the silhouette term, the vertex-target
+ * term, the scan term or the term mix are configured (and those setters return it while this term is on; the term takes no
+ * share of the mix).  MVFIT_E_STATE also without targets.  MVFIT_E_ARG for a negative or non-finite scalar.  A refused call
+ * leaves the state as it was. */
+int mvfit_set_landmark_term(mvfit_ctx* ctx, int enable, float rho, float w3d, float rho3d);
+
 /* ---- Term mix: the scene, silhouette, vertex-target and scan terms together behind coll_loss_weight ----
  * With the mix on, a weight set with coll_loss_weight = w > 0 adds to problem j
  *   pen_j = w^2 * (scene * S_sc^2 + silhouette * L_sil + vertex_targets * L_vt + scan * L_scan),

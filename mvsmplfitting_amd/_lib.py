@@ -94,7 +94,8 @@ EXPORTS = ['mvfit_create', 'mvfit_destroy', 'mvfit_last_error', 'mvfit_sync', 'm
            'mvfit_silhouette_hidden', 'mvfit_round_graph_info', 'mvfit_set_vertex_targets', 'mvfit_vertex_target_loss', 'mvfit_set_vertex_target_term',
            'mvfit_set_term_mix', 'mvfit_term_mix_read', 'mvfit_term_mix_cotangent', 'mvfit_term_mix_merge',
            'mvfit_term_mix_read4', 'mvfit_term_mix_cotangent3',
-           'mvfit_camera_normal_eqs', 'mvfit_refine_cameras', 'mvfit_set_scans', 'mvfit_scan_loss', 'mvfit_set_scan_term']
+           'mvfit_camera_normal_eqs', 'mvfit_refine_cameras', 'mvfit_set_scans', 'mvfit_scan_loss', 'mvfit_set_scan_term',
+           'mvfit_set_landmarks', 'mvfit_set_landmark_targets', 'mvfit_landmark_loss', 'mvfit_set_landmark_term']
 
 
 def load(path=None):
@@ -204,6 +205,14 @@ def load(path=None):
     lib.mvfit_scan_loss.restype = C.c_int
     lib.mvfit_set_scan_term.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
     lib.mvfit_set_scan_term.restype = C.c_int
+    lib.mvfit_set_landmarks.argtypes = [vp, C.c_int, _ip, _fp]
+    lib.mvfit_set_landmarks.restype = C.c_int
+    lib.mvfit_set_landmark_targets.argtypes = [vp, vp, vp, vp, vp]
+    lib.mvfit_set_landmark_targets.restype = C.c_int
+    lib.mvfit_landmark_loss.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float, vp, vp]
+    lib.mvfit_landmark_loss.restype = C.c_int
+    lib.mvfit_set_landmark_term.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.mvfit_set_landmark_term.restype = C.c_int
     lib.mvfit_set_term_mix.argtypes = [vp, C.POINTER(TermMix)]
     lib.mvfit_set_term_mix.restype = C.c_int
     lib.mvfit_term_mix_read.argtypes = [vp, vp]

@@ -48,6 +48,7 @@ from .joint_refine import refine_joint
 from .temporal import smooth_sequences
 from .scan import points_from_depth
 from .scan import refine_fit as scan_refine_fit
+from . import landmarks as lmk
 
 
 # pose format -> the model kind whose joint tensor it maps (reference code/utils/utils.py:441-457 smpl_to_annotation)
@@ -485,6 +486,98 @@ def refine_serial_scans(eng, xf, stage, cfg, serial, cams, frames, problems, rig
     return out, dict(report, points=count.copy())
 
 
+LANDMARK_DEFAULTS = dict(table=None, rho=100.0)
+
+
+def check_landmarks(landmarks, num_verts, is_seq=False, scene_collision=None, silhouettes=None, temporal=None, scans=None, joint=None,
+                    refine_cameras=None):
+    """fit_folder's ``landmarks`` option with the defaults filled in and the table loaded (landmarks.load_table), or
+    ValueError."""
+    if not isinstance(landmarks, dict) or 'weight' not in landmarks or landmarks.get('table') is None:
+        raise ValueError("landmarks: a dict with at least 'weight' (the term's coll_loss_weight, against pixels squared) and "
+                         "'table' (a landmark table file or dict)")
+    unknown = set(landmarks) - set(LANDMARK_DEFAULTS) - {'weight'}
+    if unknown:
+        raise ValueError('landmarks: unknown keys %s' % sorted(unknown))
+    if is_seq:
+        raise ValueError('landmarks is not available with is_seq=True')
+    if refine_cameras is not None:
+        raise ValueError('refine_cameras with landmarks is not built')
+    for name, single in (('scene_collision', scene_collision), ('silhouettes', silhouettes), ('temporal', temporal), ('scans', scans),
+                         ('joint', joint)):
+        if single is not None:
+            raise ValueError('landmarks and %s both use the fit\'s one term slot: choose one (the landmark term takes no share of the '
+                             'term mix)' % name)
+    cfg = dict(LANDMARK_DEFAULTS, **landmarks)
+    if not float(cfg['weight']) > 0.0 or not np.isfinite(float(cfg['weight'])):
+        raise ValueError('landmarks: weight must be > 0')
+    if not np.isfinite(float(cfg['rho'])) or float(cfg['rho']) < 0.0:
+        raise ValueError('landmarks: rho must be finite and >= 0')
+    table = lmk.load_table(cfg['table'])
+    if (table['keypoint_index'] < 0).any():
+        raise ValueError('landmarks: every landmark of the table needs a keypoint_index (its row of pose_keypoints_2d)')
+    ids = table['vertex_ids'][table['weights'] != 0]
+    if (ids >= int(num_verts)).any():
+        raise ValueError('landmarks: the table names vertex %d, the model has %d vertices' % (int(ids.max()), int(num_verts)))
+    cfg['table'] = table
+    return cfg
+
+
+def load_serial_landmarks(table, frames, problems, num_views, association=None):
+    """The landmark targets of one serial's problems from the keypoint files the 17 keypoints came from: (xy [N,V,L,2], conf
+    [N,V,L]) float32 with the rows table['keypoint_index'] of ``pose_keypoints_2d`` (io_formats.read_people_extra).  A problem
+    (frame, person) follows the entry the keypoints follow: persons=0 (person None) the first entry of every file, persons=
+    the entry with that id by read_people's rule, associate= (``association``: associate_serial's report) the detection the
+    track holds in that view."""
+    rows = table['keypoint_index']
+    L = len(rows)
+    by_index = association is not None or any(p is None for _, p in problems)
+    files = {}
+
+    def people(f, v):
+        if (f, v) not in files:
+            path = frames[f][1][v] if v < len(frames[f][1]) else None
+            files[(f, v)] = iof.read_people_extra(path, rows, by_index=by_index) if path is not None else {}
+        return files[(f, v)]
+
+    per_problem_rows = []
+    for f, person in problems:
+        views = []
+        for v in range(num_views):
+            entry = 0 if person is None else person
+            if association is not None:
+                k = np.flatnonzero(association['track_ids'][f, v] == person)
+                entry = int(association['slot'][f, v, k[0]]) if k.size else None
+            views.append(people(f, v).get(entry) if entry is not None else None)
+        per_problem_rows.append(views)
+    return lmk.targets_from_people(per_problem_rows, L)
+
+
+def refine_serial_landmarks(eng, xf, stage, cfg, frames, problems, num_views, association=None):
+    """The landmark refinement of one serial's fitted problems (landmarks.refine_fit: the landmark term inside the engine's
+    fit) against the targets of load_serial_landmarks, with coll_loss_weight = cfg['weight'].  A problem without a live
+    target keeps its row exactly; a serial without one is not refitted at all (report['loss'] is None: the fit's own losses
+    stand).  Returns (params, report): refine_fit's report plus targets = the live entries per problem; the engine is left
+    without table, targets and term."""
+    table = cfg['table']
+    xy, conf = load_serial_landmarks(table, frames, problems, num_views, association)
+    live = (conf > 0).reshape(len(problems), -1).sum(axis=1)
+    if not live.any():
+        return xf, dict(accepted=np.zeros(len(problems), bool), targets=live, loss=None)
+    eng.set_landmarks(table['vertex_ids'], table['weights'])
+    try:
+        eng.set_landmark_targets(xy, conf)
+        out, report = lmk.refine_fit(eng, xf, dict(stage, coll_loss_weight=float(cfg['weight'])), rho=float(cfg['rho']))
+    finally:
+        eng.clear_landmarks()
+    for j in np.flatnonzero(live == 0):
+        out[int(j)] = xf[int(j)]
+        report['accepted'][j] = False
+        report['after'][j] = report['loss'][j] = report['before'][j]
+        report['landmark_after'][j] = report['landmark_before'][j]
+    return out, dict(report, targets=live)
+
+
 def silhouette_workspace_bytes(M, H, W, Nv):
     """The mask set's workspace of include/mvfit.h (mvfit_set_silhouettes), without the contour lists."""
     return M * H * W * 5 + M * H * 4 + M * (16 * Nv + 8 * -(-Nv // 256) + 92) + 8
@@ -784,6 +877,10 @@ def serial_refinements(ctx, sp, rig, gt_xy, conf, intris, has):
     if o['scans'] is not None:
         table.append(('scans', 'scan', 'scan_report', False,
                       lambda eng, xf, sp: refine_serial_scans(eng, xf, last(), o['scans'], sp.serial, sp.cams, sp.frames, problems, rig)))
+    if o['landmarks'] is not None:
+        table.append(('landmarks', 'landmark', 'landmark_report', False,
+                      lambda eng, xf, sp: refine_serial_landmarks(eng, xf, last(), o['landmarks'], sp.frames, problems, sp.V,
+                                                                  sp.association)))
     if o['temporal'] is not None:
         table.append(('temporal', 'temporal', 'temporal_report', True,
                       lambda eng, xf, sp: smooth_sequences(eng, xf, dict(last(), coll_loss_weight=float(o['temporal']['weight'])),
@@ -905,7 +1002,8 @@ def fit_serial(ctx, sp):
             eng.set_joints3d(ann[:, :, :3], c3)
         xr, report, *extra = run(eng, xf, sp)
         xf = xr.to(xf.dtype)
-        final = torch.as_tensor(report['loss'], dtype=final.dtype, device=final.device)
+        if report['loss'] is not None:                      # (None: the refinement had nothing to do - the fit's own losses stand)
+            final = torch.as_tensor(report['loss'], dtype=final.dtype, device=final.device)
         reports[result_key] = report
         if extra:
             reports['cameras'] = extra[0]
@@ -952,7 +1050,7 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                pose_format='lsp14', use_hip=True, use_3d=False, fix_scale=None, fix_shape=None, save_meshes=False,
                mesh_folder=None, device=0, stages=None, engine: MvFit | None = None, timing: dict | None = None,
                save_images=False, image_root=None, image_folder=None, persons=0, scene_collision=None, associate=None,
-               silhouettes=None, temporal=None, joint=None, refine_cameras=None, scans=None):
+               silhouettes=None, temporal=None, joint=None, refine_cameras=None, scans=None, landmarks=None):
     """Fits every frame under keyp_root and writes the reference's result files.  Returns
     {serial: dict(frames, params [F,118], final_loss [F], n_closure [F], files [F], init [F,118], restarted [F]:
     frames fitted from their own initial guess - all of them unless is_seq, used_3d [F]: frames fitted with the 3-D joint
@@ -1039,6 +1137,17 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
     (refine_fit's, plus points = the count per problem), ``timing`` a 'scan' entry, and ``final_loss`` is the refined
     objective.  Inside ``joint``, ``scans=dict(share=..., root= | depth_root=, ...)`` with the same keys is a fourth part: at
     least two of the four.
+    landmarks: None, or dict(weight=..., table=..., rho=100.0) - after the serial's batched keypoint fit its problems are
+    refined against the points of the SAME keypoint files that the 17-row readers drop, by landmarks.refine_fit (the surface
+    landmark term inside the engine's fit) with the last stage's weights plus coll_loss_weight = weight (against pixels
+    squared); a problem keeps the refined row only if its objective fell.  ``table``: a landmark table file or dict
+    (landmarks.load_table) whose keypoint_index names each landmark's row of ``pose_keypoints_2d`` - for AlphaPose Halpe-26
+    the six foot points are rows 20-25.  A problem follows the entry its 17 keypoints follow (persons=0 the first entry,
+    persons= the id, associate= the track's detection); files with fewer rows give no targets, and a serial without any is
+    not refitted: its results are those of the call without the option, bit for bit.  ValueError before any engine is
+    created for unknown keys, weight <= 0, is_seq, a vertex id outside the model, and next to scene_collision, silhouettes,
+    temporal, scans, joint or refine_cameras.  The serial's result gains ``landmark_report`` (refine_fit's, plus targets =
+    the live entries per problem) and ``timing`` a 'landmark' entry.
     refine_cameras: None, or dict(sweeps=2, anchor=0, free='extrinsics', min_points=34) - after the serial's batched fit the
     rig is refined against the fitted bodies of the serial's whole batch and the bodies are refitted under it, with the last
     stage (calibrate.refine_rig; anchor: the view kept as the camera file gives it, or None).  Single-person and persons=
@@ -1069,7 +1178,9 @@ def fit_folder(model: dict, keyp_root, cam_file, result_folder, *, vposer=None, 
                if scans is not None else None),
         joint=check_joint(joint, is_seq, multi, scene_collision, silhouettes, temporal, scans) if joint is not None else None,
         refine_cameras=(check_refine_cameras(refine_cameras, is_seq, use_3d, scene_collision, silhouettes, temporal, joint, scans)
-                        if refine_cameras is not None else None))
+                        if refine_cameras is not None else None),
+        landmarks=(check_landmarks(landmarks, model['v_template'].shape[0], is_seq, scene_collision, silhouettes, temporal, scans, joint,
+                                   refine_cameras) if landmarks is not None else None))
     if associate is not None and associate is not False:
         if not multi:
             raise ValueError('associate finds the persons of a serial: it needs persons= a list of track ids or \'all\'')
@@ -1141,4 +1252,5 @@ __all__ = ['list_frames', 'load_serial', 'load_serial_people', 'load_serial_peop
            'FitContext', 'single_person_problems', 'persons_problems', 'check_scene_collision', 'image_path', 'render_serial_images', 'POSE_FORMATS',
            'check_silhouettes', 'check_temporal', 'mask_path', 'silhouette_workspace_bytes', 'refine_serial_silhouettes',
            'check_joint', 'load_serial_masks', 'refine_serial_joint', 'check_refine_cameras', 'refine_serial_cameras',
-           'check_scans', 'scan_path', 'subsample_rows', 'load_serial_scans', 'refine_serial_scans']
+           'check_scans', 'scan_path', 'subsample_rows', 'load_serial_scans', 'refine_serial_scans',
+           'check_landmarks', 'load_serial_landmarks', 'refine_serial_landmarks']

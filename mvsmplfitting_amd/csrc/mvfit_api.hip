@@ -126,6 +126,10 @@ TermInputs mvfit::term_inputs(const mvfit_ctx* c) {
     in.scan.on = Z.on; in.scan.term = zt.on; in.scan.ws = Z.ws.get(); in.scan.N = Z.N; in.scan.Pmax = Z.Pmax; in.scan.nf = Z.nf; in.scan.ns = Z.ns;
     in.scan.faces = c->d_faces; in.scan.w_s2m = zt.w_s2m; in.scan.w_m2s = zt.w_m2s; in.scan.sigma = zt.sigma;
     in.scan.g_verts = zt.g_verts; in.scan.loss = zt.loss; in.scan.part = zt.part;
+    const LmState& lm = c->lm;
+    in.lm.on = lm.on; in.lm.term = lm.term; in.lm.tab = lm.tab; in.lm.tgt = lm.tgt; in.lm.L = lm.L; in.lm.nt = lm.nt; in.lm.has3d = lm.has3d;
+    in.lm.rho = lm.rho; in.lm.w3d = lm.w3d; in.lm.rho3d = lm.rho3d;
+    in.lm.g_verts = lm.g_verts; in.lm.loss = lm.loss; in.lm.part = lm.part;
     return in;
 }
 
@@ -246,6 +250,15 @@ void mvfit::free_scan_term(mvfit_ctx* c) {
     c->scant = ScanTerm{};
 }
 
+void mvfit::free_landmark_targets(mvfit_ctx* c) {
+    c->lmtgt_mem.release();
+    c->lmterm_mem.release();
+    LmState& S = c->lm;
+    S.on = S.term = S.has3d = false;
+    S.tgt_L = 0;
+    S.tgt = S.g_verts = S.loss = S.part = nullptr;
+}
+
 void mvfit::free_vertex_targets(mvfit_ctx* c) {
     c->vtgt_mem.release();
     c->vtterm_mem.release();
@@ -269,6 +282,7 @@ static void free_problem_buffers(mvfit_ctx* c) {
     free_vertex_targets(c);             // and so do the vertex targets and their term
     free_term_mix(c);                   // and the term mix
     free_scan_term(c);                  // and the scan term (the scan set is not tied to the batch: it stays)
+    free_landmark_targets(c);           // and the landmark targets with their term (the table stays too)
 }
 
 extern "C" void mvfit_destroy(mvfit_ctx* c) {
@@ -371,6 +385,8 @@ extern "C" int mvfit_set_sdf(mvfit_ctx* c, const int32_t* faces, int num_faces, 
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->scant.on && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the scan term uses the ctx's term slot: switch it off first");
+    if (c->lm.term && faces && num_faces != 0)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the landmark term uses the ctx's term slot: switch it off first");
     if (c->mix.on && faces && num_faces != 0)
         return fail(c, MVFIT_E_STATE, "mvfit_set_sdf: the term mix uses the ctx's term slot (the one-person term is not part of it): switch it off first");
     HIP_OK(c, hipSetDevice(c->device));
@@ -458,9 +474,9 @@ bool mvfit::pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi) {
 
 // the interpenetration term of a chained round behind its vertex pass: the steps of its plan (round_term.cpp decides which), each
 // one launch on the round's stream with no host work.  Everything a launcher takes is in the plan, but the model, the pose
-// operands and what the round itself brings: its vertices, gate, stream and the pass's tile keys of the box.
-hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, ScanState& scan, std::string& err,
-                              const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
+// operands, the problems' cameras (the landmark term projects with them; a new batch drops the graph) and what the round itself brings: its vertices, gate, stream and the pass's tile keys of the box.
+hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, const DevProblems& Q, SilState& sil, ScanState& scan,
+                              std::string& err, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part) {
     const int B = plan.B, nv = plan.nv;
     hipError_t e = hipSuccess;
     for (int i = 0; i < plan.n && e == hipSuccess; ++i) {
@@ -479,6 +495,11 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
         case STEP_SCAN_EVAL:
             if (scan_round(scan, s.scan.faces, verts, s.scan.w_s2m, s.scan.w_m2s, s.scan.sigma, gate, s.scan.loss, s.scan.g_verts, st, err))
                 e = hipErrorLaunchFailure;
+            break;
+        case STEP_LM_EVAL:
+            e = launch_landmarks(verts, nv, B, s.lm.tab, s.lm.L, s.lm.nt, s.lm.tgt, s.lm.has3d != 0,
+                                 LmCams{Q.V, Q.cam_batched, Q.cam_R, Q.cam_t, Q.cam_f, Q.cam_c}, s.lm.rho, s.lm.w3d, s.lm.rho3d, gate, s.lm.loss,
+                                 s.lm.g_verts, st);
             break;
         case STEP_PULLBACK:
             e = launch_silhouette_pullback(M, P, B, plan.Bpad, gate, s.pull.g_verts, s.pull.loss, s.pull.part, s.pull.rec, st);
@@ -503,7 +524,7 @@ hipError_t mvfit::launch_term(const RoundTermPlan& plan, const DevModel& M, cons
 }
 
 int mvfit::run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st) {
-    const hipError_t e = launch_term(plan_round_term(term_inputs(c)), c->M, c->P, c->sil, c->scan, c->err, verts, gate, st, nullptr);
+    const hipError_t e = launch_term(plan_round_term(term_inputs(c)), c->M, c->P, c->Q, c->sil, c->scan, c->err, verts, gate, st, nullptr);
     if (e != hipSuccess) return fail(c, MVFIT_E_HIP, "%s term launch: %s", term_name(c), hipGetErrorString(e));
     return MVFIT_OK;
 }

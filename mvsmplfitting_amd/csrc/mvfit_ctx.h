@@ -16,6 +16,7 @@
 #include "dev_mem.h"
 #include "fit_kernels.h"
 #include "fit_plan.h"
+#include "landmark.h"
 #include "launchers.h"
 #include "round_term.h"
 #include "scan_loss.h"
@@ -86,6 +87,9 @@ struct mvfit_ctx {
     DevPool vtgt_mem, vtterm_mem;      // the vertex-target set (re-made when (B, K) change) and its term's round buffers
     DevPool mix_mem;                   // the term mix's round buffers (mvfit_set_term_mix)
     DevPool scanterm_mem;              // the scan term's round buffers (mvfit_set_scan_term)
+    DevPool lmtgt_mem, lmterm_mem;     // the landmark targets (re-made when (B, V, L, 3-D or not) change) and the term's round buffers
+    // table lifetime (mvfit_set_landmarks .. the next one): the landmark table, independent of the problems
+    DevPool lmtab_mem;
     // own lifetime: one buffer each, grown (or replaced) by the call that uses it, freed with the ctx
     DevBuf sdf_faces;                  // mvfit_set_sdf: faces as the reference's caller hands them to the op
     DevBuf sdf_cull;                   // face lists of the all-faces term (sdf_term.hip), sized for (B, sdf_num_faces): goes with either
@@ -109,6 +113,8 @@ struct mvfit_ctx {
     ScanTerm scant;
     // target set and term of mvfit_set_vertex_targets / mvfit_set_vertex_target_term (vertex_target.hip)
     VtxTargets vt;
+    // table, targets and term of mvfit_set_landmarks / mvfit_set_landmark_targets / mvfit_set_landmark_term (landmark.hip)
+    LmState lm;
     // the weighted sum of the scene, silhouette, vertex-target and scan terms (mvfit_set_term_mix, term_mix.hip)
     TermMix mix;
     // ---- model ----
@@ -208,14 +214,15 @@ int ensure_sdf_buffers(mvfit_ctx* c);
 bool pass_writes_box_parts(const mvfit_ctx* c, int b_lo, int b_hi);
 // the round's term: what launch_term needs is in the plan (round_term.h) - it never sees the ctx
 TermInputs term_inputs(const mvfit_ctx* c);
-hipError_t launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, SilState& sil, ScanState& scan, std::string& err,
-                       const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part);
+hipError_t launch_term(const RoundTermPlan& plan, const DevModel& M, const DevPose& P, const DevProblems& Q, SilState& sil, ScanState& scan,
+                       std::string& err, const float* verts, const int* gate, hipStream_t st, const unsigned long long* box_part);
 int run_sdf_term(mvfit_ctx* c, const float* verts, const int* gate, hipStream_t st);
 void drop_graph(mvfit_ctx* c);
 void free_obstacles(mvfit_ctx* c);
 void free_vertex_targets(mvfit_ctx* c);
 void free_term_mix(mvfit_ctx* c);
 void free_scan_term(mvfit_ctx* c);
+void free_landmark_targets(mvfit_ctx* c);   // the targets, the term and its round buffers; the table stays
 int ensure_scan_round(mvfit_ctx* c);        // mvfit_scan.hip: the scan term's round buffers, for its own setter and for the mix
 inline const char* term_name(const mvfit_ctx* c) { return term_kind_name(term_slot(term_inputs(c))); }
 // a term other than mvfit_set_sdf's is configured: it runs in chained rounds only and keeps no per-vertex samples

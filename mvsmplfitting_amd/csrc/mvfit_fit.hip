@@ -76,7 +76,7 @@ static int ensure_round_graph(mvfit_ctx* c, const StageWeights& SW, const LbOpts
         for (int r = 0; r < kGraphRounds && e == hipSuccess; ++r) {
             e = launch_vertex_pass(c->M, Pg, c->B, c->pb.verts, c->opt.pass_kernel, cs);
             if (e == hipSuccess && c->F.sdf_adj)
-                e = launch_term(term, c->M, c->P, c->sil, c->scan, c->err, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
+                e = launch_term(term, c->M, c->P, c->Q, c->sil, c->scan, c->err, c->pb.verts, c->F.sdf_gate, cs, Pg.box_part);
             launch_fit_step(O.reuse_outer != 0, c->B, cs, c->M, c->pb.obs, c->V, SW, O, c->P, c->F);
         }
         hipError_t e2 = hipStreamEndCapture(cs, &g);

@@ -71,7 +71,7 @@ extern "C" int mvfit_set_scan_term(mvfit_ctx* c, int enable, float w_s2m, float 
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (!c->scan.on) return fail(c, MVFIT_E_STATE, "mvfit_set_scan_term: no scan set is present (mvfit_set_scans)");
     if (c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_set_scan_term: the term mix uses the ctx's term slot: switch it off first");
-    if (c->sdf_num_faces || c->obst.on || c->silt.on || c->vt.term)
+    if (c->sdf_num_faces || c->obst.on || c->silt.on || c->vt.term || c->lm.term)
         return fail(c, MVFIT_E_STATE, "mvfit_set_scan_term: the %s term uses the ctx's term slot (one term per ctx): remove it first",
                     term_name(c));
     if (c->scan.N != c->B)

@@ -186,6 +186,8 @@ extern "C" int mvfit_set_scene_obstacles(mvfit_ctx* c, const float* vertices, co
         return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->scant.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the scan term uses the ctx's term slot: switch it off first");
+    if (c->lm.term)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_scene_obstacles: the landmark term uses the ctx's term slot: switch it off first");
     if (c->nv > 8192) return fail(c, MVFIT_E_UNSUPPORTED, "the scene term supports up to 8192 vertices (model has %d)", c->nv);
     if (!scene_first || num_scenes <= 0) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: bad argument (num_scenes=%d)", num_scenes);
     if (grid_size < 2 || grid_size > 128) return fail(c, MVFIT_E_ARG, "mvfit_set_scene_obstacles: grid_size %d outside [2, 128]", grid_size);
@@ -302,6 +304,8 @@ extern "C" int mvfit_set_silhouette_term(mvfit_ctx* c, int enable, float w_in, f
         return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the vertex-target term uses the ctx's term slot: switch it off first");
     if (c->scant.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the scan term uses the ctx's term slot: switch it off first");
+    if (c->lm.term)
+        return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: the landmark term uses the ctx's term slot: switch it off first");
     if (c->sdf_num_faces || c->obst.on)
         return fail(c, MVFIT_E_STATE, "mvfit_set_silhouette_term: %s the ctx's term slot (one term per ctx): remove %s first",
                     c->obst.on ? "scene obstacles use" : "mvfit_set_sdf's term uses", c->obst.on ? "them" : "it");
@@ -442,7 +446,7 @@ extern "C" int mvfit_set_vertex_target_term(mvfit_ctx* c, int enable) {
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (!c->vt.on) return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: no target set is present (mvfit_set_vertex_targets)");
     if (c->mix.on) return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: the term mix uses the ctx's term slot: switch it off first");
-    if (c->sdf_num_faces || c->obst.on || c->silt.on || c->scant.on)
+    if (c->sdf_num_faces || c->obst.on || c->silt.on || c->scant.on || c->lm.term)
         return fail(c, MVFIT_E_STATE, "mvfit_set_vertex_target_term: the %s term uses the ctx's term slot (one term per ctx): remove it first",
                     term_name(c));
     if (const int rc = ensure_vt_round(c)) return rc;
@@ -488,7 +492,7 @@ extern "C" int mvfit_set_term_mix(mvfit_ctx* c, const mvfit_term_mix* mix) {
     if (c->B == 0) return fail(c, MVFIT_E_STATE, "call mvfit_set_problems first");
     if (c->sdf_num_faces)
         return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: mvfit_set_sdf's term uses the ctx's term slot and is not part of the mix: remove it first");
-    if (c->silt.on || c->vt.term || c->scant.on)
+    if (c->silt.on || c->vt.term || c->scant.on || c->lm.term)
         return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: the %s term is on through its own setter: switch it off first", term_name(c));
     if (lam[0] > 0.f && !c->obst.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: scene > 0 needs obstacles (mvfit_set_scene_obstacles)");
     if (lam[1] > 0.f && !c->sil.on) return fail(c, MVFIT_E_STATE, "mvfit_set_term_mix: silhouette > 0 needs a mask set (mvfit_set_silhouettes)");

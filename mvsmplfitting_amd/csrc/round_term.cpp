@@ -9,11 +9,11 @@ namespace mvfit {
 
 TermKind term_slot(const TermInputs& in) {
     return in.mix.on ? TERM_MIX : in.vt.term ? TERM_VERTEX_TARGET : in.silt.on ? TERM_SILHOUETTE : in.scan.term ? TERM_SCAN :
-           in.obst.on ? TERM_SCENE : TERM_SDF;
+           in.lm.term ? TERM_LANDMARK : in.obst.on ? TERM_SCENE : TERM_SDF;
 }
 
 const char* term_kind_name(TermKind kind) {
-    static const char* const names[] = {"sdf", "scene", "silhouette", "vertex-target", "mix", "scan"};
+    static const char* const names[] = {"sdf", "scene", "silhouette", "vertex-target", "mix", "scan", "landmark"};
     return names[kind];
 }
 
@@ -50,6 +50,12 @@ struct Builder {
         s.N = in.scan.N; s.Pmax = in.scan.Pmax; s.nf = in.scan.nf; s.ns = in.scan.ns;
         s.w_s2m = w_s2m; s.w_m2s = w_m2s; s.sigma = sigma;
         s.loss = in.scan.loss; s.g_verts = in.scan.g_verts;
+    }
+    void lm_eval() {
+        LmEvalStep& s = add(STEP_LM_EVAL).lm;
+        s.tab = in.lm.tab; s.tgt = in.lm.tgt; s.L = in.lm.L; s.nt = in.lm.nt; s.has3d = in.lm.has3d ? 1 : 0;
+        s.rho = in.lm.rho; s.w3d = in.lm.w3d; s.rho3d = in.lm.rho3d;
+        s.loss = in.lm.loss; s.g_verts = in.lm.g_verts;
     }
     void pullback(const float* g_verts, const float* loss, float* part, SdfAdj* rec) {
         PullbackStep& s = add(STEP_PULLBACK).pull;
@@ -126,6 +132,11 @@ RoundTermPlan plan_round_term(const TermInputs& in, bool live) {
         b.scan_eval(in.scan.w_s2m, in.scan.w_m2s, in.scan.sigma);
         b.pullback(in.scan.g_verts, in.scan.loss, in.scan.part, in.sdf_adj);
         b.sums_at(in.scan.loss, sizeof(float));
+        break;
+    case TERM_LANDMARK:
+        b.lm_eval();
+        b.pullback(in.lm.g_verts, in.lm.loss, in.lm.part, in.sdf_adj);
+        b.sums_at(in.lm.loss, sizeof(float));
         break;
     case TERM_SCENE:
         b.scene(in.sdf_adj);

@@ -68,17 +68,26 @@ struct TermInputs {
         float w_s2m = 0.f, w_m2s = 0.f, sigma = 0.f;
         float *g_verts = nullptr, *loss = nullptr, *part = nullptr;
     } scan;
+    struct {            // the landmark table and targets (LmState), the landmark term and its round buffers
+        bool on = false, term = false;
+        const void* tab = nullptr;
+        const float* tgt = nullptr;
+        int L = 0, nt = 0;
+        bool has3d = false;
+        float rho = 0.f, w3d = 0.f, rho3d = 0.f;
+        float *g_verts = nullptr, *loss = nullptr, *part = nullptr;
+    } lm;
 };
 
-enum TermKind { TERM_SDF = 0, TERM_SCENE, TERM_SILHOUETTE, TERM_VERTEX_TARGET, TERM_MIX, TERM_SCAN };
+enum TermKind { TERM_SDF = 0, TERM_SCENE, TERM_SILHOUETTE, TERM_VERTEX_TARGET, TERM_MIX, TERM_SCAN, TERM_LANDMARK };
 
-// who holds the term slot: the mix, else the vertex-target term, the silhouette term, the scan term, the obstacles, else
-// mvfit_set_sdf's term
+// who holds the term slot: the mix, else the vertex-target term, the silhouette term, the scan term, the landmark term, the
+// obstacles, else mvfit_set_sdf's term
 TermKind term_slot(const TermInputs& in);
 const char* term_kind_name(TermKind kind);
 
 enum StepKind { STEP_SIL_EVAL = 1, STEP_VT_EVAL, STEP_MIX_COTANGENT, STEP_PULLBACK, STEP_SCENE, STEP_MIX_RECORD, STEP_SDF,
-                STEP_SCAN_EVAL };
+                STEP_SCAN_EVAL, STEP_LM_EVAL };
 
 // sil_round: the mask set's baked values (occluders only when they are set), the scalars, the round buffers it writes
 struct SilEvalStep {
@@ -147,6 +156,17 @@ struct ScanEvalStep {
     float *loss, *g_verts;
 };
 
+// launch_landmarks: the table and the targets (each one buffer whose layout follows from the sizes), the scalars, the round
+// buffers it writes; the cameras are the problems' and come with the round
+struct LmEvalStep {
+    const void* tab;
+    const float* tgt;
+    int L, nt, has3d;
+    float rho, w3d, rho3d;
+    float *loss, *g_verts;
+};
+static_assert(sizeof(LmEvalStep) <= sizeof(SilEvalStep), "the plan's step union keeps its size");
+
 struct TermStep {
     int kind;           // StepKind
     union {
@@ -158,6 +178,7 @@ struct TermStep {
         MixRecordStep rec;
         SdfStep sdf;
         ScanEvalStep scan;
+        LmEvalStep lm;
     };
 };
 

@@ -129,6 +129,8 @@ class MvFit:
         self._mix = None                         # the shares of set_term_mix while it is on
         self._scan_shape = None                  # (N, Pmax) of set_scans while a scan set is present
         self._scan_term = False
+        self._lm_L = 0                           # landmarks of set_landmarks while a table is present
+        self._lm_term = False
 
     # ------------------------------------------------------------------ options (include/mvfit.h:mvfit_options)
     def _options_struct(self, values: dict, base=None):
@@ -232,6 +234,7 @@ class MvFit:
             self._vt_term = False                # (and clears the vertex targets with their term)
             self._mix = None                     # (and switches the term mix off)
             self._scan_term = False              # (and the scan term; the scan set stays)
+            self._lm_term = False                # (and the landmark targets with their term; the table stays)
         self.B, self.V = B, V
 
     def set_joints3d(self, gt3d, conf3d):
@@ -638,6 +641,88 @@ class MvFit:
             return loss, g, nf, npt
         return loss, g
 
+    # ------------------------------------------------------------------ surface landmarks (include/mvfit.h:mvfit_set_landmarks)
+    def set_landmarks(self, vertex_ids, weights=None):
+        """Keep the landmark table (include/mvfit.h:mvfit_set_landmarks): vertex_ids [L,4] int and weights [L,4], landmark l at
+        sum_k weights[l,k] * V[vertex_ids[l,k]]; fewer than 4 columns are padded with dead slots (weight 0, never read).  A 1-D
+        vertex_ids means one vertex per landmark with weight 1.  1 <= L <= 256.  The table is independent of the problems; a
+        new table clears the targets and the term."""
+        ids = np.asarray(vertex_ids.detach().cpu().numpy() if isinstance(vertex_ids, torch.Tensor) else vertex_ids)
+        if ids.ndim == 1 and weights is None:
+            ids = ids.reshape(-1, 1)
+            w = np.ones(ids.shape, np.float32)
+        else:
+            if weights is None:
+                raise MvFitError('set_landmarks: weights are needed with vertex_ids of %d dimensions' % ids.ndim)
+            w = np.asarray(weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else weights, np.float32)
+        if ids.ndim != 2 or ids.shape != w.shape or not 1 <= ids.shape[1] <= 4:
+            raise MvFitError('set_landmarks: vertex_ids and weights must both be [L, 1..4], got %r and %r' % (ids.shape, w.shape))
+        L, k = ids.shape
+        ids4 = np.zeros((L, 4), np.int32); ids4[:, :k] = ids
+        w4 = np.zeros((L, 4), np.float32); w4[:, :k] = w
+        if L == 0:
+            raise MvFitError('set_landmarks: an empty table (clear_landmarks() removes one)')
+        rc = self._lib.mvfit_set_landmarks(self._ctx, L, ids4.ctypes.data_as(_lib._ip), w4.ctypes.data_as(_lib._fp))
+        if rc != -1:                             # (set, or a failed allocation: no targets and no term; an argument error keeps all)
+            self._lm_term = False
+            self._lm_L = L if rc == 0 else 0
+        self._check(rc)
+
+    def clear_landmarks(self):
+        """Remove the table of set_landmarks, the targets and the term."""
+        self._check(self._lib.mvfit_set_landmarks(self._ctx, 0, None, None))
+        self._lm_L = 0
+        self._lm_term = False
+
+    def set_landmark_targets(self, xy, conf, xyz=None, conf3=None):
+        """The targets of the current problems (include/mvfit.h:mvfit_set_landmark_targets): xy [B,V,L,2] pixels and conf
+        [B,V,L] finite and >= 0; optionally, together, xyz [B,L,3] world positions and conf3 [B,L].  An entry of confidence 0 is
+        never read and may hold NaN.  A second call at the same sizes keeps the library's buffers (and the captured round
+        graph)."""
+        if (xyz is None) != (conf3 is None):
+            raise MvFitError('set_landmark_targets: xyz and conf3 come together')
+        L = self._lm_L
+        t = [self._dev(xy, (self.B, self.V, L, 2)), self._dev(conf, (self.B, self.V, L))]
+        if xyz is not None:
+            t += [self._dev(xyz, (self.B, L, 3)), self._dev(conf3, (self.B, L))]
+        p = [x.data_ptr() for x in t] + [None, None]
+        rc = self._lib.mvfit_set_landmark_targets(self._ctx, p[0], p[1], p[2], p[3])
+        if rc not in (0, -1, -3):                # (a failed allocation: no targets and no term)
+            self._lm_term = False
+        self._check(rc)
+
+    def clear_landmark_targets(self):
+        """Remove the targets of set_landmark_targets (and switch their term off); the table stays."""
+        self._check(self._lib.mvfit_set_landmark_targets(self._ctx, None, None, None, None))
+        self._lm_term = False
+
+    def landmark_loss(self, vertices, rho=100.0, w3d=0.0, rho3d=0.0, need_grad=True):
+        """The landmark loss at vertices[B,Nv,3], translation included (include/mvfit.h:mvfit_landmark_loss): the robust
+        (GMoF, rho in pixels; 0: plain squares) reprojection error of every landmark in every view, weighted by conf^2, plus
+        w3d times the same on the 3-D targets (rho3d in the vertices' unit).  Returns (loss[B], g_vertices[B,Nv,3] or None)."""
+        v = self._dev(vertices)
+        if tuple(v.shape) != (self.B, self.nv, 3):
+            raise MvFitError('vertices must be [%d, %d, 3], got %r' % (self.B, self.nv, tuple(v.shape)))
+        loss = torch.empty(self.B, device=self.device)
+        g = torch.empty_like(v) if need_grad else None
+        self._check(self._lib.mvfit_landmark_loss(self._ctx, v.data_ptr(), float(rho), float(w3d), float(rho3d), loss.data_ptr(),
+                                                  g.data_ptr() if need_grad else None))
+        return loss, g
+
+    def set_landmark_term(self, rho=100.0, w3d=0.0, rho3d=0.0):
+        """Make the landmark loss of the current targets a term of closure() and fit() (include/mvfit.h:
+        mvfit_set_landmark_term): a stage with coll_loss_weight w > 0 adds w^2 * L_j to problem j, L_j = landmark_loss(rho, w3d,
+        rho3d) of the trial point's vertices, with its gradient through the model.  fit() runs such stages as chained rounds.
+        Needs set_landmark_targets; excludes set_sdf's term, scene obstacles, the silhouette, vertex-target and scan terms and
+        the term mix.  A second call with other scalars replaces them."""
+        self._check(self._lib.mvfit_set_landmark_term(self._ctx, 1, float(rho), float(w3d), float(rho3d)))
+        self._lm_term = True
+
+    def clear_landmark_term(self):
+        """Switch the term of set_landmark_term off (table and targets stay)."""
+        self._check(self._lib.mvfit_set_landmark_term(self._ctx, 0, 0.0, 0.0, 0.0))
+        self._lm_term = False
+
     def round_graph_info(self, drop=False):
         """dict(builds = round graphs captured on this engine so far, occluder_buffers = the device addresses of z_occ, z_own
         and point_flag, 0 before the first freeze) (include/mvfit.h:mvfit_round_graph_info).  drop=True drops the captured
@@ -1014,9 +1099,9 @@ class MvFit:
     def sdf_term_read(self):
         """(samples [B,Nv,4] = phi_v and its local-coordinate gradient, S [B]) of the last evaluated term.  The scene term
         (set_scene_obstacles) keeps no per-vertex samples: (None, S) while it is set; so does the silhouette term
-        (set_silhouette_term), the vertex-target term (set_vertex_target_term) and the scan term (set_scan_term), whose S is
+        (set_silhouette_term), the vertex-target term (set_vertex_target_term), the scan term (set_scan_term) and the landmark term (set_landmark_term), whose S is
         the loss L_j itself, and the term mix (set_term_mix), whose S is the weighted sum of its parts."""
-        smp = None if (self._obstacles or self._sil_term or self._vt_term or self._mix or self._scan_term) else torch.empty(self.B, self.nv, 4, device=self.device)
+        smp = None if (self._obstacles or self._sil_term or self._vt_term or self._mix or self._scan_term or self._lm_term) else torch.empty(self.B, self.nv, 4, device=self.device)
         S = torch.empty(self.B, device=self.device)
         self._check(self._lib.mvfit_sdf_term_read(self._ctx, None if smp is None else smp.data_ptr(), S.data_ptr()))
         return smp, S

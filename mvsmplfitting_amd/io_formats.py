@@ -7,6 +7,7 @@ and fitted parameters written the way the reference's tools read them.
   read_keypoints     OpenPose-style json {"people":[{"pose_keypoints_2d":[51 floats]}]} -> per person [17,3] float32
                      (reference code/utils/data_parser.py:42-90 with use_hands=False, use_face=False, the
                      'smpllsp' / halpe-17 configuration of fit_smpl.yaml)
+  read_people_extra  the rows of ``pose_keypoints_2d`` those readers drop (a Halpe-26 file's foot points, rows 20-25), per person
   read_joints3d      {"people":[{"pose_keypoints_3d":[...]}]} -> per person [-1,4] float32 (data_parser.py:93-109)
   problem_tensors    one rig + per-view keypoints -> (cams, gt_xy, conf) of MvFit.set_problems, fx for both axes
                      like the reference camera (code/init.py:113-119)
@@ -105,6 +106,34 @@ def read_people(path):
     associate.associate_serial (batch.fit_folder(associate=...)), which finds the persons across views and frames.
     Two entries with one id: ValueError naming the file."""
     return _read_people(path, 'pose_keypoints_2d', 3)
+
+
+def read_people_extra(path, rows, by_index=False):
+    """{person id: [len(rows), 3] float32 (x, y, confidence)}: the rows ``rows`` of every person's ``pose_keypoints_2d``,
+    those that read_keypoints and read_people drop included (a whole-body detector's foot, hand and face points; Halpe-26
+    keeps both big toes, small toes and heels in rows 20-25).  Ids by read_people's rule, or - by_index - the entry's index
+    in the list whatever ``person_id`` says (the single-person and the associate= paths count that way).  A file with fewer
+    rows gives zeros, i.e. confidence 0, for the missing ones.  Like read_people, an entry whose first 17 confidences are all zero counts as absent (by_index:
+    every entry is listed)."""
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    if (rows < 0).any():
+        raise ValueError('read_people_extra: negative row')
+    with open(path) as f:
+        people = json.load(f)['people']
+    by_id = not by_index and all(isinstance(p.get('person_id'), int) and not isinstance(p.get('person_id'), bool) for p in people)
+    out = {}
+    for k, p in enumerate(people):
+        a = np.array(p['pose_keypoints_2d'], dtype=np.float32).reshape([-1, 3])
+        if not by_index and not a[:17, 2].any():           # read_people's rule: the person is not in this file
+            continue
+        got = np.zeros((rows.size, 3), np.float32)
+        ok = rows < a.shape[0]
+        got[ok] = a[rows[ok]]
+        pid = int(p['person_id']) if by_id else k
+        if pid in out:
+            raise ValueError('%s lists person %d twice' % (path, pid))
+        out[pid] = got
+    return out
 
 
 def read_people3d(path):
